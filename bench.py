@@ -31,6 +31,7 @@ WORKLOADS = {
     "tiny": (5, 16, 16),
 }
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: all .npy files together
 
 
 def step_flops(s_img, s_txt, d=3072, n_double=20, n_single=40):
@@ -114,6 +115,22 @@ def cpu_baseline(f_step, seconds_budget=30.0):
             "block_check": block_check, **legs}
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write each output of the timed leg's last step as <out_dir>/<name>.npy in float32.  An output larger than its
+    share of DUMP_BUDGET_BYTES is written as a fixed, seeded sample of its flattened elements (the same indices on every run of the
+    same workload), so that two builds can be compared value for value."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_BUDGET_BYTES // len(arrays) - 4096) // 4          # float32 elements per output (4 KB left for the .npy header)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if a.numel() > share:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+
+
 def launch_ranks(n: int) -> int:
     """`python bench.py --gpus N` from a cold shell (no RANK in the environment): start N rank processes, one per GPU, as fresh
     children of THIS process - which never imports torch or touches HIP, so nothing that initialised the GPU ever execs - with
@@ -167,7 +184,12 @@ def main():
                     "default single-GPU 720p129f run appends after its timed leg")
     ap.add_argument("--secondary-budget", type=float, default=150.0, help="wall-clock seconds the secondary workloads may take in total")
     ap.add_argument("--no-vae", action="store_true", help="skip the (untimed-by-`value`) VAE tiled decode of the same video")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "returned (latents = scheduler output, noise_pred = transformer output) as DIR/<name>.npy in float32 "
+                    "(rank 0; at most 64 MB in all, a fixed seeded sample of larger outputs)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "RANK" not in os.environ:
         # cold shell: become the launcher (before torch is imported; this process never touches the GPU)
@@ -231,7 +253,7 @@ def main():
 
     def run_leg(workload, steps, warmup):
         """W untimed + K timed denoise steps of `workload` on the model as it stands; returns (seconds for the K steps on this rank,
-        [(ms, flop)] of the main-segment attention launches inside the timed region, final latents)."""
+        [(ms, flop)] of the main-segment attention launches inside the timed region, final latents, transformer output of the last step)."""
         lt, lh, lw = WORKLOADS[workload]
         x, ts, tm, ts2 = syn.synth_dit_inputs(cfg, (lt, lh, lw), s_txt, 11, seed=42, device=dev)
         ts = ts.to(torch.bfloat16)
@@ -245,24 +267,27 @@ def main():
             t = sched.timesteps[i]
             v = model(lat, t.repeat(1), text_states=ts, text_mask=tm, text_states_2=ts2, freqs_cos=cos, freqs_sin=sin,
                       guidance=guidance, return_dict=True)["x"]
-            return sched.step(v, t, lat, return_dict=False)[0]
+            return sched.step(v, t, lat, return_dict=False)[0], v
 
         with torch.no_grad():
             for i in range(warmup):
-                lat = one_step(i, lat)
+                lat, v = one_step(i, lat)
             barrier()
             ops.PROFILE_ATTN = []          # HIP events around every main-segment attention launch, on the launch stream
             t0 = time.perf_counter()
             for i in range(warmup, n_total):
-                lat = one_step(i, lat)
+                lat, v = one_step(i, lat)
             barrier()
             el = time.perf_counter() - t0
         prof, ops.PROFILE_ATTN = ops.PROFILE_ATTN, None
         att = [(e0.elapsed_time(e1), 4.0 * nq * nkv * 128 * nh) for e0, e1, nq, nkv, nh in prof if nkv > 1024 or workload == "tiny"]
         assert bool(torch.isfinite(lat).all()), f"non-finite latents ({workload})"
-        return el, att, lat
+        return el, att, lat, v
 
-    elapsed, att, lat = run_leg(a.workload, a.steps, a.warmup)
+    elapsed, att, lat, noise_pred = run_leg(a.workload, a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"latents": lat, "noise_pred": noise_pred})
+    del noise_pred
     att_ms, att_flop = [m for m, _ in att], [f for _, f in att]
 
     # Secondary workloads (BASELINE.json configs 2, 5 and 4) on the same model, AFTER the timed headline leg and never part of
@@ -273,7 +298,7 @@ def main():
         ms129 = elapsed / a.steps * 1e3
 
         def leg_entry(workload, steps, warmup, dtype, note=None):
-            el, at, _ = run_leg(workload, steps, warmup)
+            el, at, _, _ = run_leg(workload, steps, warmup)
             lt, lh, lw = WORKLOADS[workload]
             si = lt * (lh // 2) * (lw // 2)
             fs = step_flops(si, s_txt, cfg.hidden_size, cfg.mm_double_blocks_depth, cfg.mm_single_blocks_depth)
