@@ -15,6 +15,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 typedef uint16_t bf16_t;  // storage type in HBM / LDS
 
@@ -84,4 +85,13 @@ static inline int hv_set_max_lds(HvPerDeviceOnce& once, const void* fn, int byte
 static inline int hv_check_launch() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? HV_OK : HV_ERR_LAUNCH;
+}
+
+// (lo, hi) fp16 halves of w minus fp32 pivots, widened and subtracted in one v_fma_mix_f32 each (exact for fp16 values and fp16
+// pivots; the compiler emits a convert and a subtract): the shifted moments of the GroupNorm statistics at the cost of plain ones
+__device__ __forceinline__ f32x2 f16x2_minus(uint32_t w, float plo, float phi) {
+    float lo, hi;
+    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(w), "v"(plo));
+    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(hi) : "v"(w), "v"(phi));
+    return f32x2{lo, hi};
 }

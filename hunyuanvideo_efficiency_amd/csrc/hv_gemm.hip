@@ -108,8 +108,9 @@ struct GemmArgs {
     // parity class c (sp_rows[c] class-local rows = source-grid voxels), weights [class][N][sp_ntap * cin], tap offsets from sp_tab
     int sp_tile0[9], sp_rows[8], sp_ntap;
     const uint32_t* sp_tab;   // [class][sp_ntap]: (ot + 8) | (oh + 8) << 4 | (ow + 8) << 8, source voxel = clamp(class voxel + offset)
-    // GroupNorm statistics of the OUTPUT, taken in the epilogue from the values it stores: gn_partial[b][n][2] = (sum, sum of squares)
-    // over the valid rows of 64-row block b (b = tile * 4 + wave row block), one writer per entry, fixed order: run-to-run identical
+    // GroupNorm statistics of the OUTPUT, taken in the epilogue from the values it stores, per 64-row block b (b = tile * 4 + wave row
+    // block) and pair of columns (n, n+1) over its valid rows: gn_partial[b][n] = (sum, centred sum of squares), gn_partial[b][n+1] =
+    // (0, count); one writer per entry, fixed order: run-to-run identical
     float* gn_partial;
 };
 
@@ -188,15 +189,18 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[MR
         uint16_t* obase = second ? g.out1 + (n - g.n_split) : g.out0 + n;
         const int64_t ldo = second ? g.ld1 : g.ld0;
         const int act = second ? g.act1 : g.act0;
-        // GroupNorm statistics (fp16 outputs only): per 64-row block and per PAIR of adjacent columns, (sum, sum of squares) of the
-        // stored fp16 values by v_dot2_f32_f16 on the packed words the store uses - [0..3] sums, [4..7] squares of pairs 0..3
+        // GroupNorm statistics (fp16 outputs only): per 64-row block and per PAIR of adjacent columns, the sum of the stored fp16
+        // values (v_dot2_f32_f16 on the packed words the store uses) and the sum of squares of the same values SHIFTED by a pivot -
+        // the pair's even column in the block's first row (lane fr = 0 of the 16 that share fq, m-repeat 4 bq: every call site maps
+        // the block's rows contiguously from there).  Raw fp32 sums of squares would cancel against the mean (relative error
+        // ~2^-24 R^2 in the variance, R = |mean| / std); the shifted ones see R of order one.
         constexpr bool GN = std::is_same<DT, F16T>::value;
         constexpr int NGB = MREP / 4;             // 64-row blocks this wave covers (4 m-repeats x 16 lanes each)
-        float gst[NGB][8];
+        float gst[NGB][4], piv[NGB][4], gsq[NGB][8];       // gsq: (lo, hi) column of each pair
 #pragma unroll
         for (int bq = 0; bq < NGB; ++bq)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) gst[bq][j] = 0.f;
+            for (int j = 0; j < 4; ++j) gst[bq][j] = 0.f, gsq[bq][2 * j] = gsq[bq][2 * j + 1] = 0.f;
 #pragma unroll
         for (int mi = 0; mi < MREP; ++mi) {
             const int m = mrow0 + mi * MSTEP;
@@ -237,17 +241,26 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[MR
             for (int i = 0; i < 4; ++i) w[i] = DT::pack(v[2 * i], v[2 * i + 1]);
             if (m < g.M) *reinterpret_cast<u32x4*>(obase + orow[mi] * ldo) = w;
             if constexpr (GN) {
-                if (g.gn_partial && m < g.M) {
-                    typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-                    const h2_t one = {(_Float16)1.0f, (_Float16)1.0f};
+                if (g.gn_partial) {
+                    if (mi % 4 == 0) {            // all 64 lanes: the block's pivots from its first row (a clamped row if the block is empty)
+                        const int src = threadIdx.x & 48;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        // (not __builtin_bit_cast(h2_t, w[i]): on an element of an ext_vector it reads element 0 for every i - hipcc 7.2)
-                        const uint32_t wi = w[i];
-                        h2_t hv;
-                        __builtin_memcpy(&hv, &wi, 4);
-                        gst[mi / 4][i] = __builtin_amdgcn_fdot2(hv, one, gst[mi / 4][i], false);
-                        gst[mi / 4][4 + i] = __builtin_amdgcn_fdot2(hv, hv, gst[mi / 4][4 + i], false);
+                        for (int i = 0; i < 4; ++i) piv[mi / 4][i] = DT::lo((uint32_t)__shfl((int)w[i], src, 64));
+                    }
+                    if (m < g.M) {
+                        typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+                        const h2_t one = {(_Float16)1.0f, (_Float16)1.0f};
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            // (not __builtin_bit_cast(h2_t, w[i]): on an element of an ext_vector it reads element 0 for every i - hipcc 7.2)
+                            const uint32_t wi = w[i];
+                            h2_t hv;
+                            __builtin_memcpy(&hv, &wi, 4);
+                            gst[mi / 4][i] = __builtin_amdgcn_fdot2(hv, one, gst[mi / 4][i], false);
+                            const f32x2 d = f16x2_minus(wi, piv[mi / 4][i], piv[mi / 4][i]);       // exact: fp16 - fp16
+                            const f32x2 q = d * d + f32x2{gsq[mi / 4][2 * i], gsq[mi / 4][2 * i + 1]};
+                            gsq[mi / 4][2 * i] = q.x, gsq[mi / 4][2 * i + 1] = q.y;
+                        }
                     }
                 }
             }
@@ -257,8 +270,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[MR
                 // The 16 lanes that share fq hold the rows of these 8 columns (all 16 took the same `n < N` branch).  Butterfly
                 // transpose-reduction over lane bits 3..1: each step a lane keeps half of its values and receives the partner's copy
                 // of that half (8 -> 4 -> 2 -> 1 values), then one plain exchange over bit 0: 8 shuffles instead of 32.  Lane pair
-                // q = fr >> 1 ends up with value q = [square?][pair].  gn_partial[b][n .. n+7][2]: the pair's total goes to its
-                // even column, the odd column's slot is zero (a GroupNorm group holds whole pairs: C / groups is even).
+                // q = fr >> 1 ends up with value q = [square?][pair]; one more exchange over bit 3 brings (sum, square sum) of the
+                // pair together.  gn_partial[b][n .. n+7][2]: the even column of a pair gets (S = sum x, C2 = sum (x - S/k)^2) of its k
+                // values, the odd one (0, k) (a GroupNorm group holds whole pairs: C / groups is even).  C2 comes from the shifted sums,
+                // whose mean is within a few block std of zero: no cancellation; hv_groupnorm_finalize_f16 rebuilds sum x^2 in fp64.
                 const int fr_ = threadIdx.x & 15;
 #pragma unroll
                 for (int bq = 0; bq < NGB; ++bq) {
@@ -266,7 +281,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[MR
                     const bool b3 = fr_ & 8, b2 = fr_ & 4, b1 = fr_ & 2;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const float keep = b3 ? gst[bq][4 + i] : gst[bq][i], send = b3 ? gst[bq][i] : gst[bq][4 + i];
+                        const float sq = gsq[bq][2 * i] + gsq[bq][2 * i + 1];
+                        const float keep = b3 ? sq : gst[bq][i], send = b3 ? gst[bq][i] : sq;
                         a4[i] = keep + __shfl_xor(send, 8, 64);
                     }
 #pragma unroll
@@ -281,8 +297,28 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[MR
                     a1 += __shfl_xor(a1, 1, 64);
                     // value held: square = b3, pair = 2*b2 + b1
                     const int pair = (b2 ? 2 : 0) + (b1 ? 1 : 0);
+                    const float other = __shfl_xor(a1, 8, 64);
+                    const float sx = b3 ? other : a1, qd = b3 ? a1 : other;        // sum x, sum (x - p)^2
+                    int cnt = 0;                  // valid rows of the block: this lane's, then summed over the 16
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) cnt += mrow0 + (4 * bq + j) * MSTEP < g.M ? 1 : 0;
+                    cnt += __shfl_xor(cnt, 8, 64);
+                    cnt += __shfl_xor(cnt, 4, 64);
+                    cnt += __shfl_xor(cnt, 2, 64);
+                    cnt += __shfl_xor(cnt, 1, 64);
+                    const float k = (float)(2 * cnt);
+                    float pv0 = piv[bq][0], pv1 = piv[bq][1], pv2 = piv[bq][2], pv3 = piv[bq][3];
+                    asm("" : "+v"(pv0), "+v"(pv1), "+v"(pv2), "+v"(pv3));     // (a select of array elements made piv a scratch array)
+                    const float p = b2 ? (b1 ? pv3 : pv2) : (b1 ? pv1 : pv0);
+                    // C2 = sum (x - p)^2 - (sum (x - p))^2 / k: sum (x - p) = S - k p is of the order of sqrt(k) block std, the fp32
+                    // rounding of S (~2^-24 k |mean|) enters C2 only to first order in R
+                    const float sd = sx - k * p;
+                    float val;
+                    if (fr_ & 1) val = b3 ? k : 0.f;
+                    else if (cnt == 0) val = 0.f;
+                    else val = b3 ? fmaxf(qd - sd * sd * __builtin_amdgcn_rcpf(k), 0.f) : sx;
                     float* o = g.gn_partial + ((int64_t)(gn_blk0 + bq) * g.N + n + 2 * pair + (fr_ & 1)) * 2 + (b3 ? 1 : 0);
-                    *o = (fr_ & 1) ? 0.f : a1;
+                    *o = val;
                 }
             }
         }

@@ -23,16 +23,37 @@ __device__ __forceinline__ u32x4 pack8h(const float (&f)[8]) {
     return w;
 }
 
-// ---- GroupNorm pass 1: per-workgroup partial (sum, sumsq) per channel.  256 threads = (C/8) channel-threads x
-// (2048/C) row lanes; partial[blk][c][2] fp32.
+// ---- GroupNorm pass 1: per-workgroup partial (sum, sumsq) per channel of the SHIFTED values d = x - x[0][first channel of the
+// group]: one-pass moments of x itself lose the variance to cancellation (fp32 rounding of sum x^2 ~ n 2^-24 (mean^2 + var) against
+// n var), the shift leaves |mean_d| / std of the order of one sample's distance from the mean.  256 threads = (C/8) channel-threads
+// x (2048/C) row lanes; partial[blk][c][2] fp32; gn_finalize_kernel adds the pivot back.
 __global__ __launch_bounds__(256) void gn_partial_kernel(const uint16_t* __restrict__ x, int64_t ldx, int64_t M, int C,
-                                                          float* __restrict__ partial, int rows_per_blk) {
+                                                          int groups, float* __restrict__ partial, int rows_per_blk) {
     extern __shared__ float red[];   // [row lanes][C][2]
     const int cthreads = C >> 3;
     const int ct = threadIdx.x % cthreads, rl = threadIdx.x / cthreads, nrl = 256 / cthreads;
-    float s[8], q[8];
+    const int cpg = C / groups;
+    f32x2 s[4], q[4];
+    float pv[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
+    for (int j = 0; j < 8; ++j) {            // the group's pivot: row 0, first channel (as gn_finalize_kernel); c / cpg without a divide
+        const int c = ct * 8 + j;
+        pv[j] = h2f(x[(int)(((float)c + 0.5f) * (1.0f / (float)cpg)) * cpg]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] = q[i] = f32x2{0.f, 0.f};
+    // shifted values of 8 channels in plain C (exact: fp16 - fp16): inline asm here kept the compiler from issuing the four loads
+    // of a step before the first use - one or two in flight instead of four, +37 % on this latency-bound loop
+    auto acc = [&](const u32x4& w) {
+        float v[8];
+        unpack8h(w, v);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f32x2 d = f32x2{v[2 * i], v[2 * i + 1]} - f32x2{pv[2 * i], pv[2 * i + 1]};
+            s[i] += d;
+            q[i] = d * d + q[i];
+        }
+    };
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_blk;
     const int64_t r1 = min(M, r0 + rows_per_blk);
     if (rl < nrl) {
@@ -46,29 +67,15 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const uint16_t* __restr
 #pragma unroll
             for (int u = 0; u < 4; ++u) w[u] = *reinterpret_cast<const u32x4*>(xp + u * xs);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                float v[8];
-                unpack8h(w[u], v);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    s[j] += v[j];
-                    q[j] += v[j] * v[j];
-                }
-            }
+            for (int u = 0; u < 4; ++u) acc(w[u]);
         }
-        for (; r < r1; r += nrl, xp += xs) {
-            float v[8];
-            unpack8h(*reinterpret_cast<const u32x4*>(xp), v);
+        for (; r < r1; r += nrl, xp += xs) acc(*reinterpret_cast<const u32x4*>(xp));
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                s[j] += v[j];
-                q[j] += v[j] * v[j];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            red[(rl * C + ct * 8 + j) * 2] = s[j];
-            red[(rl * C + ct * 8 + j) * 2 + 1] = q[j];
+        for (int i = 0; i < 4; ++i) {
+            red[(rl * C + ct * 8 + 2 * i) * 2] = s[i].x;
+            red[(rl * C + ct * 8 + 2 * i) * 2 + 1] = q[i].x;
+            red[(rl * C + ct * 8 + 2 * i + 1) * 2] = s[i].y;
+            red[(rl * C + ct * 8 + 2 * i + 1) * 2 + 1] = q[i].y;
         }
     }
     __syncthreads();
@@ -83,11 +90,23 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const uint16_t* __restr
     }
 }
 
-// ---- GroupNorm pass 2: fold the partials [nrow][C][2] in fp64 -> per-channel affine y = x*sc[c] + sh[c].  One block per group
-// (a single block folding all groups took 90-160 us on the large activations: more than the HBM pass over the activation it
-// follows); partial rows come from gn_partial_kernel (<= 1024 rows) or from a conv epilogue (one row per 64 output rows).
+// Affine of one group from its mean and (clamped, >= 0) variance, both fp64: the shift is taken against the fp32 scale the apply
+// pass multiplies by, so x*sc + sh cancels the mean to within one fp32 rounding of sh (|mean| * sc * 2^-24).
+__device__ __forceinline__ void gn_affine_out(double mean, double var, float eps, int c0, int c1, int step,
+                                              const uint16_t* __restrict__ w, const uint16_t* __restrict__ b, float* __restrict__ affine) {
+    const double rstd = 1.0 / sqrt((var < 0.0 ? 0.0 : var) + (double)eps);
+    for (int c = c0; c < c1; c += step) {
+        const float sc = (float)(rstd * (double)h2f(w[c]));
+        affine[2 * c] = sc;
+        affine[2 * c + 1] = (float)((double)h2f(b[c]) - mean * (double)sc);
+    }
+}
+
+// ---- GroupNorm pass 2 of hv_groupnorm_affine_f16: fold the shifted partials of gn_partial_kernel [nrow <= 1024][C][2] in fp64 ->
+// per-channel affine y = x*sc[c] + sh[c].  One block per group (a single block folding all groups took 90-160 us on the large
+// activations: more than the HBM pass over the activation it follows).  mean = pivot + sum d / n, var = sum d^2 / n - (sum d / n)^2.
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ partial, int64_t nrow, int C, int groups,
-                                                           int64_t M, float eps, const uint16_t* __restrict__ w,
+                                                           const uint16_t* __restrict__ x, int64_t M, float eps, const uint16_t* __restrict__ w,
                                                            const uint16_t* __restrict__ b, float* __restrict__ affine) {
     __shared__ double ws[4], wq[4];
     const int cpg = C / groups, g = blockIdx.x;
@@ -121,20 +140,28 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
     s = (ws[0] + ws[1]) + (ws[2] + ws[3]);
     q = (wq[0] + wq[1]) + (wq[2] + wq[3]);
     const double n = (double)M * cpg;
-    const double mean = s / n;
-    double var = q / n - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    for (int c = g * cpg + threadIdx.x; c < (g + 1) * cpg; c += 256) {
-        const float wc = h2f(w[c]), bc = h2f(b[c]);
-        affine[2 * c] = rstd * wc;
-        affine[2 * c + 1] = bc - (float)mean * rstd * wc;
-    }
+    const double md = s / n;
+    gn_affine_out((double)h2f(x[g * cpg]) + md, q / n - md * md, eps, g * cpg + threadIdx.x, (g + 1) * cpg, 256, w, b, affine);
 }
 
-// ---- the same fold in two levels for the long partial lists a conv epilogue leaves (one row per 64 output rows: 66,560 rows for the
-// 65 x 256 x 256 activations): block (g, s) folds every S-th 256-row slab of group g's columns into one fp64 pair, gn_finalize2 folds
-// the S pairs in index order.  Fixed assignment and order: run-to-run identical.
+// ---- hv_groupnorm_finalize_f16: the fold in two levels of the long partial lists a conv epilogue leaves (one row per 64 output rows:
+// 66,560 rows for the 65 x 256 x 256 activations).  An epilogue entry describes one (64-row block, column pair): the even column holds
+// (S = sum x, C2 = sum (x - S/k)^2), the odd one (0, k = number of values).  The fold turns it back into raw moments in fp64,
+// sum x^2 = C2 + S^2 / k, where the cancellation of var = Q/n - mean^2 costs 2^-53 (1 + R^2) (R = |mean| / std of the group) instead
+// of the 2^-24 (1 + R^2) of fp32 sums of squares; the fp32 rounding of S enters only to first order (the between-block part of the
+// variance is rebuilt from the same rounded S).  Block (g, s) folds every S-th 256-row slab of group g's columns into one fp64 pair,
+// gn_finalize2 folds the S pairs in index order.  Fixed assignment and order: run-to-run identical.
+__device__ __forceinline__ void gn_entry_moments(const float4& v, double& s, double& q) {
+    const double sx = (double)v.x;
+    s += sx;
+    // 1/k without a divide: v_rcp_f32 (1 ulp) and two Newton steps in fp64 (2^-46, then fp64-exact for these small integers)
+    const double k = (double)v.w;
+    double inv = (double)__builtin_amdgcn_rcpf(v.w);
+    inv = inv * (2.0 - k * inv);
+    inv = inv * (2.0 - k * inv);
+    q += (double)v.y + (v.w > 0.f ? sx * sx * inv : 0.0);
+}
+
 __global__ __launch_bounds__(256) void gn_fold_kernel(const float* __restrict__ partial, int64_t nrow, int C, int groups,
                                                        double* __restrict__ tmp) {
     __shared__ double ws[4], wq[4];
@@ -143,14 +170,7 @@ __global__ __launch_bounds__(256) void gn_fold_kernel(const float* __restrict__ 
     double s = 0.0, q = 0.0;
     for (int64_t r = (int64_t)blockIdx.y * 256 + threadIdx.x; r < nrow; r += (int64_t)S * 256) {
         const float4* row = reinterpret_cast<const float4*>(p + r * C * 2);           // cpg even (host-checked): 16-B pieces
-        float fs = 0.f, fq = 0.f;
-        for (int c = 0; c < cpg / 2; ++c) {
-            const float4 v = row[c];
-            fs += v.x + v.z;
-            fq += v.y + v.w;
-        }
-        s += (double)fs;
-        q += (double)fq;
+        for (int c = 0; c < cpg / 2; ++c) gn_entry_moments(row[c], s, q);
     }
     for (int o = 32; o > 0; o >>= 1) {
         s += __shfl_xor(s, o, 64);
@@ -174,9 +194,7 @@ __global__ __launch_bounds__(256) void gn_fold_rows_kernel(const float* __restri
     const int cv = C >> 1, ct = threadIdx.x % cv, rl = threadIdx.x / cv, nrl = 256 / cv, S = gridDim.x;
     double s = 0.0, q = 0.0;
     for (int64_t r = (int64_t)blockIdx.x * nrl + rl; r < nrow; r += (int64_t)S * nrl) {
-        const float4 v = reinterpret_cast<const float4*>(partial + r * C * 2)[ct];
-        s += (double)(v.x + v.z);
-        q += (double)(v.y + v.w);
+        gn_entry_moments(reinterpret_cast<const float4*>(partial + r * C * 2)[ct], s, q);
     }
     sm[threadIdx.x][0] = s, sm[threadIdx.x][1] = q;
     __syncthreads();
@@ -204,14 +222,7 @@ __global__ __launch_bounds__(64) void gn_finalize2_kernel(const double* __restri
     }
     const double n = (double)M * cpg;
     const double mean = s / n;
-    double var = q / n - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    for (int c = g * cpg + threadIdx.x; c < (g + 1) * cpg; c += 64) {
-        const float wc = h2f(w[c]), bc = h2f(b[c]);
-        affine[2 * c] = rstd * wc;
-        affine[2 * c + 1] = bc - (float)mean * rstd * wc;
-    }
+    gn_affine_out(mean, q / n - mean * mean, eps, g * cpg + threadIdx.x, (g + 1) * cpg, 64, w, b, affine);
 }
 
 // ---- GroupNorm pass 3: y = [silu](x*sc + sh) -> fp16.  HBM-bound (read + write of the activation): a thread owns ONE 8-channel
@@ -557,17 +568,18 @@ extern "C" int hv_groupnorm_affine_f16(const void* x, int64_t ldx, int64_t M, in
     if (nblk < 1) return HV_ERR_ARG;
     const int rows_per_blk = (int)((M + nblk - 1) / nblk);
     gn_partial_kernel<<<dim3(nblk), dim3(256), (size_t)nrl * C * 2 * sizeof(float), stream>>>((const uint16_t*)x, ldx, M, C,
-                                                                                            partial_ws, rows_per_blk);
-    gn_finalize_kernel<<<dim3(groups), dim3(256), 0, stream>>>(partial_ws, nblk, C, groups, M, eps, (const uint16_t*)weight,
+                                                                                            groups, partial_ws, rows_per_blk);
+    gn_finalize_kernel<<<dim3(groups), dim3(256), 0, stream>>>(partial_ws, nblk, C, groups, (const uint16_t*)x, M, eps,
+                                                               (const uint16_t*)weight,
                                                                (const uint16_t*)bias, affine_out);
     return hv_check_launch();
 }
 
 extern "C" int hv_groupnorm_finalize_f16(const float* partial, int64_t partial_floats, int64_t nrow, int64_t M, int C, int groups,
                                          float eps, const void* weight, const void* bias, float* affine_out, hipStream_t stream) {
-    // partial: [nrow][C][2] (sum, sum of squares) rows as written by a conv epilogue (hv_conv3d_causal_f16 `gn_partial`), followed by
-    // HV_GN_FOLD_WS_FLOATS floats of workspace; M = rows of the activation the statistics cover.  The epilogue credits a pair of
-    // adjacent columns to the even one: a group must hold whole pairs.
+    // partial: [nrow][C][2] rows as written by a conv epilogue (hv_conv3d_causal_f16 `gn_partial`: per 64-row block and column pair,
+    // (sum, centred sum of squares) in the even column, (0, count) in the odd one), followed by HV_GN_FOLD_WS_FLOATS floats of
+    // workspace; M = rows of the activation the statistics cover.  A group must hold whole pairs.
     if (!partial || !weight || !bias || !affine_out || nrow <= 0 || M <= 0 || C < 8 || (C & 7) || C > 2048 || groups <= 0 ||
         groups > 64 || (groups & (groups - 1)) || (C % groups) || ((C / groups) & 1))
         return HV_ERR_ARG;

@@ -22,7 +22,7 @@ extern "C" {
 typedef struct ihipStream_t* hipStream_t;
 #endif
 
-/* ABI version of this header (bumped on any signature change). */
+/* ABI version of this header (bumped on any signature change, or a change of what a caller-visible buffer holds). */
 int hv_abi_version(void);
 
 /* K1: nn.LayerNorm(elementwise_affine=False, eps) followed by modulate()
@@ -188,9 +188,10 @@ int hv_gemm_f16(const void* A, int64_t lda, const void* W, int64_t ldw, const vo
  * (ResnetBlockCausal3D residual :413-415).  Cin % 64 == 0, Cout % 8 == 0 (callers zero-pad 16->64 and 3->8).
  * The source is addressed with 32-bit byte offsets: sT*sH*sW*ldx*2 must be < 4 GiB (HV_ERR_ARG otherwise).
  * gn_partial (nullable, device fp32 [hv_gn_partial_rows(T*H*W)][Cout][2], gn_partial_floats = its size): the epilogue also
- * leaves the GroupNorm statistics of the tensor it stores - (sum, sum of squares) per channel over each 64-row block, every entry
- * written once, in a fixed order - so the GroupNorm that follows (ResnetBlockCausal3D.norm1/norm2 :395-411, conv_norm_out) needs no
- * pass over the activation: hv_groupnorm_finalize_f16 folds them.  HV_ERR_ARG if the buffer is too small. */
+ * leaves the GroupNorm statistics of the tensor it stores - per 64-row block b and pair of adjacent columns (c, c+1), c even, over the
+ * k valid values: gn_partial[b][c] = (S = sum, C2 = sum of (x - S/k)^2), gn_partial[b][c+1] = (0, k); every entry written once, in a
+ * fixed order - so the GroupNorm that follows (ResnetBlockCausal3D.norm1/norm2 :395-411, conv_norm_out) needs no pass over the
+ * activation: hv_groupnorm_finalize_f16 folds them.  HV_ERR_ARG if the buffer is too small. */
 int hv_conv3d_causal_f16(const void* x, int64_t ldx, const void* w_taps, const void* bias, void* out, int64_t ldo,
                          int T, int H, int W, int Cin, int Cout, int up_t, int up_hw, const void* res,
                          int64_t ld_res, float* gn_partial, int64_t gn_partial_floats, hipStream_t stream);
@@ -246,7 +247,8 @@ int hv_temporal_resample_f16(const void* x, int64_t ldx, void* out, int64_t ldo,
                              int k, int s, hipStream_t stream);
 
 /* K16 pass 1+2: GroupNorm statistics (nn.GroupNorm(32, C, eps 1e-6, affine), unet_causal_3d_blocks.py:302,323) folded
- * into a per-channel affine: affine_out[2c] = rstd_g*w[c], affine_out[2c+1] = b[c] - mean_g*rstd_g*w[c].
+ * into a per-channel affine: affine_out[2c] = rstd_g*w[c], affine_out[2c+1] = b[c] - mean_g*rstd_g*w[c].  The moments are summed
+ * about a pivot per group (its first channel in row 0), so an offset group mean does not cancel the variance.
  * partial_ws: caller workspace of partial_ws_floats floats (>= 2*C; 2*C*1024 for full parallelism). */
 int hv_groupnorm_affine_f16(const void* x, int64_t ldx, int64_t M, int C, int groups, float eps, const void* weight,
                             const void* bias, float* partial_ws, int64_t partial_ws_floats, float* affine_out,
@@ -256,8 +258,9 @@ int hv_groupnorm_affine_f16(const void* x, int64_t ldx, int64_t M, int C, int gr
  * partial [nrow][C][2] fp32 followed by HV_GN_FOLD_WS_FLOATS floats of fold workspace IN THE SAME BUFFER (the fp64 fold scratch
  * starts at the next even float index behind the partials), M = rows of the activation they cover.  partial_floats = size of that
  * buffer in floats: HV_ERR_ARG unless it is >= align2(nrow*C*2) + HV_GN_FOLD_WS_FLOATS (a buffer sized for the conv alone is too
- * small and is refused, never overrun).  Folded in fp64 in a fixed order.  The epilogue credits each pair of adjacent channels
- * to the even one, so C / groups must be even (HV_ERR_ARG otherwise). */
+ * small and is refused, never overrun).  Folded in fp64 in a fixed order: sum x^2 of an entry = C2 + S^2 / k, so the variance
+ * var = Q/n - mean^2 cancels only in fp64.  The epilogue credits each pair of adjacent channels to the even one, so C / groups must
+ * be even (HV_ERR_ARG otherwise). */
 #define HV_GN_FOLD_WS_FLOATS 16384
 int hv_groupnorm_finalize_f16(const float* partial, int64_t partial_floats, int64_t nrow, int64_t M, int C, int groups, float eps,
                               const void* weight, const void* bias, float* affine_out, hipStream_t stream);
