@@ -9,9 +9,13 @@ N>1: the same single video sharded over the token axis (Ulysses sequence paralle
 i.e. strong scaling; `value` is whole-job denoise-steps/s.
 
 Prints ONE JSON line (rank 0) with the driver's contract keys plus `roofline` (dominant kernel = flash
-attention, MFMA-bound, measured with HIP events on the launch stream inside the timed region) and
-`cpu_baseline` (the oracle, i.e. the CPU restatement of the reference path, timed on this box's host cores on
-a bounded sample and FLOP-scaled - a reported baseline, not a target).
+attention, MFMA-bound, measured with HIP events on the launch stream inside the timed region).
+
+A plain run does only what that line needs: set up, warm up, time the steps, write --dump-outputs, print.
+`--full` adds, after the timed leg and never part of `value`: the secondary workloads (`secondary`), the VAE
+tiled decode of the same video (`vae_tiled_decode_s`) and `cpu_baseline` (the oracle, i.e. the CPU restatement
+of the reference path, timed on this box's host cores on a bounded sample and FLOP-scaled - a reported
+baseline, not a target - with the GPU-vs-oracle `block_check`).
 """
 import argparse
 import json
@@ -164,13 +168,23 @@ def launch_ranks(n: int) -> int:
     return rc
 
 
-def main():
+def extra_legs(a, world):
+    """The legs a run adds after its timed one, none of them part of `value`: all of them only with --full."""
+    return {"secondary": a.full and world == 1 and a.workload == "720p129f" and not (a.no_secondary or a.use_fp8 or a.force_sp),
+            "vae": a.full and a.workload != "tiny" and not a.no_vae,
+            "cpu_baseline": a.full and world == 1 and not a.no_cpu_baseline}
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="720p129f", choices=list(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed leg, also run what the headline figure does not need: the "
+                    "secondary workloads (single-GPU 720p129f: 544x960x65f, 720p x 257f, FP8-MFMA), the VAE tiled decode of the same "
+                    "video and the CPU baseline with its GPU-vs-oracle block check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--force-sp", action="store_true", help="N=1 only: run the sequence-parallel code path on a 1-rank RCCL group "
                     "(pack/unpack + self all-to-all + chunked QKV GEMMs) to price its overhead")
     ap.add_argument("--ring-degree", type=int, default=1, help="N > 1: hybrid Ulysses x Ring with this ring degree (ulysses = N / ring); "
@@ -180,13 +194,18 @@ def main():
     ap.add_argument("--fp8-mfma", action="store_true", help="with --use-fp8: run the block linears on the CDNA4 FP8 matrix cores "
                     "(v_mfma_scale_f32_16x16x128_f8f6f4; activations quantised per token to e4m3) instead of dequantising the weights "
                     "to bf16 per call - an opt-in approximation beyond the reference's weight-only FP8 (tests/test_gpu_fp8_mfma.py)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads (544x960x65f, 720p x 257f, FP8-MFMA) that a "
-                    "default single-GPU 720p129f run appends after its timed leg")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workloads (544x960x65f, 720p x 257f, "
+                    "FP8-MFMA) that a single-GPU 720p129f run appends after its timed leg")
     ap.add_argument("--secondary-budget", type=float, default=150.0, help="wall-clock seconds the secondary workloads may take in total")
-    ap.add_argument("--no-vae", action="store_true", help="skip the (untimed-by-`value`) VAE tiled decode of the same video")
+    ap.add_argument("--no-vae", action="store_true", help="with --full: skip the (untimed-by-`value`) VAE tiled decode of the same video")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
                     "returned (latents = scheduler output, noise_pred = transformer output) as DIR/<name>.npy in float32 "
                     "(rank 0; at most 64 MB in all, a fixed seeded sample of larger outputs)")
+    return ap
+
+
+def main():
+    ap = build_parser()
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
@@ -209,6 +228,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}: the launcher's world size and --gpus must agree")
+    legs = extra_legs(a, world)
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     if world > 1 or a.force_sp:
@@ -291,9 +311,9 @@ def main():
     att_ms, att_flop = [m for m, _ in att], [f for _, f in att]
 
     # Secondary workloads (BASELINE.json configs 2, 5 and 4) on the same model, AFTER the timed headline leg and never part of
-    # `value`: a few steps each inside a stated wall-clock budget (what does not fit is skipped and says so).
+    # `value`: a few steps each inside a stated wall-clock budget (what does not fit is skipped and says so).  --full only.
     secondary = []
-    if world == 1 and a.workload == "720p129f" and not a.no_secondary and not a.use_fp8 and not a.force_sp:
+    if legs["secondary"]:
         budget_s, t_sec0 = a.secondary_budget, time.perf_counter()
         ms129 = elapsed / a.steps * 1e3
 
@@ -345,9 +365,9 @@ def main():
             secondary.append(e)
         model._ws = None
         torch.cuda.empty_cache()
-    # end-to-end leg (reported beside `value`, never part of it): VAE tiled decode of this video's latents on rank 0's GPU
+    # end-to-end leg (reported beside `value`, never part of it; --full only): VAE tiled decode of this video's latents on rank 0's GPU
     vae_s = None
-    if not tiny and not a.no_vae:
+    if legs["vae"]:
         # N > 1: the 84 tiles are shared out over the ranks (AutoencoderKLCausal3D.enable_tile_parallel), all ranks take part
         from hunyuanvideo_efficiency_amd.vae import AutoencoderKLCausal3D
         vae = AutoencoderKLCausal3D(device=dev)
@@ -417,7 +437,7 @@ def main():
         }
         if secondary:
             out["secondary"] = secondary
-        if world == 1 and not a.no_cpu_baseline:
+        if legs["cpu_baseline"]:
             out["cpu_baseline"] = cpu_baseline(f_step)
         real_stdout.write(json.dumps(out) + "\n")
         real_stdout.flush()
