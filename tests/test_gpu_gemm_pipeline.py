@@ -42,7 +42,9 @@ def _both(ops, *args, **kw):
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 192), (300, 520, 256), (1000, 768, 320), (513, 1792, 384), (4096, 3072, 3072),
-                                    (2000, 9216, 448), (777, 264, 1024), (33, 3072, 15360)])
+                                    (2000, 9216, 448), (777, 264, 1024), (33, 3072, 15360),
+                                    # short last band (tiles_m 6 / 9 with GROUP_M = 4), 8-column N tails
+                                    (1281, 520, 320), (2049, 1032, 448)])
 def test_pipelined_equals_2stage_bitwise_and_oracle(ops, M, N, K):
     a, w, b = _u((M, K), f"p.a{M}"), _u((N, K), f"p.w{N}", 1 / math.sqrt(K)), _u((N,), "p.b", 0.1)
     got, ref = _both(ops, a, w, b)
