@@ -35,10 +35,20 @@ class HunyuanVideoPipeline:
 
     def prepare_latents(self, batch_size, num_channels_latents, height, width, video_length, dtype, device, generator,
                         latents=None):
-        """pipeline_hunyuan_video.py:558-594: randn [B, C, T, H/8, W/8] * init_noise_sigma (absent for flow matching)."""
+        """pipeline_hunyuan_video.py:558-594: randn [B, C, T, H/8, W/8] * init_noise_sigma (absent for flow matching).
+        `generator`: one torch.Generator (one randn call over the whole batch) or a list of B, one per video."""
         shape = (batch_size, num_channels_latents, video_length, int(height) // self.vae_scale_factor,
                  int(width) // self.vae_scale_factor)
-        if latents is None:
+        if isinstance(generator, (list, tuple)) and len(generator) != batch_size:
+            raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
+                             f" size of {batch_size}. Make sure the batch size matches the length of the generators.")
+        if latents is None and isinstance(generator, (list, tuple)):
+            # diffusers' randn_tensor with a generator list: video b is drawn by generator[b] alone (on that generator's device
+            # when its type differs), so each video's noise depends on its own seed only, whatever the batch
+            dev = torch.device(device)
+            latents = torch.cat([torch.randn((1,) + shape[1:], generator=g, dtype=dtype,
+                                             device=g.device if g.device.type != dev.type else dev) for g in generator]).to(dev)
+        elif latents is None:
             latents = torch.randn(shape, generator=generator, device=device, dtype=dtype)
         else:
             latents = latents.to(device)
@@ -66,6 +76,8 @@ class HunyuanVideoPipeline:
             batch = 1 if isinstance(prompt, str) or prompt is None else len(prompt)
             if negative_prompt is None:
                 uncond = [""] * batch
+            elif isinstance(negative_prompt, str) and not isinstance(prompt, str):
+                uncond = [negative_prompt] * batch         # one negative prompt for every prompt of a list
             elif prompt is not None and type(prompt) is not type(negative_prompt):
                 raise TypeError(f"`negative_prompt` should be the same type to `prompt`, but got {type(negative_prompt)} != {type(prompt)}.")
             elif isinstance(negative_prompt, str):
@@ -93,28 +105,55 @@ class HunyuanVideoPipeline:
                  negative_prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_mask: Optional[torch.Tensor] = None,
                  negative_prompt_embeds_2: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0):
         """Either the reference's keyword surface (`prompt=...`, text encoders attached: pipeline_hunyuan_video.py:664-1100) or
-        pre-computed `prompt_embeds` / `prompt_mask` / `prompt_embeds_2` (synthetic benchmarks, tests)."""
+        pre-computed `prompt_embeds` / `prompt_mask` / `prompt_embeds_2` (synthetic benchmarks, tests).
+        Batches: B prompts (a list, or B rows of pre-computed embeddings) x `num_videos_per_prompt` give B*N videos, prompt-major;
+        `generator` is one torch.Generator or a list of B*N (one per video: inference.resolve_seeds / seed_generators).  The
+        transformer and the VAE take the videos one after another through the same kernels and workspaces, so video i equals the
+        single-video run with generator[i] (with guidance_rescale > 0 only up to the rounding of its batched std), and N videos cost N
+        times one."""
         # classifier-free guidance (:966-1019; the non-distilled model): batch [uncond | cond] through the transformer, then
         # uncond + scale (cond - uncond); the CFG-distilled model runs with guidance_scale = 1 and never doubles the batch
         do_cfg = guidance_scale > 1.0
+        n_per = int(num_videos_per_prompt)
+        if n_per < 1:
+            raise ValueError(f"num_videos_per_prompt must be >= 1, got {num_videos_per_prompt}")
+
+        def per_video(x):
+            """Caller-given per-prompt rows -> one row per video (prompt-major, as encode_prompt repeats its outputs)."""
+            return x if x is None or n_per == 1 else x.repeat_interleave(n_per, dim=0)
         if prompt is not None:
             if self.text_encoder is None:
                 raise ValueError("prompt given but the pipeline has no text_encoder")
-            if not isinstance(prompt, str) or num_videos_per_prompt != 1:
-                raise NotImplementedError("batch 1: one prompt, one video per call")
+            if not isinstance(prompt, (str, list, tuple)) or (not isinstance(prompt, str) and not prompt):
+                raise TypeError(f"`prompt` must be a str or a non-empty list of str, got {prompt!r}")
+            prompt = prompt if isinstance(prompt, str) else list(prompt)
             device = device if device is not None else self.transformer.img_in.proj.weight.device
             prompt_embeds, negative_prompt_embeds, prompt_mask, negative_prompt_mask = self.encode_prompt(
-                prompt, device, num_videos_per_prompt, do_cfg, negative_prompt, data_type=data_type)
+                prompt, device, n_per, do_cfg, negative_prompt, data_type=data_type)
             if self.text_encoder_2 is not None:     # CLIP pooled vector (:869-886)
                 prompt_embeds_2, negative_prompt_embeds_2, _, _ = self.encode_prompt(
-                    prompt, device, num_videos_per_prompt, do_cfg, negative_prompt, text_encoder=self.text_encoder_2, data_type=data_type)
-        elif prompt_mask is None and attention_mask is not None:
-            prompt_mask = attention_mask
+                    prompt, device, n_per, do_cfg, negative_prompt, text_encoder=self.text_encoder_2, data_type=data_type)
+            else:                                   # caller-given pooled vectors: one row per prompt
+                prompt_embeds_2, negative_prompt_embeds_2 = per_video(prompt_embeds_2), per_video(negative_prompt_embeds_2)
+        else:
+            # pre-computed embeddings: one row per prompt (rows may have different valid text lengths), each repeated per video
+            if prompt_embeds is None:
+                raise ValueError("pass either `prompt` (with text encoders) or `prompt_embeds`")
+            if prompt_mask is None and attention_mask is not None:
+                prompt_mask = attention_mask
+            prompt_embeds, prompt_mask, prompt_embeds_2 = per_video(prompt_embeds), per_video(prompt_mask), per_video(prompt_embeds_2)
+            negative_prompt_embeds, negative_prompt_mask = per_video(negative_prompt_embeds), per_video(negative_prompt_mask)
+            negative_prompt_embeds_2 = per_video(negative_prompt_embeds_2)
         device = prompt_embeds.device
-        n_cond = prompt_embeds.shape[0]
-        if do_cfg:       # one batch [uncond | cond] (:896-904)
-            if negative_prompt_embeds is None:
-                raise ValueError("guidance_scale > 1 needs negative_prompt_embeds (or a prompt + text encoders)")
+        n_cond = prompt_embeds.shape[0]     # B * num_videos_per_prompt videos
+        if do_cfg:       # one batch [uncond x n_cond | cond x n_cond] (:896-904)
+            for name, cond, uncond in (("prompt_embeds", prompt_embeds, negative_prompt_embeds),
+                                       ("prompt_mask", prompt_mask, negative_prompt_mask),
+                                       ("prompt_embeds_2", prompt_embeds_2, negative_prompt_embeds_2)):
+                if cond is not None and uncond is None:
+                    raise ValueError(f"guidance_scale > 1 needs negative_{name} to go with {name} (or a prompt + text encoders)")
+                if cond is not None and uncond.shape[0] != cond.shape[0]:
+                    raise ValueError(f"negative_{name} has {uncond.shape[0]} rows, {name} has {cond.shape[0]}")
             prompt_embeds = torch.cat([negative_prompt_embeds.to(prompt_embeds), prompt_embeds])
             if prompt_mask is not None:
                 prompt_mask = torch.cat([negative_prompt_mask.to(prompt_mask), prompt_mask])

@@ -1,11 +1,13 @@
 """Sampler-side pieces of the hot path with the reference's names (hyvideo/inference.py): the sequence-parallel
-monkey-patch `parallelize_transformer` (:40-104), the RoPE table builder `get_rotary_pos_embed` (:450-495) and the
-distributed initialisation (:157-176).  One process per GPU (torchrun), RCCL through torch.distributed "nccl"."""
+monkey-patch `parallelize_transformer` (:40-104), the RoPE table builder `get_rotary_pos_embed` (:450-495), the
+distributed initialisation (:157-176) and the per-video seeds of `predict` (:533-562).  One process per GPU (torchrun), RCCL
+through torch.distributed "nccl"."""
 from __future__ import annotations
 
 import functools
 import os
-from typing import Optional
+import random
+from typing import List, Optional
 
 import torch
 import torch.distributed as dist
@@ -104,6 +106,31 @@ def parallelize_transformer(pipe):
     vae = getattr(pipe, "vae", None)
     if vae is not None and hasattr(vae, "enable_tile_parallel"):
         vae.enable_tile_parallel()      # beyond the reference (which decodes every tile on every rank): SURVEY.md 8e
+
+
+def resolve_seeds(seed, batch_size: int = 1, num_videos_per_prompt: int = 1) -> List[int]:
+    """inference.py:533-562: one seed per video, prompt-major (video j of prompt i is entry i * num_videos_per_prompt + j).
+    None -> random seeds; int s -> s + j for video j of every prompt; a list of batch_size -> seed[i] + j; a list of
+    batch_size * num_videos_per_prompt -> as given; anything else -> ValueError."""
+    if isinstance(seed, torch.Tensor):
+        seed = seed.tolist()
+    if seed is None:
+        return [random.randint(0, 1_000_000) for _ in range(batch_size * num_videos_per_prompt)]
+    if isinstance(seed, int):
+        return [seed + i for _ in range(batch_size) for i in range(num_videos_per_prompt)]
+    if isinstance(seed, (list, tuple)):
+        if len(seed) == batch_size:
+            return [int(seed[i]) + j for i in range(batch_size) for j in range(num_videos_per_prompt)]
+        if len(seed) == batch_size * num_videos_per_prompt:
+            return [int(s) for s in seed]
+        raise ValueError(f"Length of seed must be equal to number of prompt(batch_size) or "
+                         f"batch_size * num_videos_per_prompt ({batch_size} * {num_videos_per_prompt}), got {seed}.")
+    raise ValueError(f"Seed must be an integer, a list of integers, or None, got {seed}.")
+
+
+def seed_generators(seeds: List[int], device) -> List[torch.Generator]:
+    """inference.py:563: one generator per video on `device` (the pipeline's `generator` list)."""
+    return [torch.Generator(device).manual_seed(int(s)) for s in seeds]
 
 
 def get_rotary_pos_embed(transformer, video_length: int, height: int, width: int, vae: str = "884-16c-hy",

@@ -780,8 +780,7 @@ class AutoencoderKLCausal3D(nn.Module):
 
     def _decode(self, z: torch.Tensor):
         assert len(z.shape) == 5, "The input tensor should have 5 dimensions."
-        if z.shape[0] != 1:
-            raise NotImplementedError("batch 1 (use_slicing splits larger batches)")
+        assert z.shape[0] == 1, "one video per _decode call: decode() steps through a batch"
         z4 = z[0].to(torch.float32)
         self._tile_queue = None
         if self._t_ops is not None and (self.use_temporal_tiling or self.use_spatial_tiling):
@@ -810,11 +809,21 @@ class AutoencoderKLCausal3D(nn.Module):
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None):
-        """autoencoder_kl_causal_3d.py:316-342: returns (sample,) or an object with .sample; sample fp16 [B,3,T,H,W]."""
-        if self.use_slicing and z.shape[0] > 1:
-            decoded = torch.cat([self._decode(zs) for zs in z.split(1)])
-        else:
+        """autoencoder_kl_causal_3d.py:316-342: returns (sample,) or an object with .sample; sample fp16 [B,3,T,H,W].
+        B > 1 decodes the videos one after another, each through the whole single-video path (concurrent tile streams, the
+        tile-parallel sharded decode - every rank steps through the videos in the same order - or untiled), so video b equals
+        decode(z[b:b+1]) bit for bit.  That is what use_slicing asks for; it stays accepted and changes nothing."""
+        assert len(z.shape) == 5, "The input tensor should have 5 dimensions."
+        if z.shape[0] == 1:
             decoded = self._decode(z)
+        else:
+            decoded = None
+            for b in range(z.shape[0]):
+                d = self._decode(z[b:b + 1])
+                if decoded is None:         # written in place: no second copy of the batch at the end
+                    decoded = torch.empty((z.shape[0],) + tuple(d.shape[1:]), dtype=d.dtype, device=d.device)
+                decoded[b:b + 1].copy_(d)
+                del d
         if not return_dict:
             return (decoded,)
         return SimpleNamespace(sample=decoded)

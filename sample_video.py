@@ -11,6 +11,17 @@ import time
 import torch
 
 
+def _seed_arg(v: str):
+    parts = [x for x in v.split(",") if x.strip()]
+    if not parts:
+        raise argparse.ArgumentTypeError(f"--seed: no seed in {v!r}")
+    try:
+        vals = [int(x) for x in parts]
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"--seed takes integers, got {v!r}") from e
+    return vals[0] if len(vals) == 1 and "," not in v else vals
+
+
 def parse_args():
     p = argparse.ArgumentParser(description="HunyuanVideo denoise + decode on MI355X kernels")
     p.add_argument("--model", default="HYVideo-T/2-cfgdistill")
@@ -26,7 +37,11 @@ def parse_args():
     p.add_argument("--infer-steps", type=int, default=50)
     p.add_argument("--video-size", type=int, nargs="+", default=[720, 1280])
     p.add_argument("--video-length", type=int, default=129)
-    p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--seed", type=_seed_arg, default=42, help="int, or a comma-separated list: one per prompt or one per video "
+                   "(inference.py:533-562 of the reference: video j of prompt i gets seed + j, seed[i] + j, or its own)")
+    p.add_argument("--num-videos", type=int, default=1, help="videos per prompt (config.py:295-300)")
+    p.add_argument("--batch-size", type=int, default=1, help="prompts per call; one --prompt means 1, without --prompt this many "
+                   "distinct synthetic prompts")
     p.add_argument("--cfg-scale", type=float, default=1.0)
     p.add_argument("--embedded-cfg-scale", type=float, default=6.0)
     p.add_argument("--use-fp8", action="store_true")
@@ -58,7 +73,8 @@ def parse_args():
 def main():
     a = parse_args()
     from hunyuanvideo_efficiency_amd import synthetic as syn
-    from hunyuanvideo_efficiency_amd.inference import init_distributed, parallelize_transformer, get_rotary_pos_embed
+    from hunyuanvideo_efficiency_amd.inference import (init_distributed, parallelize_transformer, get_rotary_pos_embed, resolve_seeds,
+                                                       seed_generators)
     from hunyuanvideo_efficiency_amd.builders import build_model
     from hunyuanvideo_efficiency_amd.vae import AutoencoderKLCausal3D
     from hunyuanvideo_efficiency_amd.diffusion.schedulers import FlowMatchDiscreteScheduler
@@ -116,9 +132,25 @@ def main():
     if a.ulysses_degree > 1 or a.ring_degree > 1:      # inference.py:157,408
         parallelize_transformer(pipe)
     lt = (a.video_length - 1) // 4 + 1
-    _, ts, tm, ts2 = syn.synth_dit_inputs(cfg, (lt, h // 8, w // 8), a.text_len, 11, seed=a.seed, device=dev)
+    if a.num_videos < 1 or a.batch_size < 1:
+        raise ValueError("--num-videos and --batch-size must be >= 1")
+    # reference predict (inference.py:505-669): one --prompt is one prompt, whatever --batch-size says
+    n_prompts = 1 if a.prompt is not None else a.batch_size
+    if a.prompt is not None and a.batch_size != 1 and rank == 0:
+        print(f"--prompt is a single prompt: --batch-size {a.batch_size} ignored (batch size 1)")
+    seeds = resolve_seeds(a.seed, n_prompts, a.num_videos)
+    # synthetic prompt embeddings: a function of the first seed (the N videos of a prompt share them); prompt i > 0 uses the
+    # even offset 2i (odd offsets would meet the negative embeddings' seed + 1)
+    base = seeds[0]
+    syn_txt = [syn.synth_dit_inputs(cfg, (lt, h // 8, w // 8), a.text_len, 11, seed=base + 2 * i, device=dev)[1:] for i in range(n_prompts)]
+    ts, tm, ts2 = (torch.cat([p[k] for p in syn_txt]) for k in range(3))
     freqs = get_rotary_pos_embed(model, a.video_length, h, w, a.vae, a.rope_theta, device=dev)
-    gen = torch.Generator(device=dev).manual_seed(a.seed)
+    gen = torch.Generator(device=dev).manual_seed(seeds[0]) if len(seeds) == 1 else seed_generators(seeds, dev)
+    neg = {}
+    if a.cfg_scale > 1.0:      # synthetic "negative prompt" pooled vector (and embeddings without a prompt): one row per prompt
+        _, nts, ntm, nts2 = syn.synth_dit_inputs(cfg, (lt, h // 8, w // 8), a.text_len, 4, seed=base + 1, device=dev)
+        neg = dict(negative_prompt_embeds=nts.to(torch.float16).repeat(n_prompts, 1, 1), negative_prompt_mask=ntm.repeat(n_prompts, 1),
+                   negative_prompt_embeds_2=nts2.to(torch.float16).repeat(n_prompts, 1))
     torch.cuda.synchronize()
     t0 = time.time()
     def progress(i, t, latents):       # the reference shows a tqdm bar (pipeline_hunyuan_video.py:955-961); one line every 5 steps here
@@ -126,24 +158,30 @@ def main():
             print(f"  step {i + 1}/{a.infer_steps}  t={float(t):.1f}  elapsed {time.time() - t0:.1f} s", flush=True)
     common = dict(callback=progress, callback_steps=5, height=h, width=w, video_length=a.video_length, num_inference_steps=a.infer_steps, guidance_scale=a.cfg_scale,
                   embedded_guidance_scale=a.embedded_cfg_scale if cfg.guidance_embed else None, generator=gen, freqs_cis=freqs, vae_ver=a.vae,
-                  enable_tiling=a.vae_tiling, n_tokens=freqs[0].shape[0])
+                  enable_tiling=a.vae_tiling, n_tokens=freqs[0].shape[0], num_videos_per_prompt=a.num_videos)
     if a.prompt is not None:
+        # without a CLIP encoder the pooled vectors are synthetic, the negative one included (the CFG batch needs both)
+        no_clip = text_encoder_2 is None
         out = pipe(prompt=a.prompt, negative_prompt=getattr(a, "neg_prompt", None),
-                   prompt_embeds_2=None if text_encoder_2 is not None else ts2.to(torch.float16), data_type="video", **common)
+                   prompt_embeds_2=ts2.to(torch.float16) if no_clip else None,
+                   negative_prompt_embeds_2=neg.get("negative_prompt_embeds_2") if no_clip else None, data_type="video", **common)
+        prompts = [a.prompt]
     else:
-        neg = {}
-        if a.cfg_scale > 1.0:      # synthetic "negative prompt" embeddings (no text encoder in this run)
-            _, nts, ntm, nts2 = syn.synth_dit_inputs(cfg, (lt, h // 8, w // 8), a.text_len, 4, seed=a.seed + 1, device=dev)
-            neg = dict(negative_prompt_embeds=nts.to(torch.float16), negative_prompt_mask=ntm, negative_prompt_embeds_2=nts2.to(torch.float16))
         out = pipe(ts.to(torch.float16), tm, ts2.to(torch.float16), **neg, **common)
+        prompts = ["synthetic" if n_prompts == 1 else f"synthetic{i}" for i in range(n_prompts)]
     dt = time.time() - t0
     if rank == 0:
         v = out.videos
         print(f"Success, time: {dt:.2f} s; video tensor {tuple(v.shape)} {v.dtype} range [{float(v.min()):.3f}, {float(v.max()):.3f}]")
         os.makedirs(a.save_path, exist_ok=True)
-        torch.save(v[:, :, :1].clone(), os.path.join(a.save_path, "first_frame.pt"))
         from hunyuanvideo_efficiency_amd.utils.file_utils import save_videos_grid
-        print("Sample save to:", save_videos_grid(v, os.path.join(a.save_path, f"seed{a.seed}.mp4"), fps=24))
+        if v.shape[0] == 1:      # one video: the names of a single-video run
+            torch.save(v[:, :, :1].clone(), os.path.join(a.save_path, "first_frame.pt"))
+            print("Sample save to:", save_videos_grid(v, os.path.join(a.save_path, f"seed{seeds[0]}.mp4"), fps=24))
+        else:                    # the reference's loop (sample_video.py:48-55): video i of prompt i // N
+            for i in range(v.shape[0]):
+                name = f"seed{seeds[i]}_{prompts[i // a.num_videos][:100].replace('/', '')}.mp4"
+                print("Sample save to:", save_videos_grid(v[i:i + 1], os.path.join(a.save_path, name), fps=24))
 
 
 if __name__ == "__main__":
