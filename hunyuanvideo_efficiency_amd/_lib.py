@@ -104,7 +104,7 @@ def load():
             m = re.search(r"#define HV_W4_LOOP_SIGNATURE 0x([0-9a-f]{8})u", f.read(600))
         if m is None or (lib.hv_attn_w4_loop_signature() & 0xFFFFFFFF) != int(m.group(1), 16):
             raise HVKernelError(f"{LIB_PATH} was not compiled from {inc}: rebuild the extension (make -C hunyuanvideo_efficiency_amd/csrc); "
-                                "HV_ALLOW_EXPERIMENT_LIB=1 admits an experiment build (tools/attn_variants)")
+                                "HV_ALLOW_EXPERIMENT_LIB=1 admits a library built from another checkout (same-box A/Bs: tools/ab_attn.sh, tools/ab_run.sh)")
     _lib = lib
     return lib
 

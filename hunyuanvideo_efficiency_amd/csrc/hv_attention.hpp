@@ -1,4 +1,4 @@
-// Declarations shared by the attention translation units (hv_attention.hip: the 8-wave kernel + the C ABI entry points;
+// Declarations shared by the attention translation units (hv_attention.hip: the C ABI entry points, the K row-max and merge kernels;
 // hv_attention_w4.hip: the 4-wave x 64-row kernel with asm-owned accumulator registers).
 #pragma once
 #include "hv_common.hpp"

@@ -1,6 +1,6 @@
 // Flash attention forward, bf16, head_dim 128 - the 4-wave x 64-row structure (one wave per SIMD, 512 registers per lane, the
 // accumulator half of the register file owned by inline asm through LITERAL register names).  Same arithmetic contract and the
-// same AttnArgs as the 8-wave kernels of rounds 1-2 (tools/attn_variants/): swapped QK^T, the maximum - a static row bound where it is
+// same AttnArgs as the retired 8-wave kernels of rounds 1-2 (git history): swapped QK^T, the maximum - a static row bound where it is
 // provably safe, else the deferred running max - in the C operand of the S chains, P rounded to bf16 for P.V, unrounded row sums;
 // what changed is who holds what:
 //
@@ -51,14 +51,9 @@ constexpr int W4_KOFF = 0, W4_VOFF = W4_NBUF * KV_TILE_BYTES;      // LDS bytes:
 constexpr int W4_LDS = 2 * W4_NBUF * KV_TILE_BYTES;               // 128 KiB
 constexpr int A_O = 0, A_Q = 128, A_KF = 192, A_VF = 224;         // accumulator-file map (see header)
 constexpr int RING = 8;       // K and V fragment rings: 8 slots of 4 registers each
-#ifndef HV_W4_PF
-#define HV_W4_PF 4
-#endif
-#ifndef HV_W4_WGRP
-#define HV_W4_WGRP 2
-#endif
-constexpr int PF = HV_W4_PF;  // a fragment is read from LDS PF fragments (2 PF MFMA gaps) ahead of its first MFMA
-constexpr int WGRP = HV_W4_WGRP;   // one counted lgkmcnt wait per WGRP fragments (the generator's tables use the same two numbers)
+constexpr int PF = 4;      // a fragment is read from LDS PF fragments (2 PF MFMA gaps) ahead of its first MFMA
+constexpr int WGRP = 2;    // one counted lgkmcnt wait per WGRP fragments
+// tools/gen_attn_w4_asm.py schedules the steady-state iteration with the same PF and WGRP: change them there too
 // LDS instructions issued between fragment f's read and its first use = the reads of fragments f+1 .. f+PF-1 (K: 1 instruction,
 // V: 2; fragments 16..31 of a tile are V, 32.. are the next tile's K)
 __host__ __device__ constexpr int frag_insts(int f) { return (f >= 16 && f < 32) ? 2 : 1; }
@@ -132,19 +127,7 @@ __device__ __forceinline__ float acc_read() {
 }
 
 // the steady-state iteration as ONE asm statement with literal registers (tools/gen_attn_w4_asm.py)
-#if defined(HV_W4_LOOP_INC)  // experiment builds (tools/attn_variants/build_w4.sh): an iteration generated outside the tree, never the product's
-#include HV_W4_LOOP_INC
-#elif defined(HV_W4_STAMPS)  // diagnostic build: the generated iteration with s_memtime stamps around the barrier's waits
-#include "hv_attention_w4_loop_stamps.inc"
-#else
 #include "hv_attention_w4_loop.inc"
-#endif
-#ifdef HV_W4_STAMPS
-__device__ unsigned g_w4_dbg[8];
-#define HV_W4_DBG_ARGS , dbg_vm, dbg_bar, dbg_pre, dbg_p1, dbg_p2, dbg_p3
-#else
-#define HV_W4_DBG_ARGS
-#endif
 
 // ---------------------------------------------------------------------------------------------------- schedule tables
 // exponentials of P(t) per gap: 5 per 4 gaps through the S phase (40), one per gap in gaps 32-55 (24).  The k-step kk of P.V starts
@@ -522,10 +505,6 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_kernel_w4(AttnArgs a) {
         d[3] = 0x00020000u;
         return d;
     };
-#ifdef HV_W4_STAMPS
-    uint32_t dbg_vm = 0, dbg_bar = 0, dbg_pre = 0, dbg_p1 = 0, dbg_p2 = 0, dbg_p3 = 0;
-    const uint64_t dbg_t0 = __builtin_amdgcn_s_memtime();
-#endif
     const uint32_t ldsw = lds0 + wave_lds;
     auto iter_full = [&](auto j_c, int tt) __attribute__((always_inline)) {
         constexpr int J = decltype(j_c)::value;          // tt = J (mod 4): S'(tt) lives in sA for even J
@@ -537,18 +516,18 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_kernel_w4(AttnArgs a) {
             else raise_max(sB, mc);
         }
         const u32x4 krs = desc(kbase + (tt + 3) * k_tile_bytes, k_row_bytes), vrs = desc(vbase + (tt + 2) * v_tile_bytes, v_row_bytes);
-        if constexpr (J == 0) w4_iter_0(sA, sB, negm, l_run, l2_run, mn, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw HV_W4_DBG_ARGS);
-        else if constexpr (J == 1) w4_iter_1(sA, sB, negm, l_run, l2_run, mn, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw HV_W4_DBG_ARGS);
-        else if constexpr (J == 2) w4_iter_2(sA, sB, negm, l_run, l2_run, mn, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw HV_W4_DBG_ARGS);
-        else w4_iter_3(sA, sB, negm, l_run, l2_run, mn, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw HV_W4_DBG_ARGS);
+        if constexpr (J == 0) w4_iter_0(sA, sB, negm, l_run, l2_run, mn, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw);
+        else if constexpr (J == 1) w4_iter_1(sA, sB, negm, l_run, l2_run, mn, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw);
+        else if constexpr (J == 2) w4_iter_2(sA, sB, negm, l_run, l2_run, mn, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw);
+        else w4_iter_3(sA, sB, negm, l_run, l2_run, mn, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw);
     };
     auto iter_static = [&](auto j_c, int tt) __attribute__((always_inline)) {
         constexpr int J = decltype(j_c)::value;
         const u32x4 krs = desc(kbase + (tt + 3) * k_tile_bytes, k_row_bytes), vrs = desc(vbase + (tt + 2) * v_tile_bytes, v_row_bytes);
-        if constexpr (J == 0) w4_iter_0_static(sA, sB, negm, l_run, l2_run, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw HV_W4_DBG_ARGS);
-        else if constexpr (J == 1) w4_iter_1_static(sA, sB, negm, l_run, l2_run, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw HV_W4_DBG_ARGS);
-        else if constexpr (J == 2) w4_iter_2_static(sA, sB, negm, l_run, l2_run, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw HV_W4_DBG_ARGS);
-        else w4_iter_3_static(sA, sB, negm, l_run, l2_run, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw HV_W4_DBG_ARGS);
+        if constexpr (J == 0) w4_iter_0_static(sA, sB, negm, l_run, l2_run, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw);
+        else if constexpr (J == 1) w4_iter_1_static(sA, sB, negm, l_run, l2_run, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw);
+        else if constexpr (J == 2) w4_iter_2_static(sA, sB, negm, l_run, l2_run, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw);
+        else w4_iter_3_static(sA, sB, negm, l_run, l2_run, vks_lo, vks_hi, vv4, koff4, voff4, krs, vrs, ldsw);
     };
     if (static_max) {
         for (; t + 6 < ntiles; t += 4) {         // all four FULL: K((t+3)+3) exists
@@ -564,12 +543,6 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_kernel_w4(AttnArgs a) {
         iter_full(std::integral_constant<int, 2>{}, t + 2);
         iter_full(std::integral_constant<int, 3>{}, t + 3);
     }
-#ifdef HV_W4_STAMPS
-    if (blockIdx.x == 300 && wave_u == 1 && lane == 0) {       // a mid-launch workgroup (every CU busy), one wave
-        const uint64_t dbg_t1 = __builtin_amdgcn_s_memtime();
-        g_w4_dbg[0] = dbg_vm; g_w4_dbg[1] = dbg_bar; g_w4_dbg[2] = dbg_pre; g_w4_dbg[3] = (unsigned)(dbg_t1 - dbg_t0); g_w4_dbg[4] = (unsigned)t; g_w4_dbg[5] = dbg_p1; g_w4_dbg[6] = dbg_p2; g_w4_dbg[7] = dbg_p3;
-    }
-#endif
     // the tail iterations keep run-time ring offsets: point vk0 at K(t+1)'s buffer (its first PF fragments are already in flight)
     set_vk(((t + 1) & 3) * KV_TILE_BYTES);
     l_run[0] += l2_run[0];
@@ -664,9 +637,6 @@ HvPerDeviceOnce g_w4_lds_once;
 
 // crc32 of the generated iteration this library was compiled from (tests/test_capi_cpu.py compares it with the in-tree .inc)
 extern "C" int hv_attn_w4_loop_signature(void) { return (int)HV_W4_LOOP_SIGNATURE; }
-#ifdef HV_W4_STAMPS
-extern "C" int hv_attn_w4_debug_read(unsigned* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_w4_dbg), sizeof(unsigned) * 8) == hipSuccess ? 0 : -1; }
-#endif
 
 int hv_attn::launch_w4(const AttnArgs& a, dim3 grid, hipStream_t stream) {
     if (hv_set_max_lds(g_w4_lds_once, (const void*)attn_fwd_kernel_w4, W4_LDS) != HV_OK) return HV_ERR_LAUNCH;

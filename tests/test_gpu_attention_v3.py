@@ -4,8 +4,7 @@ bounded-random test never takes it):
   * a late key far above everything before it -> raise_max fires mid-stream, for some rows only;
   * a steadily growing max: every tile raises it by < THR (deferred: never rescaled) vs by > THR (rescaled every tile);
   * the first tile all very negative (tile 0 fixes the initial max) and a huge first key (later tiles vanish);
-The product library ships ONE attention kernel (no run-time selection); the superseded generations live in tools/attn_variants/ and
-are compared on the same cases by tools/attn_variants/check_variants.py when a same-box A/B library is built."""
+The product library ships ONE attention kernel (no run-time selection)."""
 import math
 
 import pytest

@@ -19,60 +19,42 @@ Register map (arch VGPRs pinned by "{v[..]}" constraints, accumulator registers 
 Schedule per iteration t (64 MFMA gaps): see hv_attention_w4.hip header; the tables here are the single source of it.
 """
 import os
-import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.environ.get("HV_W4_INC_OUT") or os.path.join(ROOT, "hunyuanvideo_efficiency_amd", "csrc", "hv_attention_w4_loop.inc")
+OUT = os.path.join(ROOT, "hunyuanvideo_efficiency_amd", "csrc", "hv_attention_w4_loop.inc")
 
 A_O, A_Q, A_KF, A_VF = 0, 128, 192, 224
 RING = 8
-PF = int(os.environ.get("HV_W4_PF", "4"))       # fragments of LDS read-ahead (must match hv_attention_w4.hip)
-WGRP = int(os.environ.get("HV_W4_WGRP", "2"))   # one counted lgkmcnt wait per WGRP fragments (must match hv_attention_w4.hip)
-ORDER = os.environ.get("HV_W4_ORDER", "rdpaem")    # order of a gap's fillers behind its MFMA: fragment reads, DMA piece, packs, adds, exps, row max (memory first: +2.9 % over VALU first, profiles/r03/attn_filler_order.txt)
-EXPD = os.environ.get("HV_W4_EXPD", "")
-DMAPH = int(os.environ.get("HV_W4_DMAPH", "3"))     # the DMA pieces go to gaps = DMAPH (mod 4) of the S phase
-VSPLIT = os.environ.get("HV_W4_VSPLIT", "0") == "1"   # second half of a V fragment read one gap later
-DOT = os.environ.get("HV_W4_DOT", "0") == "1"
-LAG = int(os.environ.get("HV_W4_LAG", "1"))       # gaps between a v_exp_f32 and the pack / row-sum add that read it
+PF = 4          # fragments of LDS read-ahead (must match hv_attention_w4.hip)
+WGRP = 2        # one counted lgkmcnt wait per WGRP fragments (must match hv_attention_w4.hip)
+ORDER = "rdpaem"    # order of a gap's fillers behind its MFMA: fragment reads, DMA piece, packs, adds, exps, row max (memory first: +2.9 % over VALU first, profiles/r03/attn_filler_order.txt)
+DMAPH = 3       # the DMA pieces go to gaps = DMAPH (mod 4) of the S phase
+LAG = 1         # gaps between a v_exp_f32 and the pack / row-sum add that read it
 EXR = 12                                          # ring of the last exponentials (>= 2 per gap x (LAG + 1) + the pair partner)
 V_NEGM, V_PW, V_EX, V_L, V_MX, V_VV, V_KOFF, V_VOFF, V_VKS = 128, 160, 222, 200, 202, 206, 212, 216, 236
 NBUF, TILE_BYTES = 4, 16384
 LDS_KOFF, LDS_VOFF = 0, NBUF * TILE_BYTES      # LDS bytes: [K0 K1 K2 K3 | V0 V1 V2 V3]
 V_L2 = 234      # second partial row sum per query block (v234, v235): consecutive adds never hit the same accumulator
-PKADD = os.environ.get("HV_W4_PKADD") == "1"      # experiment: one v_pk_add_f32 per PAIR of exponentials; pairs (v200,v201) = query block 0
-                                                  # (even, odd exponentials), (v234,v235) = query block 1
 
 
 def l_reg(qb, odd):
-    if PKADD:
-        return (V_L if qb == 0 else V_L2) + odd
     return (V_L2 if odd else V_L) + qb
 
 
 def exps_before(g):
     """exponentials issued before gap g: 5 per 4 gaps through the S phase (gaps 0..31: 40), then one per gap, the last at gap 54 (two in
-    gap 32), so that with the consumers up to LAG = 2 gaps behind, the pack of the last pair (gap <= 56) precedes its MFMA (gap 57)."""
-    if EXPD == "u":     # uniform over gaps 0..53
-        return min(64, (g * 64 + 53) // 54)
-    if EXPD == "f":     # 3 per 2 gaps through the S phase, 2 per 3 gaps after it
-        return g + g // 2 if g <= 32 else min(64, 48 + ((g - 32) * 2 + 2) // 3)
-    if EXPD == "b":     # one per gap through the S phase, 4 per 3 gaps after it
-        return g if g <= 32 else min(64, 32 + ((g - 32) * 4 + 2) // 3)
+    gap 32), so that with the consumers up to 2 gaps behind, the pack of the last pair (gap <= 56) precedes its MFMA (gap 57)."""
     if g <= 32:
         return g + (g + 3) // 4
     return min(64, 41 + (g - 32))
 
 
-def frag_insts(f):
-    return 2 if (16 <= f < 32 and "H" not in ABL) else 1
+def frag_insts(f):      # LDS instructions per fragment: K one ds_read_b128, V two ds_read_b64_tr_b16
+    return 2 if 16 <= f < 32 else 1
 
 
 def wait_for(f):    # first MFMA of fragment f (f % WGRP == 0): f .. f+WGRP-1 landed = all but the reads of f+WGRP .. f+PF-1 outstanding
     return sum(frag_insts(f + i) for i in range(WGRP, PF))
-
-
-ABL = os.environ.get("HV_W4_ABL", "")      # timing-only ablations (WRONG results): v = no softmax VALU, l = no LDS fragment reads, d = no DMA, w = no lgkmcnt waits, m = no row max, H = one ds_read_b128 per V fragment
-STAMPS = os.environ.get("HV_W4_STAMPS") == "1"     # diagnostic build only (never shipped): s_memtime around the barrier's waits
 
 
 def gen_iter(j, static=False):
@@ -83,8 +65,6 @@ def gen_iter(j, static=False):
     KD, VD = LDS_KOFF + ((j + 3) & 3) * TILE_BYTES, LDS_VOFF + ((j + 2) & 3) * TILE_BYTES
     L = []
     A = L.append
-    if STAMPS:      # s[90:99] are this build's scratch (clobbered): t0 = iteration start
-        A("s_memtime s[90:91]")
 
     def s_reg(base, qb, kb, r):
         return f"v{base + 16 * (2 * qb + kb) + r}"
@@ -98,16 +78,10 @@ def gen_iter(j, static=False):
 
     for g in range(64):
         A(f"; ---- gap {g}")
-        if STAMPS and g in (16, 32, 48):      # phase stamps (each drains the LDS queue: timing of this build only)
-            A("s_memtime s[94:95]")
-            A("s_waitcnt lgkmcnt(0)")
-            A("s_sub_u32 s98, s94, s90")
-            A(f"s_add_u32 %[acc_p{g // 16}], %[acc_p{g // 16}], s98")
         dma = g < 32 and (g & 3) == DMAPH
         if dma and ((g >> 2) & 3) == 0:      # M0 once per tensor: piece i adds i * 1024 through its immediate offset
             A(f"s_add_u32 m0, %[ldsw], {KD if g < 16 else VD}")
         # ---- MFMA
-        at_mfma = None
         if g < 32:
             f, qb = g >> 1, g & 1
             kb, ks = f >> 3, f & 7
@@ -115,7 +89,6 @@ def gen_iter(j, static=False):
             if qb == 0 and f % WGRP == 0:
                 A(f"s_waitcnt lgkmcnt({wait_for(f)})")
             c = f"v[{V_NEGM + 16 * qb}:{V_NEGM + 16 * qb + 15}]" if ks == 0 else s_tile(SN, qb, kb)
-            at_mfma = len(L)
             A(f"v_mfma_f32_32x32x16_bf16 {s_tile(SN, qb, kb)}, a[{kf}:{kf + 3}], a[{qf}:{qf + 3}], {c}")
         else:
             j = g - 32
@@ -124,29 +97,13 @@ def gen_iter(j, static=False):
             if qb == 0 and f % WGRP == 0:
                 A(f"s_waitcnt lgkmcnt({wait_for(f)})")
             pw = V_PW + 4 * (4 * qb + kk)
-            at_mfma = len(L)
             A(f"v_mfma_f32_32x32x16_bf16 a[{ot}:{ot + 15}], a[{vf}:{vf + 3}], v[{pw}:{pw + 3}], a[{ot}:{ot + 15}]")
         # ---- barrier: this wave's pieces of K(t+2) / V(t+1) by the counted vmcnt (the 8 youngest = this iteration's), everyone's by the barrier
         if g == 2 * (32 - PF):
-            if STAMPS:
-                A("s_memtime s[92:93]")
-                A("s_waitcnt lgkmcnt(0)")
             A("s_waitcnt vmcnt(8)")
-            if STAMPS:
-                A("s_memtime s[94:95]")
-                A("s_waitcnt lgkmcnt(0)")
             A("s_barrier")
-            if STAMPS:
-                A("s_memtime s[96:97]")
-                A("s_waitcnt lgkmcnt(0)")
-                A("s_sub_u32 s98, s94, s92")
-                A("s_add_u32 %[acc_vm], %[acc_vm], s98")
-                A("s_sub_u32 s98, s96, s94")
-                A("s_add_u32 %[acc_bar], %[acc_bar], s98")
-                A("s_sub_u32 s98, s92, s90")
-                A("s_add_u32 %[acc_pre], %[acc_pre], s98")
-        # ---- the gap's fillers, collected by kind and emitted in ORDER (p packs, a adds, r fragment reads, e exponentials, m row max)
-        packs, adds, reads, exps, maxs = [], [], [], [], []
+        # ---- the gap's fillers, collected by kind and emitted in ORDER (p packs, a adds, r fragment reads, e exponentials, m row max, d DMA)
+        packs, adds, reads, exps, maxs, dmas = [], [], [], [], [], []
         # packs and row-sum adds of the exponentials issued LAG gaps ago (the MFMAs in between separate them from their v_exp_f32)
         if g >= LAG:
             for e in range(exps_before(g - LAG), exps_before(g - LAG + 1)):
@@ -154,17 +111,7 @@ def gen_iter(j, static=False):
                 if j & 1:
                     packs.append(f"v_cvt_pk_bf16_f32 v{V_PW + 4 * (4 * qb + kk) + (j >> 1)}, {ex_reg(e - 1)}, {ex_reg(e)}")
             for e in range(exps_before(g - LAG), exps_before(g - LAG + 1)):
-                kk, qb, j = e >> 4, (e >> 3) & 1, e & 7
-                if DOT:     # row sums from the PACKED words: one v_dot2c_f32_bf16 against (1.0, 1.0) per two exponentials (l then sums exactly the P the PV MFMA uses)
-                    if j & 1:
-                        adds.append(f"v_dot2c_f32_bf16 v{l_reg(qb, (j >> 1) & 1)}, 0x3f803f80, v{V_PW + 4 * (4 * qb + kk) + (j >> 1)}")
-                    continue
-                if PKADD:
-                    if e & 1:
-                        a0 = l_reg(qb, 0)
-                        e0 = V_EX + ((e - 1) % EXR)
-                        adds.append(f"v_pk_add_f32 v[{a0}:{a0 + 1}], v[{a0}:{a0 + 1}], v[{e0}:{e0 + 1}]")
-                    continue
+                qb = (e >> 3) & 1
                 acc = l_reg(qb, e & 1)
                 adds.append(f"v_add_f32 v{acc}, v{acc}, {ex_reg(e)}")
         # fragment reads, PF fragments ahead
@@ -179,18 +126,7 @@ def gen_iter(j, static=False):
                 j2 = f2 - 16
                 kk2, db2 = j2 >> 2, j2 & 3
                 slot = A_VF + 4 * (f2 % RING)
-                if "H" in ABL:      # timing only: what a V pre-transposed in HBM would issue - ONE 16-byte read per fragment (same bytes)
-                    reads.append(f"ds_read_b128 a[{slot}:{slot + 3}], v{V_VKS + (j2 & 7)} offset:{KB1 + (j2 >> 3) * 8192}")      # a conflict-free address pattern (K's)
-                else:
-                    reads.append(f"ds_read_b64_tr_b16 a[{slot}:{slot + 1}], v{V_VV + db2} offset:{VB + kk2 * 4096}")
-                    if not VSPLIT:
-                        reads.append(f"ds_read_b64_tr_b16 a[{slot + 2}:{slot + 3}], v{V_VV + db2} offset:{VB + kk2 * 4096 + 2048}")
-        elif VSPLIT and "H" not in ABL:
-            f2 = g // 2 + PF
-            if 16 <= f2 < 32:
-                j2 = f2 - 16
-                kk2, db2 = j2 >> 2, j2 & 3
-                slot = A_VF + 4 * (f2 % RING)
+                reads.append(f"ds_read_b64_tr_b16 a[{slot}:{slot + 1}], v{V_VV + db2} offset:{VB + kk2 * 4096}")
                 reads.append(f"ds_read_b64_tr_b16 a[{slot + 2}:{slot + 3}], v{V_VV + db2} offset:{VB + kk2 * 4096 + 2048}")
         # exponentials of P(t)
         for e in range(exps_before(g), exps_before(g + 1)):
@@ -206,7 +142,6 @@ def gen_iter(j, static=False):
             else:
                 maxs.append(f"v_max3_f32 v{V_MX + qb}, v{V_MX + qb}, {s_reg(SN, qb, kb, r)}, {s_reg(SN, qb, kb, r + 1)}")
         # ---- DMA piece (K(t+3) at gaps 3..15, V(t+2) at gaps 19..31); M0 was written at the top of the gap
-        dmas = []
         if dma:
             i = (g >> 2) & 3
             if g < 16:
@@ -214,49 +149,8 @@ def gen_iter(j, static=False):
             else:
                 dmas.append(f"buffer_load_dwordx4 v{V_VOFF + i}, %[vrs], 0 offen{f' offset:{i * 1024}' if i else ''} lds")
         kinds = {"p": packs, "a": adds, "r": reads, "e": exps, "m": maxs, "d": dmas}
-        for kind in ORDER:      # an upper-case letter puts that kind in FRONT of the gap's MFMA (behind its wait)
-            if kind.isupper():
-                L[at_mfma:at_mfma] = kinds[kind.lower()]
-                at_mfma += len(kinds[kind.lower()])
-            else:
-                for ln in kinds[kind]:
-                    A(ln)
-    if ABL:
-        def drop(ln):
-            op = ln.split()[0]
-            if "P" in ABL and op == "v_cvt_pk_bf16_f32":
-                return False
-            if "v" in ABL and op in ("v_exp_f32", "v_add_f32", "v_cvt_pk_bf16_f32", "v_max3_f32", "v_max_f32"):
-                return True
-            if "m" in ABL and op in ("v_max3_f32", "v_max_f32"):
-                return True
-            if "l" in ABL and (op.startswith("ds_read") or op == "v_xor_b32"):
-                return True
-            if "d" in ABL and (op.startswith("buffer_load") or (op == "s_add_u32" and "m0" in ln) or ln.startswith("s_waitcnt vmcnt")):
-                return True
-            if "w" in ABL and ln.startswith("s_waitcnt lgkmcnt") and not STAMPS:
-                return True
-            return False
-        L = [ln for ln in L if not drop(ln)]
-        if "S" in ABL:      # timing only: every 32x32x16 MFMA as two 16x16x32 on the same operand registers (same flops, same operand data, garbage results)
-            def split(ln):
-                if not ln.startswith("v_mfma_f32_32x32x16_bf16"):
-                    return [ln]
-                d, a, b, c = [x.strip() for x in ln.split(None, 1)[1].split(", ")]
-                def quad(r, i):
-                    pre, lo = re.match(r"([av])\[(\d+):\d+\]", r).groups()
-                    return f"{pre}[{int(lo) + 4 * i}:{int(lo) + 4 * i + 3}]"
-                return [f"v_mfma_f32_16x16x32_bf16 {quad(d, i)}, {a}, {b}, {quad(c, i)}" for i in range(2)]
-            L = [x for ln in L for x in split(ln)]
-        if "P" in ABL:      # timing only: truncating pack by v_perm_b32 instead of v_cvt_pk_bf16_f32
-            def perm(ln):
-                if not ln.startswith("v_cvt_pk_bf16_f32"):
-                    return ln
-                d, a, b = [x.strip() for x in ln.split(None, 1)[1].split(",")]
-                return f"v_perm_b32 {d}, {b}, {a}, s99"
-            L = ["s_mov_b32 s99, 0x07060302"] + [perm(ln) for ln in L]
-        if "m" in ABL:
-            L += [f"v_mov_b32 v{V_MX}, 0", f"v_mov_b32 v{V_MX + 1}, 0"]
+        for kind in ORDER:
+            L += kinds[kind]
     return L
 
 
@@ -270,21 +164,15 @@ def emit_fn(name, j, static=False):
     def tiles(var, base, pre):
         return ", ".join(f'"{pre}{{v[{base + 16 * (2 * qb + kb)}:{base + 16 * (2 * qb + kb) + 15}]}}"({var}[{qb}][{kb}])' for qb in range(2) for kb in range(2))
     clob = [f'"v{i}"' for i in list(range(V_PW, V_PW + 32)) + list(range(V_EX, V_EX + EXR))]
-    dbg_args = ", uint32_t& acc_vm, uint32_t& acc_bar, uint32_t& acc_pre, uint32_t& acc_p1, uint32_t& acc_p2, uint32_t& acc_p3" if STAMPS else ""
-    dbg_out = ', [acc_vm] "+s"(acc_vm), [acc_bar] "+s"(acc_bar), [acc_pre] "+s"(acc_pre), [acc_p1] "+s"(acc_p1), [acc_p2] "+s"(acc_p2), [acc_p3] "+s"(acc_p3)' if STAMPS else ""
-    if STAMPS:
-        clob += [f'"s{i}"' for i in range(90, 99)]
-    if "P" in ABL:
-        clob += ['"s99"']
     mx_arg = "" if static else "float (&mx)[2], "
     mx_out = "" if static else f', "={{v{V_MX}}}"(mx[0]), "={{v{V_MX + 1}}}"(mx[1])'
     kind = "static row bound in -m: no row max of S'(t+1), never a rescale" if static else "online (deferred) running max: row max of S'(t+1) in mx"
     return f'''// iteration t = {j} (mod 4): S'(t) in {sc}, S'(t+1) produced in {sn}; K(t+1) in ring buffer {(j + 1) & 3}, V(t) in {j & 3}; {kind}
 __device__ __forceinline__ void {name}(f32x16 (&sA)[2][2], f32x16 (&sB)[2][2], const f32x16 (&negm)[2], float (&l)[2], float (&l2)[2], {mx_arg}
-                                       u32x4 vks_lo, u32x4 vks_hi, u32x4 vv, u32x4 koff, u32x4 voff, u32x4 krs, u32x4 vrs, uint32_t ldsw{dbg_args}) {{
+                                       u32x4 vks_lo, u32x4 vks_hi, u32x4 vv, u32x4 koff, u32x4 voff, u32x4 krs, u32x4 vrs, uint32_t ldsw) {{
     asm volatile(
 {text}
-        : {tiles(sn, SN, "=")}, "+{{v{l_reg(0, 0)}}}"(l[0]), "+{{v{l_reg(1, 0)}}}"(l[1]), "+{{v{l_reg(0, 1)}}}"(l2[0]), "+{{v{l_reg(1, 1)}}}"(l2[1]){mx_out}{dbg_out}
+        : {tiles(sn, SN, "=")}, "+{{v{l_reg(0, 0)}}}"(l[0]), "+{{v{l_reg(1, 0)}}}"(l[1]), "+{{v{l_reg(0, 1)}}}"(l2[0]), "+{{v{l_reg(1, 1)}}}"(l2[1]){mx_out}
         : {tiles(sc, SC, "")}, "{{v[{V_NEGM}:{V_NEGM + 15}]}}"(negm[0]), "{{v[{V_NEGM + 16}:{V_NEGM + 31}]}}"(negm[1]),
           "{{v[{V_VKS}:{V_VKS + 3}]}}"(vks_lo), "{{v[{V_VKS + 4}:{V_VKS + 7}]}}"(vks_hi), "{{v[{V_VV}:{V_VV + 3}]}}"(vv),
           "{{v[{V_KOFF}:{V_KOFF + 3}]}}"(koff), "{{v[{V_VOFF}:{V_VOFF + 3}]}}"(voff), [krs] "s"(krs), [vrs] "s"(vrs), [ldsw] "s"(ldsw)
