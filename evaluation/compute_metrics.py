@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""PSNR / SSIM between two folders of videos, on the GPU (the fork's evaluation/compute_metrics.py and, for a --root2 that holds one
+sub-folder per experiment, its compute_metrics_threads.py; the kernel needs no thread pool).
+
+Files are paired by name.  `.pt` (torch.load(weights_only=True); [C,T,H,W] or [1,C,T,H,W], values in [-1, 1] as infer.py writes
+them) and `.npy` (the same layouts, or uint8 frames [T,H,W,C] as save_videos_grid's fallback writes them) are read directly; `.mp4`
+only if imageio is importable - otherwise an .mp4 pair is an error, not a silent skip.  Scores are per frame over the common frames
+and averaged over all frames of all pairs; the result file has the reference's lines.  No LPIPS: it needs AlexNet + LPIPS weights,
+so result files carry no `LPIPS` key."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+EXTS = (".pt", ".npy", ".mp4")
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Compute PSNR / SSIM between two sets of videos on the GPU.")
+    p.add_argument("--root1", type=str, required=True, help="Directory of reference/original videos (.pt, .npy; .mp4 with imageio).")
+    p.add_argument("--root2", type=str, required=True, help="Directory of reconstructed videos, or of one sub-folder per experiment.")
+    p.add_argument("--results-dir", type=str, required=True, help="Directory to store the metric results.")
+    return p.parse_args(argv)
+
+
+def list_videos(root):
+    return sorted(f for f in os.listdir(root) if f.endswith(EXTS) and os.path.isfile(os.path.join(root, f)))
+
+
+def pair_files(root1, root2):
+    """names present in both folders, sorted (compute_metrics.py:96-104)"""
+    return sorted(set(list_videos(root1)) & set(list_videos(root2)))
+
+
+def read_video(path):
+    """-> (tensor [C,T,H,W] on the host, rescale): float videos are in [-1, 1] (rescale=True), uint8 frames become [0, 1] floats"""
+    ext = os.path.splitext(path)[1]
+    if ext == ".pt":
+        x = torch.load(path, map_location="cpu", weights_only=True)
+    elif ext == ".npy":
+        x = torch.from_numpy(np.load(path, allow_pickle=False))
+    else:
+        try:
+            import imageio
+        except ImportError as e:
+            raise RuntimeError(f"{path}: reading .mp4 needs imageio, which is not installed; score the .pt reconstructions instead") from e
+        rd = imageio.get_reader(path)
+        x = torch.from_numpy(np.stack([np.asarray(f) for f in rd]))
+        rd.close()
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{path}: expected one tensor, got {type(x).__name__}")
+    if x.dtype == torch.uint8:                          # frames [T,H,W,C] (or [T,H,W]): q / 255 quantises back to q
+        if x.dim() == 3:
+            x = x[..., None]
+        if x.dim() != 4:
+            raise ValueError(f"{path}: uint8 frames must be [T,H,W,C], got {tuple(x.shape)}")
+        return (x.permute(3, 0, 1, 2).float() / 255.0).contiguous(), False
+    if x.dim() == 5 and x.shape[0] == 1:
+        x = x[0]
+    if x.dim() != 4:
+        raise ValueError(f"{path}: expected [C,T,H,W] or [1,C,T,H,W], got {tuple(x.shape)}")
+    return x, True
+
+
+def score_folders(root1, root2, results_dir, device="cuda"):
+    from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator
+    names = pair_files(root1, root2)
+    if not names:
+        print(f"No matching video files between {root1} and {root2}.")
+        return None
+    print(f"Found {len(names)} matching pairs.")
+    acc = MetricsAccumulator()
+    for name in names:
+        v1, r1 = read_video(os.path.join(root1, name))
+        v2, r2 = read_video(os.path.join(root2, name))
+        if r1 != r2:
+            raise ValueError(f"{name}: one side holds uint8 frames and the other float video")
+        dt = torch.float16 if v1.dtype == torch.float16 and v2.dtype == torch.float16 else torch.float32
+        m = acc.add_video(v1.to(device, dtype=dt), v2.to(device, dtype=dt), rescale=r1)
+        print(f"{name}: PSNR {m['psnr_mean']:.4f} SSIM {m['ssim_mean']:.6f} ({len(m['psnr'])} frames)")
+    results = acc.result()
+    path = acc.save(results_dir, root1, root2)
+    print(f"Results: {results}\nSaved to {path}")
+    return path
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    subdirs = sorted(d for d in os.listdir(a.root2) if os.path.isdir(os.path.join(a.root2, d)))
+    if subdirs and not list_videos(a.root2):            # one folder per experiment: one result file each
+        return [score_folders(a.root1, os.path.join(a.root2, d), os.path.join(a.results_dir, d)) for d in subdirs]
+    return [score_folders(a.root1, a.root2, a.results_dir)]
+
+
+if __name__ == "__main__":
+    main()

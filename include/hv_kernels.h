@@ -296,6 +296,22 @@ int hv_copy4d_16b(const void* src, const int64_t* src_strides, void* dst, const 
 /* K20 tail: (image / 2 + 0.5).clamp(0, 1) in fp16 then .float() (pipeline_hunyuan_video.py:1090-1092). */
 int hv_vae_postprocess_f16_f32(const void* x, float* out, int64_t n, hipStream_t stream);
 
+/* Reconstruction scoring (evaluation/compute_metrics.py:31-41 compute_psnr / compute_ssim of the fork, without the mp4 round trip):
+ * per-frame statistics of two videos a, b [C,T,H,W] (C = 1 | 3; dtype 0 = fp16, 1 = fp32; element strides *_sc, *_st, *_sh, W contiguous)
+ * on the 8-bit frames save_videos_grid would write: q = (uint8) trunc(clamp(rescale ? (x + 1) / 2 : x, 0, 1) * 255), every step in fp32
+ * as utils/file_utils.py:frames_uint8 rounds it.  Outputs, one row per frame: sse int64 [T] = sum (qa - qb)^2 over C,H,W;
+ * minmax int32 [T][4] = min(qa), max(qa), min(qb), max(qb); ssim_sum fp64 [T][C] = sum over the (H-6) x (W-6) window positions of the
+ * SSIM map of channel c (7x7 uniform window, sample covariance, K1 0.01, K2 0.03, data range max(qa) - min(qa) of the frame:
+ * skimage.metrics.structural_similarity's defaults as the fork calls it); 0 for a frame whose `a` is constant (the caller's rule gives
+ * such a frame SSIM 1).  Box moments are exact integers; the map value is fp32, summed in fp64 in a fixed order (no atomics: run-to-run
+ * identical).  passes: 3 = both; 1 = the statistics pass alone (sse, minmax); 2 = the SSIM pass alone, reading the data range from a
+ * `minmax` an earlier statistics pass filled (how tools/bench_metrics.py times the two separately).  workspace: >= hv_video_metrics_workspace_bytes(C, T, H, W) bytes, 16-byte aligned.  H < 7 or W < 7, T > 65535 and
+ * negative or overlapping strides are HV_ERR_ARG (the workspace query returns 0 for them). */
+int hv_video_metrics(const void* a, int64_t a_sc, int64_t a_st, int64_t a_sh, const void* b, int64_t b_sc, int64_t b_st,
+                     int64_t b_sh, int dtype, int C, int T, int H, int W, int rescale, int passes, void* sse, void* minmax,
+                     void* ssim_sum, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int64_t hv_video_metrics_workspace_bytes(int C, int T, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

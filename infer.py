@@ -25,9 +25,11 @@ class VideoTensorDataset:
         return torch.load(path, map_location="cpu", weights_only=True), self.tensor_files[idx]
 
 
-def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1):
+def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, scorer=None, save=True):
     """Reconstructs the first `max_files` tensors, `batch_size` at a time (tensors of one batch must have equal shapes, as a
-    DataLoader's default collate requires); every input still gets its own <name>.pt of shape [1, C, T, H, W]."""
+    DataLoader's default collate requires); every input still gets its own <name>.pt of shape [1, C, T, H, W].
+    `scorer` (a metrics.MetricsAccumulator): each reconstruction is scored against its input while both are on the device
+    (PSNR / SSIM per frame of the common frames).  save=False skips the copy to the host and the .pt files."""
     if batch_size < 1:
         raise ValueError(f"--batch-size must be >= 1, got {batch_size}")
     os.makedirs(output_dir, exist_ok=True)
@@ -43,6 +45,12 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1):
         print(f"Processing {', '.join(names)}, video shape: {tuple(video.shape)}")
         with torch.no_grad():
             recon = model(video, return_dict=False, return_posterior=True, sample_posterior=False)[0]
+        if scorer is not None:
+            m = scorer.add_video(video, recon, rescale=True)
+            for b, name in enumerate(names):
+                print(f"Scored {name}: PSNR {m['psnr'][b].mean():.4f} SSIM {m['ssim'][b].mean():.6f} ({m['psnr'].shape[1]} frames)")
+        if not save:
+            continue
         recon = recon.cpu().float()
         for b, name in enumerate(names):
             out_path = os.path.join(output_dir, f"{name}.pt")
@@ -64,7 +72,16 @@ def parse_args(argv=None):
     p.add_argument("--batch-size", type=int, default=1, help="videos per forward (equal shapes); the VAE runs them one after another")
     p.add_argument("--num-workers", type=int, default=4)
     p.add_argument("--reduced", action="store_true", help="synthetic-weight mode only: reduced channel widths (32,64,128,128)")
-    return p.parse_args(argv)
+    p.add_argument("--score", action="store_true", help="score every reconstruction against its input on the GPU (PSNR / SSIM per frame, "
+                                                       "evaluation/compute_metrics.py without the mp4 round trip) and write metrics_<timestamp>.txt")
+    p.add_argument("--results-dir", type=str, default=None, help="with --score: where the result file goes (default: --output-dir)")
+    p.add_argument("--no-save", action="store_true", help="with --score: do not copy reconstructions to the host or write .pt files")
+    a = p.parse_args(argv)
+    if a.no_save and not a.score:
+        p.error("--no-save is only valid with --score (nothing would be produced)")
+    if a.results_dir and not a.score:
+        p.error("--results-dir is only valid with --score")
+    return a
 
 
 def main(argv=None):
@@ -82,7 +99,16 @@ def main(argv=None):
         if a.config_json:
             from hunyuanvideo_efficiency_amd.vae import _apply_t_ops_config_to_vae, load_t_ops_config
             _apply_t_ops_config_to_vae(vae, load_t_ops_config(a.config_json))
-    return infer_vae(vae, VideoTensorDataset(a.tensor_dir), device, a.output_dir, a.max_files, a.batch_size)
+    if not a.score:
+        return infer_vae(vae, VideoTensorDataset(a.tensor_dir), device, a.output_dir, a.max_files, a.batch_size)
+    from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator
+    scorer = MetricsAccumulator()
+    done = infer_vae(vae, VideoTensorDataset(a.tensor_dir), device, a.output_dir, a.max_files, a.batch_size, scorer, not a.no_save)
+    results = scorer.result()
+    print(f"Results over {scorer.frames} frames: {results}")
+    path = scorer.save(a.results_dir or a.output_dir, a.tensor_dir, a.output_dir)
+    print(f"Saved metrics to {path}")
+    return done
 
 
 if __name__ == "__main__":
