@@ -131,10 +131,174 @@ typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 __device__ __forceinline__ int swz_a(int row) { return (row >> 1) & 7; }
 __device__ __forceinline__ int swz_w(int row) { return (((row >> 3) & 3) << 1) | ((row >> 1) & 1); }
 
-__device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == 1) return gelu_tanh_f(v);
-    if (act == 2) return silu_f(v);
-    return v;
+// ---- pieces shared by every main loop below
+
+// XCD-aware tile mapping (bijective for any grid size): workgroup -> linear tile index, so that each XCD (workgroup id mod 8) gets a
+// contiguous chunk of tiles
+__device__ __forceinline__ int xcd_linear_tile() {
+    const int nwg = gridDim.x;
+    const int bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
+// banded tile order: linear index -> (tm, tn), M fastest inside a band of GROUP_M M-tiles (the last band may be shorter)
+struct TileMN { int tm, tn; };
+__device__ __forceinline__ TileMN tile_of(int lin, int tiles_m, int tiles_n) {
+    const int band = lin / (GROUP_M * tiles_n), rem = lin % (GROUP_M * tiles_n);
+    const int band_m0 = band * GROUP_M;
+    const int gm = min(GROUP_M, tiles_m - band_m0);
+    return TileMN{band_m0 + rem % gm, rem / gm};
+}
+
+// Conv gather: source coordinates of an output row (= output voxel), and the source row a tap reads from them.  Replicate / causal
+// padding = the clamps, nearest upsample = the halvings (first frame not repeated in T), stride = the coordinate multipliers.
+// The pipelined loops keep a row's three coordinates (already multiplied by the stride) PACKED in one register, t in bits 0-7, h in
+// bits 8-19, w in bits 20-31; conv_fits_packing() is the host-side guard of those widths.
+constexpr int PACK_T_LIMIT = 256;       // t coordinates (frames, after the stride; + 1 in the sub-pixel form) must stay below this
+constexpr int PACK_HW_LIMIT = 4096;     // extent of the h and w coordinates: at most this
+struct ConvGather {
+    struct Vox { int t, h, w; };
+    // output row (clamped by the caller: tails read valid rows) -> its voxel in a frames x H x W grid, times the stride
+    static __device__ __forceinline__ Vox voxel(int row, int H, int W, int mt = 1, int mh = 1, int mw = 1, int t0 = 0) {
+        const int w = (row % W) * mw;
+        const int th = row / W;
+        const int t = (th / H) * mt + t0;
+        const int h = (th % H) * mh;
+        return Vox{t, h, w};
+    }
+    static __device__ __forceinline__ uint32_t pack(Vox v) { return (uint32_t)v.t | ((uint32_t)v.h << 8) | ((uint32_t)v.w << 20); }
+    static __device__ __forceinline__ uint32_t pack(const GemmArgs& g, int row) { return pack(voxel(row, g.cH, g.cW, g.mt, g.mh, g.mw)); }
+    static __device__ __forceinline__ int pt(uint32_t c) { return (int)(c & 255u); }
+    static __device__ __forceinline__ int ph(uint32_t c) { return (int)((c >> 8) & 4095u); }
+    static __device__ __forceinline__ int pw(uint32_t c) { return (int)(c >> 20); }
+    // source index of one (strided, tap-shifted) coordinate: causal front pad / replicate pad, then the upsample
+    static __device__ __forceinline__ int src_t(const GemmArgs& g, int t) {
+        int ti = max(t, 0);
+        if (g.up_t) ti = ti == 0 ? 0 : 1 + ((ti - 1) >> 1);
+        return ti;
+    }
+    static __device__ __forceinline__ int src_h(const GemmArgs& g, int h) { return min(max(h, 0), g.bH - 1) >> g.up_hw; }
+    static __device__ __forceinline__ int src_w(const GemmArgs& g, int w) { return min(max(w, 0), g.bW - 1) >> g.up_hw; }
+    static __device__ __forceinline__ uint32_t row_bytes(const GemmArgs& g) { return (uint32_t)g.lda * 2u; }
+    static __device__ __forceinline__ uint32_t src_offset(const GemmArgs& g, int ti, int hi, int wi) {
+        return (uint32_t)((ti * g.sH + hi) * g.sW + wi) * row_bytes(g);
+    }
+    // byte offset of the source row tap (dt, dh, dw) of a packed row reads
+    static __device__ __forceinline__ uint32_t tap_offset(const GemmArgs& g, uint32_t c, int dt, int dh, int dw) {
+        return src_offset(g, src_t(g, pt(c) + dt - 2), src_h(g, ph(c) + dh - 1), src_w(g, pw(c) + dw - 1));
+    }
+    // ... of the centre column dw = 1 (conv128s: unit stride along W, so the column needs no clamp)
+    static __device__ __forceinline__ uint32_t centre_offset(const GemmArgs& g, uint32_t c, int dt, int dh) {
+        return src_offset(g, src_t(g, pt(c) + dt - 2), src_h(g, ph(c) + dh - 1), pw(c) >> g.up_hw);
+    }
+    // ... of a sub-pixel tap: the packed row is a SOURCE-grid voxel, displaced by the tap's offset and clamped there; the offset comes
+    // from the table entry of (parity class, tap), (ot + 8) | (oh + 8) << 4 | (ow + 8) << 8 (wave-uniform: a scalar load, once per cin/64 K-tiles)
+    struct SubTap { uint32_t row_bytes; int ot, oh, ow; };
+    static __device__ __forceinline__ SubTap subpixel_tap(const GemmArgs& g, int cls, int tap) {
+        const uint32_t rb = row_bytes(g);
+        const uint32_t e = g.sp_tab[cls * g.sp_ntap + tap];
+        return SubTap{rb, (int)(e & 15u) - 8, (int)((e >> 4) & 15u) - 8, (int)((e >> 8) & 15u) - 8};
+    }
+    static __device__ __forceinline__ uint32_t subpixel_offset(const GemmArgs& g, uint32_t c, SubTap o) {
+        const int ti = max(pt(c) + o.ot, 0), hi = min(max(ph(c) + o.oh, 0), g.sH - 1), wi = min(max(pw(c) + o.ow, 0), g.sW - 1);
+        return (uint32_t)((ti * g.sH + hi) * g.sW + wi) * o.row_bytes;
+    }
+};
+// host side: the packed-coordinate gather needs cin a power of two (a tap = a whole number of K-tiles found by a shift) and
+// coordinates within the packing
+inline bool conv_fits_packing(int cin, int t_limit, int h_extent, int w_extent) {
+    return (cin & (cin - 1)) == 0 && t_limit < PACK_T_LIMIT && h_extent <= PACK_HW_LIMIT && w_extent <= PACK_HW_LIMIT;
+}
+
+// Source of an LDS-DMA: a wave-uniform base kept a scalar pair (stops the compiler folding it into per-lane 64-bit pointers) ...
+// (a function of its own for gemm_kernel's conv mode, which fixes the base before it refreshes the offsets)
+struct DmaBase { const char* p; };
+__device__ __forceinline__ DmaBase dma_base(const void* src) {
+    uint64_t bv = reinterpret_cast<uint64_t>(src);
+    asm volatile("" : "+s"(bv));
+    return DmaBase{reinterpret_cast<const char*>(bv)};
+}
+// ... plus invariant per-lane byte offsets, one per 16-byte-per-lane piece (512 threads x 16 B = 64 LDS rows = 8 KiB): the saddr +
+// 32-bit voffset form of global_load_lds, no 64-bit vector address arithmetic in the K loop
+template <int NP>
+__device__ __forceinline__ void dma_pieces(DmaBase b, const uint32_t (&off)[NP], char* dst) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        uint32_t o = off[i];
+        asm volatile("" : "+v"(o));        // opaque per iteration: the zero-extension stays next to the load
+        __builtin_amdgcn_global_load_lds((gbl_ptr_t)(b.p + o), (lds_ptr_t)(dst + i * 8192), 16, 0, 0);
+    }
+}
+template <int NP>
+__device__ __forceinline__ void dma_pieces(const void* src, const uint32_t (&off)[NP], char* dst) { dma_pieces(dma_base(src), off, dst); }
+
+// fragment read offsets (bytes inside an LDS operand image of 128-byte rows), k-step 0; k-step 1 flips chunk bit 2 = byte bit 6
+// (A rows: row0 a multiple of 16, so the swizzle depends on fr alone)
+__device__ __forceinline__ int a_frag_offset(int row0, int fr, int fq) { return (row0 + fr) * 128 + ((fq ^ swz_a(fr)) << 4); }
+// W rows are dealt to MFMA rows interleaved: MFMA row fr of the 16-row group at row0 holds W row row0 + (fr >> 2) * 8 + (fr & 3)
+__device__ __forceinline__ int w_frag_offset(int row0, int fr, int fq) {
+    const int w_lr = row0 + (fr >> 2) * 8 + (fr & 3);
+    return w_lr * 128 + ((fq ^ swz_w(w_lr)) << 4);
+}
+
+// Phase protocol of the pipelined loops.  One phase: [fragment reads | DMA issue | counted waits] barrier [MFMA cluster] barrier.
+// phase_sync<VM>() ends the first part: VM is the phase's vmcnt literal (an immediate in the s_waitcnt), the wave's own fragment
+// reads are waited for with lgkmcnt(0), and the MFMA cluster runs at raised priority; phase_sync_novm() is the same for a phase
+// with no DMA to retire.  phase_end() closes the MFMA cluster.  The sched_barriers keep the compiler from moving anything across.
+template <int VM>
+__device__ __forceinline__ void phase_sync() {
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" : : "n"(VM) : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(1);
+}
+__device__ __forceinline__ void phase_sync_novm() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(1);
+}
+__device__ __forceinline__ void phase_end() {
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
+// Hand-off from a pipelined K loop to the epilogue; returns the GemmArgs the epilogue must use.
+// The epilogue's global reads (bias, gate, residual rows, fp8 row scales) must not be hoisted into the K loop's tail: every
+// wait there is a COUNTED vmcnt that assumes the only vector-memory operations in flight are the LDS-DMAs (an extra plain
+// load issued behind them would be among "the N youngest" and let a needed half-tile stay in flight: a race that showed up as
+// wrong N-tail tiles of the fp8 kernel).  The compiler does hoist such loads across an asm with a "memory" clobber (kernel-
+// argument pointers are invariant to it), so the pointers themselves are made opaque here, after the last MFMA phase.
+// ... and every accumulator is pinned HERE, under the full EXEC mask: the epilogue consumes acc[mi][ni] only inside the
+// divergent `column < N` / `row < M` regions, and the compiler sinks pure instructions towards their uses - it moved the last
+// K-tile's v_mfma_scale_* (an intrinsic it does not treat as convergent) into those regions, where they ran with a partial EXEC
+// mask: wrong N-tail tiles in the fp8 kernel only, plus ~200 spilled fragment registers kept alive for the sunk MFMAs.
+template <int MREP, int NREP>
+__device__ __forceinline__ GemmArgs epilogue_handoff(const GemmArgs& g, const f32x4 (&acc)[MREP][NREP]) {
+#pragma unroll
+    for (int mi = 0; mi < MREP; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NREP; ++ni) asm volatile("" : : "v"(acc[mi][ni]));     // a USE, not a redefinition: no effect on the loop's allocation
+    GemmArgs ge = g;
+    asm volatile("s_waitcnt vmcnt(0)" : "+s"(ge.bias), "+s"(ge.gate), "+s"(ge.res), "+s"(ge.a_scale), "+s"(ge.w_scale), "+s"(ge.out0),
+                 "+s"(ge.out1), "+s"(ge.out_f32), "+s"(ge.gn_partial) : : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return ge;
+}
+
+// Launch of one main loop over tiles of BM x BN outputs: one workgroup per tile, the kernel's dynamic LDS size raised once per device
+// (`once` is one per KERNEL).  A caller that lays out its own M tiles (the sub-pixel form: tiles per parity class) sets g.tiles_m.
+template <auto KERNEL, int LDS_BYTES, int BN>
+int launch_tiles(GemmArgs& g, hipStream_t stream) {
+    static HvPerDeviceOnce once;
+    if (hv_set_max_lds(once, (const void*)KERNEL, LDS_BYTES) != HV_OK) return HV_ERR_LAUNCH;
+    if (g.tiles_m == 0) g.tiles_m = (g.M + BM - 1) / BM;
+    g.tiles_n = (g.N + BN - 1) / BN;
+    KERNEL<<<dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(512), LDS_BYTES, stream>>>(g);
+    return hv_check_launch();
 }
 
 // ---- epilogue shared by both main loops: lane holds, per (mi, n-repeat pair), 8 consecutive n of row m
@@ -333,17 +497,8 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel(GemmArgs g) {
     const int wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3;
 
-    // ---- XCD-aware tile mapping (bijective for any grid size)
-    const int nwg = gridDim.x;
-    int lin;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
-    const int band = lin / (GROUP_M * g.tiles_n), rem = lin % (GROUP_M * g.tiles_n);
-    const int band_m0 = band * GROUP_M;
-    const int gm = min(GROUP_M, g.tiles_m - band_m0);
-    const int tm = band_m0 + rem % gm, tn = rem / gm;
+    const TileMN tile = tile_of(xcd_linear_tile(), g.tiles_m, g.tiles_n);
+    const int tm = tile.tm, tn = tile.tn;
     const int m0 = tm * BM, n0 = tn * BN;
 
     // ---- per-thread staging addresses: 4 DMA pieces per operand per K-tile, each 512 thr x 16 B = 64 rows
@@ -363,15 +518,13 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel(GemmArgs g) {
             const int th = ar / g.cW;
             const int vh = (th % g.cH) * g.mh;
             const int vt = (th / g.cH) * g.mt;
-            const uint32_t row_bytes = (uint32_t)g.lda * 2u;
+            const uint32_t row_bytes = ConvGather::row_bytes(g);
             uint32_t aT[3], aH[3], aW[3];
 #pragma unroll
             for (int d = 0; d < 3; ++d) {
-                int ti = max(vt + d - 2, 0);
-                if (g.up_t) ti = ti == 0 ? 0 : 1 + ((ti - 1) >> 1);
-                aT[d] = (uint32_t)ti * (uint32_t)(g.sH * g.sW) * row_bytes;
-                aH[d] = (uint32_t)(min(max(vh + d - 1, 0), g.bH - 1) >> g.up_hw) * (uint32_t)g.sW * row_bytes;
-                aW[d] = (uint32_t)(min(max(vw + d - 1, 0), g.bW - 1) >> g.up_hw) * row_bytes + (uint32_t)((scp ^ swz_a(row)) << 4);
+                aT[d] = (uint32_t)ConvGather::src_t(g, vt + d - 2) * (uint32_t)(g.sH * g.sW) * row_bytes;
+                aH[d] = (uint32_t)ConvGather::src_h(g, vh + d - 1) * (uint32_t)g.sW * row_bytes;
+                aW[d] = (uint32_t)ConvGather::src_w(g, vw + d - 1) * row_bytes + (uint32_t)((scp ^ swz_a(row)) << 4);
             }
             offT[i][0] = aT[0]; offT[i][1] = aT[1] - aT[0]; offT[i][2] = aT[2] - aT[1];
             offH[i][0] = aH[0]; offH[i][1] = aH[1] - aH[0]; offH[i][2] = aH[2] - aH[1];
@@ -402,9 +555,7 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel(GemmArgs g) {
         if (CONV) {
             const int tap = koff / g.cin, c0 = koff - tap * g.cin;
             const int dt = tap / 9, dh = (tap / 3) % 3, dw = tap % 3;
-            uint64_t abv = reinterpret_cast<uint64_t>(g.A + c0);
-            asm volatile("" : "+s"(abv));
-            const char* ab = reinterpret_cast<const char*>(abv);
+            const DmaBase ab = dma_base(g.A + c0);
             if (c0 == 0) {      // a new tap (every cin/64 K-tiles): wave-uniform branch
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -413,32 +564,11 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel(GemmArgs g) {
                                  offH[i][0] + (dh >= 1 ? offH[i][1] : 0u) + (dh >= 2 ? offH[i][2] : 0u) +
                                  offW[i][0] + (dw >= 1 ? offW[i][1] : 0u) + (dw >= 2 ? offW[i][2] : 0u);
             }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                uint32_t o = tap_off[i];
-                asm volatile("" : "+v"(o));
-                __builtin_amdgcn_global_load_lds((gbl_ptr_t)(ab + o), (lds_ptr_t)(base + i * 8192), 16, 0, 0);
-            }
+            dma_pieces(ab, tap_off, base);
         } else {
-            uint64_t abv = reinterpret_cast<uint64_t>(a_tile + koff * 2);
-            asm volatile("" : "+s"(abv));      // keep the tile base a scalar pair: stops the compiler folding it into per-lane 64-bit pointers
-            const char* ab = reinterpret_cast<const char*>(abv);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                uint32_t o = a_o[i];
-                asm volatile("" : "+v"(o));    // opaque per iteration: the zero-extension stays next to the load (saddr + 32-bit voffset form)
-                __builtin_amdgcn_global_load_lds((gbl_ptr_t)(ab + o), (lds_ptr_t)(base + i * 8192), 16, 0, 0);
-            }
+            dma_pieces(a_tile + koff * 2, a_o, base);
         }
-        uint64_t wbv = reinterpret_cast<uint64_t>(w_tile + koff * 2);
-        asm volatile("" : "+s"(wbv));
-        const char* wb = reinterpret_cast<const char*>(wbv);
-#pragma unroll
-        for (int i = 0; i < WPIECES; ++i) {
-            uint32_t o = w_o[i];
-            asm volatile("" : "+v"(o));
-            __builtin_amdgcn_global_load_lds((gbl_ptr_t)(wb + o), (lds_ptr_t)(base + TILE_BYTES + i * 8192), 16, 0, 0);
-        }
+        dma_pieces(w_tile + koff * 2, w_o, base + TILE_BYTES);
     };
 
     // ---- fragment read offsets (bytes inside an operand tile), k-step 0; k-step 1 flips chunk bit 2
@@ -525,16 +655,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
 
-    const int nwg = gridDim.x;
-    int lin;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
-    const int band = lin / (GROUP_M * g.tiles_n), rem = lin % (GROUP_M * g.tiles_n);
-    const int band_m0 = band * GROUP_M;
-    const int gm = min(GROUP_M, g.tiles_m - band_m0);
-    const int tm = band_m0 + rem % gm, tn = rem / gm;
+    const TileMN tile = tile_of(xcd_linear_tile(), g.tiles_m, g.tiles_n);
+    const int tm = tile.tm, tn = tile.tn;
     int m0 = tm * BM;
     const int n0 = tn * 256;
     // sub-pixel mode: the M tile's output parity class and its class-local rows
@@ -562,14 +684,9 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
                 if constexpr (SP) {
                     // sub-pixel mode: row = voxel (kt, kh, kw) of the SOURCE grid; the frame coordinate is the k of "taps on frames
                     // k-1, k" (odd frames of a temporally upsampled output: k = kt + 1)
-                    const int ar = min(m0 + arow, sp_M - 1);
-                    const int kw = ar % g.sW, th = ar / g.sW;
-                    a_o[h][i] = (uint32_t)(th / g.sH + sp_pt) | ((uint32_t)(th % g.sH) << 8) | ((uint32_t)kw << 20);
-                } else {
-                const int ar = min(m0 + arow, g.M - 1);
-                const int vw = (ar % g.cW) * g.mw, th = ar / g.cW;
-                a_o[h][i] = (uint32_t)((th / g.cH) * g.mt) | ((uint32_t)((th % g.cH) * g.mh) << 8) | ((uint32_t)vw << 20);
-                }
+                    a_o[h][i] = ConvGather::pack(ConvGather::voxel(min(m0 + arow, sp_M - 1), g.sH, g.sW, 1, 1, 1, sp_pt));
+                } else
+                a_o[h][i] = ConvGather::pack(g, min(m0 + arow, g.M - 1));
             } else
             a_o[h][i] = (uint32_t)((int64_t)(min(m0 + arow, g.M - 1) - m0) * g.lda * DT::ESIZE + ((scp ^ swz_a(srow)) << 4));
             const int lr = i * 64 + srow;                                   // LDS row of half-tile Bn<h>
@@ -584,31 +701,16 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
     uint32_t tap_off[2][2] = {{0u, 0u}, {0u, 0u}};
     const uint32_t a_chunk = (uint32_t)((scp ^ swz_a(srow)) << 4);
     const int lg_cin = CONV ? 31 - __builtin_clz((unsigned)g.cin) : 0;       // cin is a power of two >= 256 here (host-side dispatch)
-    auto conv_tap = [&](int h, int tap) {      // wave-uniform tap (dt, dh, dw): replicate / causal padding = the clamps, upsample = the halvings
-        const uint32_t row_bytes = (uint32_t)g.lda * 2u;
+    auto conv_tap = [&](int h, int tap) {      // wave-uniform tap (dt, dh, dw), or entry `tap` of the class's offset table
         if constexpr (SP) {
-            const uint32_t e = g.sp_tab[sp_c * g.sp_ntap + tap];      // wave-uniform: a scalar load, once per cin/64 K-tiles
-            const int ot = (int)(e & 15u) - 8, oh = (int)((e >> 4) & 15u) - 8, ow = (int)((e >> 8) & 15u) - 8;
+            const ConvGather::SubTap o = ConvGather::subpixel_tap(g, sp_c, tap);
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const uint32_t c = a_o[h][i];
-                const int ti = max((int)(c & 255u) + ot, 0);
-                const int hi = min(max((int)((c >> 8) & 4095u) + oh, 0), g.sH - 1);
-                const int wi = min(max((int)(c >> 20) + ow, 0), g.sW - 1);
-                tap_off[h][i] = (uint32_t)((ti * g.sH + hi) * g.sW + wi) * row_bytes + a_chunk;
-            }
+            for (int i = 0; i < 2; ++i) tap_off[h][i] = ConvGather::subpixel_offset(g, a_o[h][i], o) + a_chunk;
             return;
         }
         const int dt = tap / 9, dh = (tap / 3) % 3, dw = tap % 3;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const uint32_t c = a_o[h][i];
-            int ti = max((int)(c & 255u) + dt - 2, 0);
-            if (g.up_t) ti = ti == 0 ? 0 : 1 + ((ti - 1) >> 1);
-            const int hi = min(max((int)((c >> 8) & 4095u) + dh - 1, 0), g.bH - 1) >> g.up_hw;
-            const int wi = min(max((int)(c >> 20) + dw - 1, 0), g.bW - 1) >> g.up_hw;
-            tap_off[h][i] = (uint32_t)((ti * g.sH + hi) * g.sW + wi) * row_bytes + a_chunk;
-        }
+        for (int i = 0; i < 2; ++i) tap_off[h][i] = ConvGather::tap_offset(g, a_o[h][i], dt, dh, dw) + a_chunk;
     };
 
     // half-tile J (0 Am0, 1 Bn0, 2 Bn1, 3 Am1) of K-tile `tile` into buffer `buf` (wave-uniform: the destination goes through M0)
@@ -617,29 +719,21 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
         char* dst = smem + buf * BUF8_BYTES + J * HT_BYTES + wave_lds;
         constexpr bool isA = (J == 0 || J == 3);
         constexpr int h = (J == 3 || J == 2) ? 1 : 0;
-        uint64_t bv;
+        const char* src;
         if constexpr (CONV && isA) {
             const int tap = (tile * BK) >> lg_cin, c0 = tile * BK - (tap << lg_cin);
             if (c0 == 0) conv_tap(h, tap);       // a new tap for this stream: once per cin/64 K-tiles
-            bv = reinterpret_cast<uint64_t>(a_tile + c0 * 2);
+            src = a_tile + c0 * 2;
         } else {
-            bv = reinterpret_cast<uint64_t>((isA ? a_tile : w_tile) + (int64_t)tile * (BK * 2));
+            src = (isA ? a_tile : w_tile) + (int64_t)tile * (BK * 2);
         }
-        asm volatile("" : "+s"(bv));
-        const char* b = reinterpret_cast<const char*>(bv);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            uint32_t o = isA ? (CONV ? tap_off[h][i] : a_o[h][i]) : w_o[h][i];
-            asm volatile("" : "+v"(o));
-            __builtin_amdgcn_global_load_lds((gbl_ptr_t)(b + o), (lds_ptr_t)(dst + i * 8192), 16, 0, 0);
-        }
+        dma_pieces(src, isA ? (CONV ? tap_off[h] : a_o[h]) : w_o[h], dst);
     };
 
     // ---- fragment read offsets inside a half-tile (k-step 0; k-step 1 flips chunk bit 2 = byte bit 6)
     const int fr = lane & 15, fq = lane >> 4;
-    const int a_rd = (wm * 64 + fr) * 128 + ((fq ^ swz_a(fr)) << 4);                         // + mi * 2048
-    const int w_lr = wn * 32 + (fr >> 2) * 8 + (fr & 3);                                     // + (ni & 1) * 4 rows = 512 B
-    const int w_rd = w_lr * 128 + ((fq ^ swz_w(w_lr)) << 4);
+    const int a_rd = a_frag_offset(wm * 64, fr, fq);                                        // + mi * 2048
+    const int w_rd = w_frag_offset(wn * 32, fr, fq);                                         // + (ni & 1) * 4 rows = 512 B
 
     f32x4 acc[8][4];
 #pragma unroll
@@ -695,25 +789,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
     using I2 = std::integral_constant<int, 2>;
     using I3 = std::integral_constant<int, 3>;
 
-    // one phase: [fragment reads | DMA issue | counted waits] barrier [16 MFMAs] barrier.   VM = vmcnt literal of this phase.
-#define HV_PHASE_SYNC(VM)                                            \
-    asm volatile("s_waitcnt vmcnt(" #VM ")\n\ts_waitcnt lgkmcnt(0)" ::: "memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                \
-    __builtin_amdgcn_s_barrier();                                     \
-    __builtin_amdgcn_sched_barrier(0);                                \
-    __builtin_amdgcn_s_setprio(1);
-#define HV_PHASE_SYNC_NOVM()                                          \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                \
-    __builtin_amdgcn_sched_barrier(0);                                \
-    __builtin_amdgcn_s_barrier();                                     \
-    __builtin_amdgcn_sched_barrier(0);                                \
-    __builtin_amdgcn_s_setprio(1);
-#define HV_PHASE_END()                                                \
-    __builtin_amdgcn_s_setprio(0);                                    \
-    __builtin_amdgcn_sched_barrier(0);                                \
-    __builtin_amdgcn_s_barrier();                                     \
-    __builtin_amdgcn_sched_barrier(0);
-
+    // one phase: [fragment reads | DMA issue | counted waits] barrier [16 MFMAs] barrier (phase_sync<vmcnt literal> ... phase_end).
     // KIND 0: steady (every phase issues, vmcnt(10)); 1: tile nkt-2 (only phase 1 issues; 10, 8, 6, 4); 2: tile nkt-1 (2, 0, 0, 0)
     auto tile_fn = [&](auto BUFc, auto KINDc, int t) {
         constexpr int BUF = decltype(BUFc)::value, KIND = decltype(KINDc)::value;
@@ -728,24 +804,24 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
             __builtin_amdgcn_sched_barrier(0);
             readA(B{}, I0{});
             if constexpr (KIND <= 1) stage(I1{}, BUF ^ 1, t + 1);
-            HV_PHASE_SYNC_NOVM()
+            phase_sync_novm();
             mma(I0{}, I0{}, wf0);
-            HV_PHASE_END()
+            phase_end();
             readB(B{}, I1{}, wf0);
             if constexpr (KIND == 0) stage(I0{}, BUF, t + 2);
-            HV_PHASE_SYNC_NOVM()
+            phase_sync_novm();
             mma(I0{}, I1{}, wf0);
-            HV_PHASE_END()
+            phase_end();
             readA(B{}, I1{});
             if constexpr (KIND == 0) stage(I2{}, BUF, t + 2);
-            HV_PHASE_SYNC_NOVM()
+            phase_sync_novm();
             mma(I1{}, I1{}, wf0);
-            HV_PHASE_END()
+            phase_end();
             readB(B{}, I0{}, wf0);
             if constexpr (KIND == 0) stage(I3{}, BUF, t + 2);
-            if constexpr (KIND == 0) { HV_PHASE_SYNC(6) } else { HV_PHASE_SYNC(0) }
+            if constexpr (KIND == 0) phase_sync<6>(); else phase_sync<0>();
             mma(I1{}, I0{}, wf0);
-            HV_PHASE_END()
+            phase_end();
             return;
         }
         // phase 1: Q(m0, n0)
@@ -753,26 +829,26 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
         __builtin_amdgcn_sched_barrier(0);
         readA(B{}, I0{});
         if constexpr (KIND <= 1) stage(I3{}, BUF ^ 1, t + 1);
-        if constexpr (KIND <= 1) { HV_PHASE_SYNC(10) } else { HV_PHASE_SYNC(2) }
+        if constexpr (KIND <= 1) phase_sync<10>(); else phase_sync<2>();
         mma(I0{}, I0{}, wf0);
-        HV_PHASE_END()
+        phase_end();
         // phase 2: Q(m0, n1)
         readB(B{}, I1{}, wf1);
         if constexpr (KIND == 0) stage(I0{}, BUF, t + 2);
-        if constexpr (KIND == 0) { HV_PHASE_SYNC(10) } else if constexpr (KIND == 1) { HV_PHASE_SYNC(8) } else { HV_PHASE_SYNC(0) }
+        if constexpr (KIND == 0) phase_sync<10>(); else if constexpr (KIND == 1) phase_sync<8>(); else phase_sync<0>();
         mma(I0{}, I1{}, wf1);
-        HV_PHASE_END()
+        phase_end();
         // phase 3: Q(m1, n1)
         readA(B{}, I1{});
         if constexpr (KIND == 0) stage(I1{}, BUF, t + 2);
-        if constexpr (KIND == 0) { HV_PHASE_SYNC(10) } else if constexpr (KIND == 1) { HV_PHASE_SYNC(6) } else { HV_PHASE_SYNC(0) }
+        if constexpr (KIND == 0) phase_sync<10>(); else if constexpr (KIND == 1) phase_sync<6>(); else phase_sync<0>();
         mma(I1{}, I1{}, wf1);
-        HV_PHASE_END()
+        phase_end();
         // phase 4: Q(m1, n0)   (B(n0) still in registers from phase 1)
         if constexpr (KIND == 0) stage(I2{}, BUF, t + 2);
-        if constexpr (KIND == 0) { HV_PHASE_SYNC(10) } else if constexpr (KIND == 1) { HV_PHASE_SYNC(4) } else { HV_PHASE_SYNC(0) }
+        if constexpr (KIND == 0) phase_sync<10>(); else if constexpr (KIND == 1) phase_sync<4>(); else phase_sync<0>();
         mma(I1{}, I0{}, wf0);
-        HV_PHASE_END()
+        phase_end();
     };
 
     // ---- prologue: half-tiles 0..6 (K-tile 0 and Am0, Bn0, Bn1 of K-tile 1); phase 0 reads half-tiles 0 and 1.
@@ -807,50 +883,13 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
     tile_fn(I0{}, I1{}, t);
     tile_fn(I1{}, I2{}, t + 1);
     if (wm == 0) __builtin_amdgcn_s_barrier();      // balance the barrier count of the staggered rows
-#undef HV_PHASE_SYNC
-#undef HV_PHASE_SYNC_NOVM
-#undef HV_PHASE_END
-    // The epilogue's global reads (bias, gate, residual rows, fp8 row scales) must not be hoisted into the K loop's tail: every
-    // wait there is a COUNTED vmcnt that assumes the only vector-memory operations in flight are the LDS-DMAs (an extra plain
-    // load issued behind them would be among "the N youngest" and let a needed half-tile stay in flight: a race that showed up as
-    // wrong N-tail tiles of the fp8 kernel).  The compiler does hoist such loads across an asm with a "memory" clobber (kernel-
-    // argument pointers are invariant to it), so the pointers themselves are made opaque here, after the last MFMA phase.
-    // ... and every accumulator is pinned HERE, under the full EXEC mask: the epilogue consumes acc[mi][ni] only inside the
-    // divergent `column < N` / `row < M` regions, and the compiler sinks pure instructions towards their uses - it moved the last
-    // K-tile's v_mfma_scale_* (an intrinsic it does not treat as convergent) into those regions, where they ran with a partial EXEC
-    // mask: wrong N-tail tiles in the fp8 kernel only, plus ~200 spilled fragment registers kept alive for the sunk MFMAs.
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) asm volatile("" : : "v"(acc[mi][ni]));     // a USE, not a redefinition: no effect on the loop's allocation
-    GemmArgs ge = g;
-    asm volatile("s_waitcnt vmcnt(0)" : "+s"(ge.bias), "+s"(ge.gate), "+s"(ge.res), "+s"(ge.a_scale), "+s"(ge.w_scale), "+s"(ge.out0),
-                 "+s"(ge.out1), "+s"(ge.out_f32), "+s"(ge.gn_partial) : : "memory");
-    __builtin_amdgcn_sched_barrier(0);
+    GemmArgs ge = epilogue_handoff(g, acc);
     if constexpr (SP) {
         ge.M = sp_M;
         const SpRowMap rm{g.sH, g.sW, g.cH, g.cW, g.up_t, sp_pt, (sp_c >> 1) & 1, sp_c & 1};
         gemm_epilogue<DT, 8, 4, 16, SpRowMap>(ge, acc, m0 + wm * 128 + fr, n0 + wn * 64, fq, rm, tm * 4 + wm * 2);
     } else
     gemm_epilogue<DT, 8, 4>(ge, acc, m0 + wm * 128 + fr, n0 + wn * 64, fq, IdRowMap(), tm * 4 + wm * 2);
-}
-
-template <typename DT, bool CONV = false>
-int launch_gemm8(GemmArgs& g, hipStream_t stream) {
-    static HvPerDeviceOnce once;
-    if (hv_set_max_lds(once, (const void*)gemm8_kernel<DT, CONV>, LDS8_BYTES) != HV_OK) return HV_ERR_LAUNCH;
-    g.tiles_m = (g.M + BM - 1) / BM;
-    g.tiles_n = (g.N + 255) / 256;
-    gemm8_kernel<DT, CONV><<<dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(512), LDS8_BYTES, stream>>>(g);
-    return hv_check_launch();
-}
-
-int launch_gemm8_subpixel(GemmArgs& g, hipStream_t stream) {      // g.tiles_m / sp_* filled by the caller
-    static HvPerDeviceOnce once;
-    if (hv_set_max_lds(once, (const void*)gemm8_kernel<F16T, true, true>, LDS8_BYTES) != HV_OK) return HV_ERR_LAUNCH;
-    g.tiles_n = (g.N + 255) / 256;
-    gemm8_kernel<F16T, true, true><<<dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(512), LDS8_BYTES, stream>>>(g);
-    return hv_check_launch();
 }
 
 // =====================================================================================================================
@@ -876,12 +915,7 @@ __global__ __launch_bounds__(512, 2) void conv128_kernel(GemmArgs g) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;          // waves 0-3 (wm 0,1) / 4-7 (wm 2,3) = the two waves of every SIMD
 
-    const int nwg = gridDim.x;
-    int lin;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int lin = xcd_linear_tile();
     const int tm = lin / g.tiles_n, tn = lin % g.tiles_n;       // tiles_n == 1 for every 128-channel layer: consecutive M tiles per XCD
     const int m0 = tm * BM, n0 = tn * 128;
 
@@ -893,9 +927,7 @@ __global__ __launch_bounds__(512, 2) void conv128_kernel(GemmArgs g) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int arow = (lr >> 5) * 64 + h * 32 + (lr & 31);           // tile row: wave row (lr>>5), its rows [h*32, h*32+32)
-            const int ar = min(m0 + arow, g.M - 1);
-            const int vw = (ar % g.cW) * g.mw, th = ar / g.cW;
-            a_o[h][i] = (uint32_t)((th / g.cH) * g.mt) | ((uint32_t)((th % g.cH) * g.mh) << 8) | ((uint32_t)vw << 20);
+            a_o[h][i] = ConvGather::pack(g, min(m0 + arow, g.M - 1));
         }
         w_o[i] = (uint32_t)((int64_t)(min(n0 + lr, g.N - 1) - n0) * g.ldw * 2 + ((scp ^ swz_w(lr)) << 4));
     }
@@ -906,44 +938,26 @@ __global__ __launch_bounds__(512, 2) void conv128_kernel(GemmArgs g) {
     const int lg_cin = 31 - __builtin_clz((unsigned)g.cin);
     auto conv_tap = [&](int h, int tap) {
         const int dt = tap / 9, dh = (tap / 3) % 3, dw = tap % 3;
-        const uint32_t row_bytes = (uint32_t)g.lda * 2u;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const uint32_t c = a_o[h][i];
-            int ti = max((int)(c & 255u) + dt - 2, 0);
-            if (g.up_t) ti = ti == 0 ? 0 : 1 + ((ti - 1) >> 1);
-            const int hi = min(max((int)((c >> 8) & 4095u) + dh - 1, 0), g.bH - 1) >> g.up_hw;
-            const int wi = min(max((int)(c >> 20) + dw - 1, 0), g.bW - 1) >> g.up_hw;
-            tap_off[h][i] = (uint32_t)((ti * g.sH + hi) * g.sW + wi) * row_bytes + a_chunk;
-        }
+        for (int i = 0; i < 2; ++i) tap_off[h][i] = ConvGather::tap_offset(g, a_o[h][i], dt, dh, dw) + a_chunk;
     };
     // unit U (0 Am0, 1 B, 2 Am1) of K-tile `tile` into buffer `buf`
     auto stage = [&](auto Uc, int buf, int tile) {
         constexpr int U = decltype(Uc)::value;
         char* dst = smem + buf * C128_BUF + U * C128_UNIT + wave_lds;
-        uint64_t bv;
         if constexpr (U != 1) {
             constexpr int h = U >> 1;
             const int tap = (tile * BK) >> lg_cin, c0 = tile * BK - (tap << lg_cin);
             if (c0 == 0) conv_tap(h, tap);
-            bv = reinterpret_cast<uint64_t>(a_base + c0 * 2);
+            dma_pieces(a_base + c0 * 2, tap_off[h], dst);
         } else {
-            bv = reinterpret_cast<uint64_t>(w_tile + (int64_t)tile * (BK * 2));
-        }
-        asm volatile("" : "+s"(bv));
-        const char* b = reinterpret_cast<const char*>(bv);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            uint32_t o = U == 1 ? w_o[i] : tap_off[U >> 1][i];
-            asm volatile("" : "+v"(o));
-            __builtin_amdgcn_global_load_lds((gbl_ptr_t)(b + o), (lds_ptr_t)(dst + i * 8192), 16, 0, 0);
+            dma_pieces(w_tile + (int64_t)tile * (BK * 2), w_o, dst);
         }
     };
 
     const int fr = lane & 15, fq = lane >> 4;
-    const int a_rd = (wm * 32 + fr) * 128 + ((fq ^ swz_a(fr)) << 4);                         // + mi' * 2048 (mi' = 0, 1)
-    const int w_lr = wn * 64 + (fr >> 2) * 8 + (fr & 3);                                     // + (ni>>1)*32 rows + (ni&1)*4 rows
-    const int w_rd = w_lr * 128 + ((fq ^ swz_w(w_lr)) << 4);
+    const int a_rd = a_frag_offset(wm * 32, fr, fq);                                        // + mi' * 2048 (mi' = 0, 1)
+    const int w_rd = w_frag_offset(wn * 64, fr, fq);                                         // + (ni>>1)*32 rows + (ni&1)*4 rows
 
     f32x4 acc[4][4];
 #pragma unroll
@@ -980,17 +994,6 @@ __global__ __launch_bounds__(512, 2) void conv128_kernel(GemmArgs g) {
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>;
-#define HV_C_SYNC(VM)                                                 \
-    asm volatile("s_waitcnt vmcnt(" #VM ")\n\ts_waitcnt lgkmcnt(0)" ::: "memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                \
-    __builtin_amdgcn_s_barrier();                                     \
-    __builtin_amdgcn_sched_barrier(0);                                \
-    __builtin_amdgcn_s_setprio(1);
-#define HV_C_END()                                                    \
-    __builtin_amdgcn_s_setprio(0);                                    \
-    __builtin_amdgcn_sched_barrier(0);                                \
-    __builtin_amdgcn_s_barrier();                                     \
-    __builtin_amdgcn_sched_barrier(0);
     // KIND 0 steady (issues for tile t+2; vmcnt 10 / 8), 1 = tile nkt-2 (no issue; 6 / 2), 2 = tile nkt-1 (0 / 0)
     auto tile_fn = [&](auto BUFc, auto KINDc, int t) {
         constexpr int BUF = decltype(BUFc)::value, KIND = decltype(KINDc)::value;
@@ -1000,14 +1003,14 @@ __global__ __launch_bounds__(512, 2) void conv128_kernel(GemmArgs g) {
         __builtin_amdgcn_sched_barrier(0);
         readA(B{}, I0{});
         if constexpr (KIND == 0) { stage(I0{}, NB, t + 2); stage(I1{}, NB, t + 2); }
-        if constexpr (KIND == 0) { HV_C_SYNC(10) } else if constexpr (KIND == 1) { HV_C_SYNC(6) } else { HV_C_SYNC(0) }
+        if constexpr (KIND == 0) phase_sync<10>(); else if constexpr (KIND == 1) phase_sync<6>(); else phase_sync<0>();
         mma(I0{});
-        HV_C_END()
+        phase_end();
         readA(B{}, I1{});
         if constexpr (KIND == 0) stage(I2{}, NB, t + 2);
-        if constexpr (KIND == 0) { HV_C_SYNC(8) } else if constexpr (KIND == 1) { HV_C_SYNC(2) } else { HV_C_SYNC(0) }
+        if constexpr (KIND == 0) phase_sync<8>(); else if constexpr (KIND == 1) phase_sync<2>(); else phase_sync<0>();
         mma(I1{});
-        HV_C_END()
+        phase_end();
     };
 
     const int nkt = g.K / BK;      // a multiple of 3, >= 27 (host-side dispatch)
@@ -1028,26 +1031,8 @@ __global__ __launch_bounds__(512, 2) void conv128_kernel(GemmArgs g) {
     tile_fn(I1{}, I1{}, t + 1);
     tile_fn(I2{}, I2{}, t + 2);
     if (wm < 2) __builtin_amdgcn_s_barrier();
-#undef HV_C_SYNC
-#undef HV_C_END
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) asm volatile("" : : "v"(acc[mi][ni]));
-    GemmArgs ge = g;
-    asm volatile("s_waitcnt vmcnt(0)" : "+s"(ge.bias), "+s"(ge.gate), "+s"(ge.res), "+s"(ge.a_scale), "+s"(ge.w_scale), "+s"(ge.out0),
-                 "+s"(ge.out1), "+s"(ge.out_f32), "+s"(ge.gn_partial) : : "memory");
-    __builtin_amdgcn_sched_barrier(0);
+    const GemmArgs ge = epilogue_handoff(g, acc);
     gemm_epilogue<DT, 4, 4>(ge, acc, m0 + wm * 64 + fr, n0 + wn * 64, fq, IdRowMap(), tm * 4 + wm);
-}
-
-int launch_conv128(GemmArgs& g, hipStream_t stream) {
-    static HvPerDeviceOnce once;
-    if (hv_set_max_lds(once, (const void*)conv128_kernel, C128_LDS) != HV_OK) return HV_ERR_LAUNCH;
-    g.tiles_m = (g.M + BM - 1) / BM;
-    g.tiles_n = (g.N + 127) / 128;
-    conv128_kernel<<<dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(512), C128_LDS, stream>>>(g);
-    return hv_check_launch();
 }
 
 // =====================================================================================================================
@@ -1096,12 +1081,7 @@ __device__ __forceinline__ void conv128s_body(GemmArgs g) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
 
-    const int nwg = gridDim.x;
-    int lin;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int lin = xcd_linear_tile();
     const int m0 = lin * BM;          // tiles_n == 1
 
     const int srow = tid >> 3, scp = tid & 7;
@@ -1112,8 +1092,7 @@ __device__ __forceinline__ void conv128s_body(GemmArgs g) {
         for (int u = 0; u < 2; ++u) {
             const int R = u * 128 + i * 64 + srow;                          // LDS row R holds tile row 4 * (R & 63) + (R >> 6)
             const int ar = min(m0 + (((R & 63) << 2) | (R >> 6)), g.M - 1);
-            const int vw = ar % g.cW, th = ar / g.cW;
-            a_o[u][i] = (uint32_t)((th / g.cH) * g.mt) | ((uint32_t)((th % g.cH) * g.mh) << 8) | ((uint32_t)vw << 20);
+            a_o[u][i] = ConvGather::pack(ConvGather::voxel(ar, g.cH, g.cW, g.mt, g.mh));      // unit stride along W (host-side dispatch)
         }
         const int lr = i * 64 + srow;
         w_o[i] = (uint32_t)((int64_t)min(lr, g.N - 1) * g.ldw * 2 + ((scp ^ swz_w(lr)) << 4));
@@ -1125,45 +1104,21 @@ __device__ __forceinline__ void conv128s_body(GemmArgs g) {
     const int lg_cpk = 31 - __builtin_clz((unsigned)g.cin) - 6;      // log2(K-tiles per tap)
     const int cpk_mask = (1 << lg_cpk) - 1;
     auto conv_row = [&](int u, int dt, int dh) {                     // gather offsets of the centre tap (dt, dh, 1)
-        const uint32_t row_bytes = (uint32_t)g.lda * 2u;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const uint32_t c = a_o[u][i];
-            int ti = max((int)(c & 255u) + dt - 2, 0);
-            if (g.up_t) ti = ti == 0 ? 0 : 1 + ((ti - 1) >> 1);
-            const int hi = min(max((int)((c >> 8) & 4095u) + dh - 1, 0), g.bH - 1) >> g.up_hw;
-            const int wi = (int)(c >> 20) >> g.up_hw;
-            tap_off[u][i] = (uint32_t)((ti * g.sH + hi) * g.sW + wi) * row_bytes + a_chunk;
-        }
+        for (int i = 0; i < 2; ++i) tap_off[u][i] = ConvGather::centre_offset(g, a_o[u][i], dt, dh) + a_chunk;
     };
     auto stageA = [&](auto Uc, int grp) {                            // half U of group grp's activation block
         constexpr int U = decltype(Uc)::value;
         char* dst = smem + CS_A0 + (grp & 1) * CS_ABUF + U * 16384 + wave_lds;
         const int dtdh = grp >> lg_cpk, cc = grp & cpk_mask;
         if (cc == 0) conv_row(U, dtdh / 3, dtdh % 3);
-        uint64_t bv = reinterpret_cast<uint64_t>(a_base + cc * (BK * 2));
-        asm volatile("" : "+s"(bv));
-        const char* b = reinterpret_cast<const char*>(bv);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            uint32_t o = tap_off[U][i];
-            asm volatile("" : "+v"(o));
-            __builtin_amdgcn_global_load_lds((gbl_ptr_t)(b + o), (lds_ptr_t)(dst + i * 8192), 16, 0, 0);
-        }
+        dma_pieces(a_base + cc * (BK * 2), tap_off[U], dst);
     };
     auto stageB = [&](int tile) {                                    // weights of K-tile `tile` (loop order) into slot tile & 3
         char* dst = smem + (tile & 3) * CS_SLOT + wave_lds;
         const int grp = tile / 3, dw = tile - grp * 3;
         const int kt = ((((grp >> lg_cpk) * 3 + dw) << lg_cpk) + (grp & cpk_mask));      // K-tile index in the weight layout
-        uint64_t bv = reinterpret_cast<uint64_t>(w_base + (int64_t)kt * (BK * 2));
-        asm volatile("" : "+s"(bv));
-        const char* b = reinterpret_cast<const char*>(bv);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            uint32_t o = w_o[i];
-            asm volatile("" : "+v"(o));
-            __builtin_amdgcn_global_load_lds((gbl_ptr_t)(b + o), (lds_ptr_t)(dst + i * 8192), 16, 0, 0);
-        }
+        dma_pieces(w_base + (int64_t)kt * (BK * 2), w_o, dst);
     };
 
     const int fr = lane & 15, fq = lane >> 4;
@@ -1179,8 +1134,7 @@ __device__ __forceinline__ void conv128s_body(GemmArgs g) {
         a_rd[4] = addr(jw == 0 ? rb : 192 + rb - 1);
         a_rd[5] = addr(jw + 3 == g.cW - 1 ? 192 + rb : rb + 1);
     }
-    const int w_lr = wn * 64 + (fr >> 2) * 8 + (fr & 3);                                     // + (ni>>1)*32 rows + (ni&1)*4 rows
-    const int w_rd = w_lr * 128 + ((fq ^ swz_w(w_lr)) << 4);
+    const int w_rd = w_frag_offset(wn * 64, fr, fq);                                         // + (ni>>1)*32 rows + (ni&1)*4 rows
 
     f32x4 acc[4][4];
 #pragma unroll
@@ -1189,6 +1143,8 @@ __device__ __forceinline__ void conv128s_body(GemmArgs g) {
         for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
     vec8 ab[4][2], ax[2], wf[2][2];       // blocks 0..3 (kept for the three taps of a group), the extra block of tap 0 / tap 2
 
+    // the full form computes both 32-column halves NH of the wave's 64 columns, NARROW only half 0 and only in the waves with wn = 0
+    constexpr int NHALVES = NARROW ? 1 : 2;
     auto readA = [&](vec8 (&dst)[2], int a) {
         if (NARROW && wn != 0) return;
 #pragma unroll
@@ -1196,14 +1152,7 @@ __device__ __forceinline__ void conv128s_body(GemmArgs g) {
     };
     auto readB = [&](auto NHc, int wslot) {
         constexpr int NH = decltype(NHc)::value;
-        if constexpr (NARROW) {
-            if (NH != 0 || wn != 0) return;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int nl = 0; nl < 2; ++nl) wf[nl][ks] = *reinterpret_cast<const vec8*>(smem + ((w_rd ^ (ks << 6)) + wslot) + nl * 512);
-            return;
-        }
+        if (NH >= NHALVES || (NARROW && wn != 0)) return;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const char* base = smem + ((w_rd ^ (ks << 6)) + wslot) + NH * 4096;
@@ -1213,25 +1162,14 @@ __device__ __forceinline__ void conv128s_body(GemmArgs g) {
     };
     auto mma = [&](auto DWc, auto NHc) {
         constexpr int DW = decltype(DWc)::value, NH = decltype(NHc)::value;
-        if constexpr (NARROW) {
-            if (NH != 0 || wn != 0) return;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi) {
-                    const int b = mi + DW - 1;
-                    const vec8& a = b < 0 || b > 3 ? ax[ks] : ab[b < 0 ? 0 : b > 3 ? 3 : b][ks];
-#pragma unroll
-                    for (int nl = 0; nl < 2; ++nl) acc[mi][nl] = DT::mfma(wf[nl][ks], a, acc[mi][nl]);     // columns 8 fq + 4 nl + r: 0..7 for fq = 0
-                }
-            return;
-        }
+        if (NH >= NHALVES || (NARROW && wn != 0)) return;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi) {
                 const int b = mi + DW - 1;                 // block holding row j + DW - 1 of output row j = ... + mi
                 const vec8& a = b < 0 || b > 3 ? ax[ks] : ab[b < 0 ? 0 : b > 3 ? 3 : b][ks];
+                // (NARROW: columns 8 fq + 4 nl + r, 0..7 for fq = 0)
 #pragma unroll
                 for (int nl = 0; nl < 2; ++nl) acc[mi][NH * 2 + nl] = DT::mfma(wf[nl][ks], a, acc[mi][NH * 2 + nl]);
             }
@@ -1239,23 +1177,6 @@ __device__ __forceinline__ void conv128s_body(GemmArgs g) {
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>;
-#define HV_S_SYNC_NOVM()                                              \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                \
-    __builtin_amdgcn_sched_barrier(0);                                \
-    __builtin_amdgcn_s_barrier();                                     \
-    __builtin_amdgcn_sched_barrier(0);                                \
-    __builtin_amdgcn_s_setprio(1);
-#define HV_S_SYNC(VM)                                                 \
-    asm volatile("s_waitcnt vmcnt(" #VM ")\n\ts_waitcnt lgkmcnt(0)" ::: "memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                \
-    __builtin_amdgcn_s_barrier();                                     \
-    __builtin_amdgcn_sched_barrier(0);                                \
-    __builtin_amdgcn_s_setprio(1);
-#define HV_S_END()                                                    \
-    __builtin_amdgcn_s_setprio(0);                                    \
-    __builtin_amdgcn_sched_barrier(0);                                \
-    __builtin_amdgcn_s_barrier();                                     \
-    __builtin_amdgcn_sched_barrier(0);
     // KIND 0: steady group; 1: the last but one (no A0 of group g+2); 2: the last (nothing left to issue)
     auto tile_fn = [&](auto DWc, auto KINDc, int grp) {
         constexpr int DW = decltype(DWc)::value, KIND = decltype(KINDc)::value;
@@ -1272,22 +1193,22 @@ __device__ __forceinline__ void conv128s_body(GemmArgs g) {
         if constexpr (DW == 2) readA(ax, a_rd[5] + abuf);
         readB(I0{}, wslot);
         if constexpr (KIND < 2) stageB(t + 3);
-        HV_S_SYNC_NOVM()
+        phase_sync_novm();
         mma(DWc, I0{});
-        HV_S_END()
+        phase_end();
         if constexpr (DW == 0) readA(ab[3], a_rd[3] + abuf);
         readB(I1{}, wslot);
         if constexpr (KIND < 2 && DW == 0) stageA(I1{}, grp + 1);
         if constexpr (KIND == 0 && DW == 2) stageA(I0{}, grp + 2);
         if constexpr (KIND == 0) {
-            if constexpr (DW == 2) { HV_S_SYNC(6) } else { HV_S_SYNC(8) }
+            if constexpr (DW == 2) phase_sync<6>(); else phase_sync<8>();
         } else if constexpr (KIND == 1) {
-            if constexpr (DW == 2) { HV_S_SYNC(4) } else { HV_S_SYNC(8) }
+            if constexpr (DW == 2) phase_sync<4>(); else phase_sync<8>();
         } else {
-            if constexpr (DW == 0) { HV_S_SYNC(2) } else { HV_S_SYNC(0) }
+            if constexpr (DW == 0) phase_sync<2>(); else phase_sync<0>();
         }
         mma(DWc, I1{});
-        HV_S_END()
+        phase_end();
     };
 
     const int ngrp = g.K / (3 * BK);      // >= 2 (host-side dispatch)
@@ -1311,47 +1232,12 @@ __device__ __forceinline__ void conv128s_body(GemmArgs g) {
     tile_fn(I1{}, I2{}, grp);
     tile_fn(I2{}, I2{}, grp);
     if (wm < 2) __builtin_amdgcn_s_barrier();
-#undef HV_S_SYNC
-#undef HV_S_SYNC_NOVM
-#undef HV_S_END
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) asm volatile("" : : "v"(acc[mi][ni]));
-    GemmArgs ge = g;
-    asm volatile("s_waitcnt vmcnt(0)" : "+s"(ge.bias), "+s"(ge.gate), "+s"(ge.res), "+s"(ge.a_scale), "+s"(ge.w_scale), "+s"(ge.out0),
-                 "+s"(ge.out1), "+s"(ge.out_f32), "+s"(ge.gn_partial) : : "memory");
-    __builtin_amdgcn_sched_barrier(0);
+    const GemmArgs ge = epilogue_handoff(g, acc);
     gemm_epilogue<DT, 4, 4, 1>(ge, acc, m0 + wm * 64 + 4 * fr, wn * 64, fq, IdRowMap(), lin * 4 + wm);
 }
 
 __global__ __launch_bounds__(512, 2) void conv128s_kernel(GemmArgs g) { conv128s_body<false>(g); }
 __global__ __launch_bounds__(512, 2) void conv128s_narrow_kernel(GemmArgs g) { conv128s_body<true>(g); }
-
-int launch_conv128s(GemmArgs& g, hipStream_t stream) {
-    static HvPerDeviceOnce once;
-    if (hv_set_max_lds(once, (const void*)conv128s_kernel, CS_LDS) != HV_OK) return HV_ERR_LAUNCH;
-    g.tiles_m = (g.M + BM - 1) / BM;
-    g.tiles_n = 1;
-    if (g.N <= 32) {
-        static HvPerDeviceOnce once_n;
-        if (hv_set_max_lds(once_n, (const void*)conv128s_narrow_kernel, CS_LDS) != HV_OK) return HV_ERR_LAUNCH;
-        conv128s_narrow_kernel<<<dim3((unsigned)g.tiles_m), dim3(512), CS_LDS, stream>>>(g);
-        return hv_check_launch();
-    }
-    conv128s_kernel<<<dim3((unsigned)g.tiles_m), dim3(512), CS_LDS, stream>>>(g);
-    return hv_check_launch();
-}
-
-template <typename DT, bool CONV, int BN>
-int launch_bn(GemmArgs& g, hipStream_t stream) {
-    static HvPerDeviceOnce once;     // one per template instantiation
-    if (hv_set_max_lds(once, (const void*)gemm_kernel<DT, CONV, BN>, lds_bytes<BN>()) != HV_OK) return HV_ERR_LAUNCH;
-    g.tiles_m = (g.M + BM - 1) / BM;
-    g.tiles_n = (g.N + BN - 1) / BN;
-    gemm_kernel<DT, CONV, BN><<<dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(512), lds_bytes<BN>(), stream>>>(g);
-    return hv_check_launch();
-}
 
 template <typename DT, bool CONV>
 int launch(GemmArgs& g, hipStream_t stream) {
@@ -1361,28 +1247,28 @@ int launch(GemmArgs& g, hipStream_t stream) {
         if constexpr (CONV && std::is_same<DT, F16T>::value) {
             // the pipelined 256 x 128 conv tile: cin a power of two >= 128 (a tap spans >= 2 K-tiles), 27*cin/64 K-tiles (a multiple of 3),
             // coordinates within the packing
-            const bool pow2 = (g.cin & (g.cin - 1)) == 0;
-            if (pow2 && g.cin >= 128 && (g.K / BK) % 3 == 0 && g.K / BK >= 6 && g.cT * g.mt < 256 && g.bH <= 4096 && g.bW <= 4096 &&
+            if (conv_fits_packing(g.cin, g.cT * g.mt, g.bH, g.bW) && g.cin >= 128 && (g.K / BK) % 3 == 0 && g.K / BK >= 6 &&
                 !hv_gemm_force_2stage()) {
                 // unit stride along W, clamp extent = output width, output rows of a tile = whole W rows: the W-shift-reuse kernel
-                static const bool no_shift = getenv("HV_CONV_NOSHIFT") != nullptr;
-                if (g.mw == 1 && g.bW == g.cW && g.cW <= 256 && 256 % g.cW == 0 && g.cW % 4 == 0 && !no_shift) return launch_conv128s(g, stream);
-                return launch_conv128(g, stream);
+                // (narrow form for Cout <= 32)
+                if (g.mw == 1 && g.bW == g.cW && g.cW <= 256 && 256 % g.cW == 0 && g.cW % 4 == 0)
+                    return g.N <= 32 ? launch_tiles<conv128s_narrow_kernel, CS_LDS, 128>(g, stream)
+                                     : launch_tiles<conv128s_kernel, CS_LDS, 128>(g, stream);
+                return launch_tiles<conv128_kernel, C128_LDS, 128>(g, stream);
             }
         }
-        return launch_bn<DT, CONV, 128>(g, stream);
+        return launch_tiles<gemm_kernel<DT, CONV, 128>, lds_bytes<128>(), 128>(g, stream);
     }
     if constexpr (!CONV) {
-        if (g.K >= 3 * BK && !hv_gemm_force_2stage()) return launch_gemm8<DT>(g, stream);     // pipelined main loop
+        if (g.K >= 3 * BK && !hv_gemm_force_2stage()) return launch_tiles<gemm8_kernel<DT>, LDS8_BYTES, 256>(g, stream);     // pipelined main loop
     } else if constexpr (std::is_same<DT, F16T>::value) {
         // conv: the pipelined loop re-forms its gather offsets per tap from packed coordinates (no room for the 36 separable offsets
         // next to the deeper pipeline's fragments), which pays when a tap spans >= 4 K-tiles: cin a power of two >= 256 - the 256-
-        // and 512-channel layers that make up the BN = 256 convs of the decoder; coordinates must fit the packing (t < 256, h, w < 4096)
-        const bool pow2 = (g.cin & (g.cin - 1)) == 0;
-        if (pow2 && g.cin >= 256 && g.cT * g.mt < 256 && g.bH <= 4096 && g.bW <= 4096 && !hv_gemm_force_2stage())
-            return launch_gemm8<DT, true>(g, stream);
+        // and 512-channel layers that make up the BN = 256 convs of the decoder; coordinates must fit the packing
+        if (conv_fits_packing(g.cin, g.cT * g.mt, g.bH, g.bW) && g.cin >= 256 && !hv_gemm_force_2stage())
+            return launch_tiles<gemm8_kernel<DT, true>, LDS8_BYTES, 256>(g, stream);
     }
-    return launch_bn<DT, CONV, 256>(g, stream);
+    return launch_tiles<gemm_kernel<DT, CONV, 256>, lds_bytes<256>(), 256>(g, stream);
 }
 
 int fill_common(GemmArgs& g, const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, int M, int N, int K,
@@ -1400,6 +1286,21 @@ int fill_common(GemmArgs& g, const void* A, int64_t lda, const void* W, int64_t 
     g.out0 = (uint16_t*)out0; g.ld0 = ld0; g.act0 = act0; g.n_split = n_split;
     g.out1 = (uint16_t*)out1; g.ld1 = ld1; g.act1 = act1;
     g.gate = (const uint16_t*)gate; g.res = (const uint16_t*)res; g.ld_res = ld_res;
+    return HV_OK;
+}
+
+// Conv entry points: the implicit GEMM of an `ntap`-tap conv (weights [Cout][ntap][Cin]) from the channels-last source grid `s` to
+// the output grid `o`, and its gather geometry: stride per axis, nearest upsample up_t / up_hw; indices are clamped to the source grid
+// as the upsample shows it (extent s << up_hw).  M = the source grid in the sub-pixel form (rows are class-local), else the output grid.
+struct Grid { int t, h, w; };
+int fill_conv(GemmArgs& g, const void* x, int64_t ldx, const void* w, int ntap, const void* bias, void* out, int64_t ldo, const void* res,
+              int64_t ld_res, int M, Grid o, Grid s, int Cin, int Cout, int up_t, int up_hw, Grid stride) {
+    int rc = fill_common(g, x, ldx, w, (int64_t)ntap * Cin, bias, M, Cout, ntap * Cin, out, ldo, 0, 0, nullptr, 0, 0, nullptr, res, ld_res);
+    if (rc != HV_OK) return rc;
+    g.cT = o.t; g.cH = o.h; g.cW = o.w; g.cin = Cin; g.up_t = up_t; g.up_hw = up_hw;
+    g.sT = s.t; g.sH = s.h; g.sW = s.w;
+    g.mt = stride.t; g.mh = stride.h; g.mw = stride.w; g.bH = s.h << up_hw; g.bW = s.w << up_hw;
+    if ((int64_t)s.t * s.h * s.w * ldx * 2 >= ((int64_t)1 << 32)) return HV_ERR_ARG;   // the gather uses 32-bit byte offsets (4 GiB source)
     return HV_OK;
 }
 
@@ -1426,7 +1327,7 @@ extern "C" int hv_gemm_fp8(const void* A_q, int64_t lda, const float* a_row_scal
     g.a_scale = a_row_scale;
     g.w_scale = (const uint16_t*)w_scale_bf16;
     if (M == 0) return HV_OK;
-    return launch_gemm8<FP8T>(g, stream);
+    return launch_tiles<gemm8_kernel<FP8T>, LDS8_BYTES, 256>(g, stream);
 }
 
 extern "C" int hv_gemm_f16(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, int M, int N, int K,
@@ -1451,13 +1352,9 @@ extern "C" int hv_conv3d_causal_f16(const void* x, int64_t ldx, const void* w_ta
     if ((int64_t)T * H * W > 0x7fffffff) return HV_ERR_ARG;
     if ((up_t && !(T & 1)) || (up_hw && ((H & 1) || (W & 1)))) return HV_ERR_ARG;
     GemmArgs g;
-    int rc = fill_common(g, x, ldx, w_taps, (int64_t)27 * Cin, bias, T * H * W, Cout, 27 * Cin, out, ldo, 0, 0, nullptr, 0, 0,
-                         nullptr, res, ld_res);
+    int rc = fill_conv(g, x, ldx, w_taps, 27, bias, out, ldo, res, ld_res, T * H * W, {T, H, W},
+                       {up_t ? (T + 1) / 2 : T, H >> up_hw, W >> up_hw}, Cin, Cout, up_t, up_hw, {1, 1, 1});
     if (rc != HV_OK) return rc;
-    g.cT = T; g.cH = H; g.cW = W; g.cin = Cin; g.up_t = up_t; g.up_hw = up_hw;
-    g.sT = up_t ? (T + 1) / 2 : T; g.sH = H >> up_hw; g.sW = W >> up_hw;
-    g.mt = g.mh = g.mw = 1; g.bH = H; g.bW = W;
-    if ((int64_t)g.sT * g.sH * g.sW * ldx * 2 >= ((int64_t)1 << 32)) return HV_ERR_ARG;   // the gather uses 32-bit byte offsets (4 GiB source)
     if (gn_partial) {
         if (gn_partial_floats < hv_gn_partial_rows(g.M) * (int64_t)Cout * 2) return HV_ERR_ARG;
         g.gn_partial = gn_partial;
@@ -1484,16 +1381,14 @@ extern "C" int hv_conv3d_upsampled_subpixel_f16(const void* x, int64_t ldx, cons
     // The caller builds weights and table (vae_ops.subpixel_weights): which taps are summed, and whether the rounding residue of a
     // sum is carried as an extra "lo" tap, is its choice - this kernel only needs offsets.
     if (!x || !w_sub || !tap_table || !out || sT <= 0 || sH <= 0 || sW <= 0 || ntap < 1 || ntap > 27 || (up_t & ~1)) return HV_ERR_ARG;
-    if (Cin < 256 || (Cin & (Cin - 1)) || Cout <= 128 || (Cout & 7)) return HV_ERR_ARG;       // the pipelined conv tile's shapes
+    // the pipelined conv tile's shapes; the packed frame coordinate goes up to sT (k = kt + 1 for odd output frames)
+    if (Cin < 256 || !conv_fits_packing(Cin, sT + 1, sH, sW) || Cout <= 128 || (Cout & 7)) return HV_ERR_ARG;
     const int T2 = up_t ? 2 * sT - 1 : sT, H2 = 2 * sH, W2 = 2 * sW, ncls = up_t ? 8 : 4;
-    if ((int64_t)T2 * H2 * W2 > 0x7fffffff || sT + 1 >= 256 || sH > 4096 || sW > 4096) return HV_ERR_ARG;
+    if ((int64_t)T2 * H2 * W2 > 0x7fffffff) return HV_ERR_ARG;
     GemmArgs g;
-    int rc = fill_common(g, x, ldx, w_sub, (int64_t)ntap * Cin, bias, sT * sH * sW, Cout, ntap * Cin, out, ldo, 0, 0, nullptr, 0, 0,
-                         nullptr, nullptr, 0);
+    int rc = fill_conv(g, x, ldx, w_sub, ntap, bias, out, ldo, nullptr, 0, sT * sH * sW, {T2, H2, W2}, {sT, sH, sW}, Cin, Cout, up_t, 1,
+                       {1, 1, 1});
     if (rc != HV_OK) return rc;
-    g.cT = T2; g.cH = H2; g.cW = W2; g.cin = Cin; g.up_t = up_t; g.up_hw = 1;
-    g.sT = sT; g.sH = sH; g.sW = sW; g.mt = g.mh = g.mw = 1; g.bH = H2; g.bW = W2;
-    if ((int64_t)sT * sH * sW * ldx * 2 >= ((int64_t)1 << 32)) return HV_ERR_ARG;
     g.sp_ntap = ntap; g.sp_tab = (const uint32_t*)tap_table;
     int tiles = 0;
     for (int c = 0; c < 8; ++c) {
@@ -1510,7 +1405,7 @@ extern "C" int hv_conv3d_upsampled_subpixel_f16(const void* x, int64_t ldx, cons
         if (gn_partial_floats < (int64_t)tiles * 4 * Cout * 2) return HV_ERR_ARG;
         g.gn_partial = gn_partial;
     }
-    return launch_gemm8_subpixel(g, stream);
+    return launch_tiles<gemm8_kernel<F16T, true, true>, LDS8_BYTES, 256>(g, stream);
 }
 
 extern "C" int hv_conv3d_causal_strided_f16(const void* x, int64_t ldx, const void* w_taps, const void* bias, void* out, int64_t ldo,
@@ -1524,12 +1419,8 @@ extern "C" int hv_conv3d_causal_strided_f16(const void* x, int64_t ldx, const vo
     const int T = (sT - 1) / stride_t + 1, H = (sH - 1) / stride_h + 1, W = (sW - 1) / stride_w + 1;
     if ((int64_t)sT * sH * sW > 0x7fffffff) return HV_ERR_ARG;
     GemmArgs g;
-    int rc = fill_common(g, x, ldx, w_taps, (int64_t)27 * Cin, bias, T * H * W, Cout, 27 * Cin, out, ldo, 0, 0, nullptr, 0, 0,
-                         nullptr, nullptr, 0);
+    int rc = fill_conv(g, x, ldx, w_taps, 27, bias, out, ldo, nullptr, 0, T * H * W, {T, H, W}, {sT, sH, sW}, Cin, Cout, 0, 0,
+                       {stride_t, stride_h, stride_w});
     if (rc != HV_OK) return rc;
-    g.cT = T; g.cH = H; g.cW = W; g.cin = Cin; g.up_t = 0; g.up_hw = 0;
-    g.sT = sT; g.sH = sH; g.sW = sW;
-    g.mt = stride_t; g.mh = stride_h; g.mw = stride_w; g.bH = sH; g.bW = sW;
-    if ((int64_t)sT * sH * sW * ldx * 2 >= ((int64_t)1 << 32)) return HV_ERR_ARG;
     return launch<F16T, true>(g, stream);
 }

@@ -1,7 +1,7 @@
 """GPU: every GEMM / conv main loop at its tile and dispatch edges, against an fp64 reference with a per-element error bound
 (tests/error_bounds.py), with every operand embedded in NaN-poisoned memory and every output in a sentinel-filled buffer.
 
-Path table - a Python mirror of the dispatch in csrc/hv_gemm.hip (launch, launch_gemm8, hv_gemm_fp8, hv_conv3d_causal_f16,
+Path table - a Python mirror of the dispatch in csrc/hv_gemm.hip (launch, launch_tiles, hv_gemm_fp8, hv_conv3d_causal_f16,
 hv_conv3d_upsampled_subpixel_f16); test_path_table_matches_launched_kernels confirms it with the profiler:
 
     B1 gemm_kernel<BF16T,false,128>   hv_gemm_bf16, N <= 128          F1-F3: the same three for hv_gemm_f16
@@ -70,11 +70,11 @@ def _record(path, r):
 # ------------------------------------------------------------------------------------------------------ the dispatcher's mirror
 def gemm_path(kind, N, K):
     if kind == "fp8":
-        return "Q"                                   # hv_gemm_fp8 -> launch_gemm8<FP8T> for every N
+        return "Q"                                   # hv_gemm_fp8 -> gemm8_kernel<FP8T> for every N
     p = "B" if kind == "bf16" else "F"
     if N <= 128:
-        return p + "1"                               # launch(): N <= 128 -> launch_bn<.., 128>
-    return p + ("3" if K >= 3 * 64 else "2")       # K >= 3 BK -> launch_gemm8 (HV_GEMM_2STAGE unset)
+        return p + "1"                               # launch(): N <= 128 -> gemm_kernel<.., 128>
+    return p + ("3" if K >= 3 * 64 else "2")       # K >= 3 BK -> gemm8_kernel (HV_GEMM_2STAGE unset)
 
 
 def conv_path(T, H, W, cin, cout):
