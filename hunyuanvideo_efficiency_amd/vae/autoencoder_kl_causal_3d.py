@@ -11,7 +11,11 @@ Execution model: activations are fp16 CHANNELS-LAST ([T*H*W voxels, C]) so that
   * GroupNorm is a per-channel affine after a two-level reduction (K16),
   * the mid-block attention needs no rearrange: "b (f h w) c" IS this layout (K18); the frame-causal mask is realised by
     giving frame f's queries exactly the keys of frames <= f (no [L,L] mask tensor - the reference builds a 606 MB one),
-  * tiles are decoded one after another and blended in the reference's exact order (K19) by strided kernels.
+  * tiling (K19): vae/tiling.py holds the reference's tile geometry once (TilePlan: decode = latent source, sample output; encode =
+    the two swapped).  `_assemble_temporal` / `_assemble_spatial` walk the plan for both halves, take each tile from a tile
+    source (`_decode_tile` / `_encode_tile`, or for decode `_predecoded`: tiles decoded ahead on two streams or sharded over
+    ranks, enumerated by the same plan through `_tile_views`) and blend / crop / copy in the reference's exact order with
+    strided kernels, in place.
 """
 from __future__ import annotations
 
@@ -24,6 +28,7 @@ import torch.nn as nn
 
 from .. import synthetic as syn
 from .. import vae_ops as V
+from .tiling import AxisPlan, TilePlan
 
 F16 = torch.float16
 
@@ -141,6 +146,7 @@ class AutoencoderKLCausal3D(nn.Module):
         # 3.50 / 3.48 s on one stream, 3.20 / 3.20 s on two, 3.69 s on three (tools/bench_vae_streams.py; bit-identical outputs)
         self.decode_streams = 2
         self._streams = None
+        self._tp_enabled, self._tp_group, self._tp_gather = False, None, "all"          # enable_tile_parallel()
 
     # ------------------------------------------------------------------ reference surface
     @property
@@ -228,11 +234,8 @@ class AutoencoderKLCausal3D(nn.Module):
             lin(a + "to_out.0", sd[a + "to_out.0.weight"], sd[a + "to_out.0.bias"])
         # UpsampleCausal3D convs of the decoder in sub-pixel form (vae_ops.subpixel_weights): the 256- and 512-channel upsamplers
         mode = V.subpixel_mode()
-        boc = self.config.block_out_channels
-        nb = len(boc)
-        for i in range(nb):
+        for i, (sp, tm) in enumerate(self._resample_schedule()):
             name = f"decoder.up_blocks.{i}.upsamplers.0.conv.conv"
-            sp, tm = i < 3, (i >= nb - 1 - 2) and (i != nb - 1)
             if mode == "off" or name not in P or not sp:
                 continue
             _, bp, cip, cop = P[name]
@@ -333,11 +336,11 @@ class AutoencoderKLCausal3D(nn.Module):
         h = self._conv(P, pre + "conv_in.conv", x1, T, H, W)
         dec_ops = (self._t_ops or {}).get("decoder", {})
         h, T = self._mid_block(P, pre + "mid_block.", h, T, H, W, dec_ops.get("mid_block"))
-        boc = self.config.block_out_channels
-        nb = len(boc)
+        schedule = self._resample_schedule()
+        nb = len(schedule)
         n_res = self.config.layers_per_block + 1
         st = None          # GroupNorm statistics of h, when the conv that produced h took them
-        for i in range(nb):
+        for i, (sp, tm) in enumerate(schedule):
             bc = self._block_cfg(dec_ops.get("up_blocks"), i) or {}
             eib = bc.get("enable_t_interp_before_block", [False] * n_res)
             eia = bc.get("enable_t_interp_after_block", [False] * n_res)
@@ -346,8 +349,6 @@ class AutoencoderKLCausal3D(nn.Module):
             sc = int(bc.get("interp_t_scale_factor", 2))
             if (any(eib) or any(eia)) and bc.get("interp_mode", "nearest") != "nearest":
                 raise NotImplementedError("t_ops interp_mode: only 'nearest' has a kernel (the fork's config default)")
-            sp = i < 3
-            tm = (i >= nb - 1 - 2) and (i != nb - 1)
             for j in range(n_res):
                 if eib[j]:
                     h, T = V.temporal_nearest_up(h, T, H * W, sc)      # unet_causal_3d_blocks.py:884-895
@@ -381,7 +382,13 @@ class AutoencoderKLCausal3D(nn.Module):
         out = self._conv(P, pre + "conv_out.conv", h, T, H, W)
         return out, T, H, W
 
-    # ------------------------------------------------------------------ shared by both halves: mid block, t_ops bookkeeping
+    # ------------------------------------------------------------------ shared by both halves: block schedule, mid block, t_ops
+    def _resample_schedule(self) -> List[Tuple[bool, bool]]:
+        """Per block, in the half's own order: (resamples H and W, resamples T) - vae/vae.py:65-75,187-195 for the 884 ratios:
+        log2(8) = 3 spatial layers from the front, log2(4) = 2 temporal ones before the last block."""
+        nb = len(self.config.block_out_channels)
+        return [(i < 3, (i >= nb - 1 - 2) and (i != nb - 1)) for i in range(nb)]
+
     @staticmethod
     def _block_cfg(cfgs, i):
         for c in cfgs or []:
@@ -446,9 +453,8 @@ class AutoencoderKLCausal3D(nn.Module):
         pre = "encoder."
         enc_ops = (self._t_ops or {}).get("encoder", {})
         h = self._conv(P, pre + "conv_in.conv", x, T, H, W)
-        boc = self.config.block_out_channels
-        nb, n_res = len(boc), self.config.layers_per_block
-        for i in range(nb):
+        n_res = self.config.layers_per_block
+        for i, (sp, tm) in enumerate(self._resample_schedule()):
             bc = self._block_cfg(enc_ops.get("down_blocks"), i)
             conf = self._pool_conf(bc, n_res, "DownEncoderBlockCausal3D")
             for j in range(n_res):
@@ -458,8 +464,6 @@ class AutoencoderKLCausal3D(nn.Module):
                 h = self._resnet(P, f"{pre}down_blocks.{i}.resnets.{j}.", h, T, H, W)
                 if after:
                     h, T = V.temporal_avg_pool(h, T, H * W, k, s)
-            sp = i < 3
-            tm = (i >= nb - 1 - 2) and (i != nb - 1)
             if sp or tm:
                 stride = ((2 if tm else 1), (2 if sp else 1), (2 if sp else 1))
                 if bc and "downsample_stride" in bc:
@@ -472,76 +476,6 @@ class AutoencoderKLCausal3D(nn.Module):
         wq, bq = P["quant_conv"]
         moments = V.gemm_f16(self._pad_channels(h, wq.shape[1]), wq, bq, k=wq.shape[1])
         return moments, T, H, W
-
-    def _plain_encode(self, x4):
-        buf, T, H, W = self._encode_tile(x4)
-        c = 2 * self.config.latent_channels
-        out = torch.empty(c, T, H, W, dtype=F16, device=buf.device)
-        V.copy4d_(self._cl_view(buf, T, H, W, c), out)
-        return out
-
-    def _spatial_tiled_encode(self, x4):
-        """autoencoder_kl_causal_3d.py:362-420 on a [3,T,H,W] view; returns planar fp16 moments [2*latent,T',H',W']."""
-        ov = int(self.tile_sample_min_size * (1 - self.tile_overlap_factor))
-        ext = int(self.tile_latent_min_size * self.tile_overlap_factor)
-        lim = self.tile_latent_min_size - ext
-        c = 2 * self.config.latent_channels
-        rows = []
-        for i in range(0, x4.shape[-2], ov):
-            row = []
-            for j in range(0, x4.shape[-1], ov):
-                buf, T, H, W = self._encode_tile(x4[:, :, i:i + self.tile_sample_min_size, j:j + self.tile_sample_min_size])
-                row.append(self._cl_view(buf, T, H, W, c))
-            rows.append(row)
-        heights = [min(r[0].shape[2], lim) for r in rows]
-        widths = [min(t.shape[3], lim) for t in rows[0]]
-        out = torch.empty(c, rows[0][0].shape[1], sum(heights), sum(widths), dtype=F16, device=x4.device)
-        y0 = 0
-        for i, row in enumerate(rows):
-            x0 = 0
-            for j, tile in enumerate(row):
-                if i > 0:
-                    a = rows[i - 1][j]
-                    e = min(a.shape[2], tile.shape[2], ext)
-                    V.blend_(a[:, :, a.shape[2] - e:, :], tile[:, :, :e, :], 2, e)
-                if j > 0:
-                    a = row[j - 1]
-                    e = min(a.shape[3], tile.shape[3], ext)
-                    V.blend_(a[:, :, :, a.shape[3] - e:], tile[:, :, :, :e], 3, e)
-                V.copy4d_(tile[:, :, :heights[i], :widths[j]], out[:, :, y0:y0 + heights[i], x0:x0 + widths[j]])
-                x0 += widths[j]
-            y0 += heights[i]
-        return out
-
-    def _temporal_tiled_encode(self, x4):
-        """autoencoder_kl_causal_3d.py:470-510."""
-        T = x4.shape[1]
-        ov = int(self.tile_sample_min_tsize * (1 - self.tile_overlap_factor))
-        ext = int(self.tile_latent_min_tsize * self.tile_overlap_factor)
-        lim = self.tile_latent_min_tsize - ext
-        row = []
-        for i in range(0, T, ov):
-            tile = x4[:, i:i + self.tile_sample_min_tsize + 1]
-            if self.use_spatial_tiling and (tile.shape[-1] > self.tile_sample_min_size or tile.shape[-2] > self.tile_sample_min_size):
-                enc = self._spatial_tiled_encode(tile)
-            else:
-                enc = self._plain_encode(tile)
-            if i > 0:
-                enc = enc[:, 1:]
-            row.append(enc)
-        lens = [min(t.shape[1], lim + (1 if i == 0 else 0)) for i, t in enumerate(row)]
-        out = torch.empty(row[0].shape[0], sum(lens), row[0].shape[2], row[0].shape[3], dtype=F16, device=x4.device)
-        t0 = 0
-        for i, tile in enumerate(row):
-            if i > 0:
-                a = row[i - 1]
-                e = min(a.shape[1], tile.shape[1], ext)
-                if e > 0:
-                    V.blend_(a[:, a.shape[1] - e:], tile[:, :e], 1, e)
-            if lens[i] > 0:
-                V.copy4d_(tile[:, :lens[i]], out[:, t0:t0 + lens[i]])
-            t0 += lens[i]
-        return out
 
     @torch.no_grad()
     def encode(self, x: torch.Tensor, return_dict: bool = True):
@@ -557,14 +491,9 @@ class AutoencoderKLCausal3D(nn.Module):
         return SimpleNamespace(latent_dist=posterior, tiles_ci=None)
 
     def _encode_moments(self, x):
-        x4 = x[0]
         if self._t_ops is not None and (self.use_temporal_tiling or self.use_spatial_tiling):
             raise NotImplementedError("t_ops change the compression ratios the tile/blend geometry assumes; the fork runs them untiled")
-        if self.use_temporal_tiling and x4.shape[1] > self.tile_sample_min_tsize:
-            return self._temporal_tiled_encode(x4)[None]
-        if self.use_spatial_tiling and (x4.shape[-1] > self.tile_sample_min_size or x4.shape[-2] > self.tile_sample_min_size):
-            return self._spatial_tiled_encode(x4)[None]
-        return self._plain_encode(x4)[None]
+        return self._assemble_temporal(self._tile_plan(decode=False), x[0], self._encode_tile, 2 * self.config.latent_channels)[None]
 
     @torch.no_grad()
     def forward(self, sample: torch.Tensor, sample_posterior: bool = False, return_dict: bool = True,
@@ -577,22 +506,84 @@ class AutoencoderKLCausal3D(nn.Module):
             return (dec, posterior) if return_posterior else (dec,)
         return SimpleNamespace(sample=dec, posterior=posterior) if return_posterior else SimpleNamespace(sample=dec)
 
-    # ------------------------------------------------------------------ tiling (reference loop order)
+    # ------------------------------------------------------------------ tiling (reference loop order), both halves
+    def _tile_plan(self, decode: bool) -> TilePlan:
+        """autoencoder_kl_causal_3d.py:117-132 as a plan: decode tiles the latent and blends samples, encode the other way round."""
+        lat, smp = (self.tile_latent_min_tsize, self.tile_latent_min_size), (self.tile_sample_min_tsize, self.tile_sample_min_size)
+        (src_t, src_s), (out_t, out_s) = (lat, smp) if decode else (smp, lat)
+        return TilePlan(AxisPlan.of(src_t, out_t, self.tile_overlap_factor) if self.use_temporal_tiling else None,
+                        AxisPlan.of(src_s, out_s, self.tile_overlap_factor) if self.use_spatial_tiling else None)
+
     @staticmethod
-    def _cl_view(buf, T, H, W, c=3):
-        """[C,T,H,W] strided view of a channels-last [T*H*W, 8] buffer."""
+    def _cl_view(buf, T, H, W, c):
+        """[C,T,H,W] strided view of a channels-last [T*H*W, >= c] buffer."""
         return buf.as_strided((c, T, H, W), (1, H * W * buf.stride(0), W * buf.stride(0), buf.stride(0)), buf.storage_offset())
 
-    def _plain_decode(self, z4):
-        buf, T, H, W = self._take_tile(z4)
-        out = torch.empty(3, T, H, W, dtype=F16, device=buf.device)
-        V.copy4d_(self._cl_view(buf, T, H, W), out)
+    def _assemble_spatial(self, plan: TilePlan, x4, tile, c: int):
+        """autoencoder_kl_causal_3d.py:362-469 on a [C,T,H,W] view (one tile where it is not tiled in space): every tile from
+        `tile(view) -> (channels-last buffer, T', H', W')` first, then row by row blend-above, blend-left (in place: a tile's
+        blends read the already blended neighbours), crop, copy.  Returns planar fp16 [c,T',H',W']."""
+        rows = plan.spatial_rows(x4)
+        if rows is None:
+            buf, T, H, W = tile(x4)
+            out = torch.empty(c, T, H, W, dtype=F16, device=buf.device)
+            V.copy4d_(self._cl_view(buf, T, H, W, c), out)
+            return out
+        ext, lim = plan.spatial.extent, plan.spatial.limit
+        rows = [[self._cl_view(*tile(v), c) for v in row] for row in rows]
+        heights = [min(r[0].shape[2], lim) for r in rows]
+        widths = [min(t.shape[3], lim) for t in rows[0]]
+        out = torch.empty(c, rows[0][0].shape[1], sum(heights), sum(widths), dtype=F16, device=x4.device)
+        y0 = 0
+        for i, row in enumerate(rows):
+            x0 = 0
+            for j, t in enumerate(row):
+                if i > 0:
+                    a = rows[i - 1][j]
+                    e = min(a.shape[2], t.shape[2], ext)
+                    V.blend_(a[:, :, a.shape[2] - e:, :], t[:, :, :e, :], 2, e)
+                if j > 0:
+                    a = row[j - 1]
+                    e = min(a.shape[3], t.shape[3], ext)
+                    V.blend_(a[:, :, :, a.shape[3] - e:], t[:, :, :, :e], 3, e)
+                V.copy4d_(t[:, :, :heights[i], :widths[j]], out[:, :, y0:y0 + heights[i], x0:x0 + widths[j]])
+                x0 += widths[j]
+            y0 += heights[i]
         return out
+
+    def _assemble_temporal(self, plan: TilePlan, x4, tile, c: int):
+        """autoencoder_kl_causal_3d.py:470-541 (the spatial assembly alone where x4 is not tiled in time): every temporal tile
+        assembled in space, then blend with the previous one and copy.  An overlap or a trailing tile can be empty (one latent
+        frame, whose only output frame is dropped): V.blend_ and V.copy4d_ return early on empty views."""
+        groups = plan.temporal_tiles(x4)
+        if groups is None:
+            return self._assemble_spatial(plan, x4, tile, c)
+        row, lens = [], []
+        for i, g in enumerate(groups):
+            first, most = plan.temporal_frames(i)
+            row.append(self._assemble_spatial(plan, g, tile, c)[:, first:])
+            lens.append(min(row[i].shape[1], most))
+        out = torch.empty(c, sum(lens), row[0].shape[2], row[0].shape[3], dtype=F16, device=x4.device)
+        t0 = 0
+        for i, t in enumerate(row):
+            if i > 0:
+                a = row[i - 1]
+                e = min(a.shape[1], t.shape[1], plan.temporal.extent)
+                V.blend_(a[:, a.shape[1] - e:], t[:, :e], 1, e)
+            V.copy4d_(t[:, :lens[i]], out[:, t0:t0 + lens[i]])
+            t0 += lens[i]
+        return out
+
+    def _decoded_size(self, z_view) -> Tuple[int, int, int]:
+        """(T', H', W') of the video a latent view [C,T,H,W] decodes to."""
+        s = self.config.spatial_compression_ratio
+        return (z_view.shape[1] - 1) * self.time_compression_ratio + 1, z_view.shape[2] * s, z_view.shape[3] * s
 
     # ------------------------------------------------------------------ tile parallelism (SURVEY.md 8e; new vs the reference,
     # which decodes every tile on every rank).  Tiles are independent until the blend: each rank decodes its share, the decoded
     # tiles are all-gathered (one RCCL all-gather per round of P tiles, in flight while the next round decodes), and every rank
-    # runs the reference's blend loops over the complete set, so decode() still returns the whole video on every rank.
+    # assembles the complete set (_predecoded is then the assemblers' tile source), so decode() still returns the whole video on
+    # every rank.
     def enable_tile_parallel(self, group=None, enable: bool = True, gather: Optional[str] = None):
         """gather (or HV_VAE_TILE_GATHER): "all" (default) - every decoded tile is all-gathered, every rank blends and returns the
         whole video (what the reference's callers get, since it decodes everything everywhere); "rank0" - tiles are gathered to
@@ -607,29 +598,9 @@ class AutoencoderKLCausal3D(nn.Module):
             raise ValueError(f"tile gather mode must be 'all' or 'rank0', got {g!r}")
         self._tp_gather = g
 
-    def _spatial_views(self, z4):
-        ov = int(self.tile_latent_min_size * (1 - self.tile_overlap_factor))
-        for i in range(0, z4.shape[-2], ov):
-            for j in range(0, z4.shape[-1], ov):
-                yield z4[:, :, i:i + self.tile_latent_min_size, j:j + self.tile_latent_min_size]
-
-    def _needs_spatial(self, z4):
-        return self.use_spatial_tiling and (z4.shape[-1] > self.tile_latent_min_size or z4.shape[-2] > self.tile_latent_min_size)
-
     def _tile_views(self, z4):
-        """Latent views of every tile, in exactly the order the decode loops below consume them."""
-        if self.use_temporal_tiling and z4.shape[1] > self.tile_latent_min_tsize:
-            ov = int(self.tile_latent_min_tsize * (1 - self.tile_overlap_factor))
-            for i in range(0, z4.shape[1], ov):
-                tile = z4[:, i:i + self.tile_latent_min_tsize + 1]
-                if self._needs_spatial(tile):
-                    yield from self._spatial_views(tile)
-                else:
-                    yield tile
-        elif self._needs_spatial(z4):
-            yield from self._spatial_views(z4)
-        else:
-            yield z4
+        """Latent views of every tile of a decode, from the plan the assemblers walk: in the order they take tiles."""
+        return self._tile_plan(decode=True).views(z4)
 
     @staticmethod
     def _assign_tiles(costs: List[int], world: int) -> List[List[int]]:
@@ -647,12 +618,11 @@ class AutoencoderKLCausal3D(nn.Module):
         dist = _dist()
         world, rank = dist.get_world_size(group), dist.get_rank(group)
         views = list(self._tile_views(z4))
-        tc = self.time_compression_ratio
-        dims = [((v.shape[1] - 1) * tc + 1, v.shape[2] * 8, v.shape[3] * 8) for v in views]     # decoded T', H', W'
+        dims = [self._decoded_size(v) for v in views]
         plan = self._assign_tiles([v.shape[1] * v.shape[2] * v.shape[3] for v in views], world)
         rounds = max(len(p) for p in plan)
         max_rows = max(t * h * w for t, h, w in dims)
-        to_root = getattr(self, "_tp_gather", "all") == "rank0"
+        to_root = self._tp_gather == "rank0"
         root = dist.get_global_rank(group, 0) if group is not None else 0
         gathered = torch.empty(rounds, world, max_rows, 8, dtype=F16, device=z4.device) if (rank == 0 or not to_root) else None
         mine = torch.zeros(rounds, max_rows, 8, dtype=F16, device=z4.device)
@@ -681,7 +651,7 @@ class AutoencoderKLCausal3D(nn.Module):
 
     def _decode_tiles_concurrent(self, z4):
         """All tiles of a tiled decode, decoded on `decode_streams` HIP streams at once (greedy by tile size), returned in the order
-        the blend loops consume them.  A tile is a chain of ~150 dependent launches whose grids often end in a partly filled last
+        of _tile_views.  A tile is a chain of ~150 dependent launches whose grids often end in a partly filled last
         round of workgroups (one per CU: 544 workgroups = 2.1 rounds on 256 CUs), and of small kernels (statistics folds, the
         mid-block attention); a second, independent tile fills those gaps.  Same kernels on the same data: bit-identical output."""
         views = list(self._tile_views(z4))
@@ -708,104 +678,33 @@ class AutoencoderKLCausal3D(nn.Module):
             cur.wait_stream(st)
         return out
 
-    def _take_tile(self, z_view):
-        """The decode loops' tile source: decode here, or (tile-parallel) the next pre-decoded tile."""
-        q = getattr(self, "_tile_queue", None)
-        if q is None:
-            return self._decode_tile(z_view)
-        buf, T, H, W = q.pop(0)
-        assert (T, H, W) == ((z_view.shape[1] - 1) * self.time_compression_ratio + 1, z_view.shape[2] * 8, z_view.shape[3] * 8)
-        return buf, T, H, W
-
-    def _spatial_tiled_decode(self, z4):
-        """autoencoder_kl_causal_3d.py:422-469 on a [C,T,H,W] view; returns planar fp16 [3,T',H',W']."""
-        ov = int(self.tile_latent_min_size * (1 - self.tile_overlap_factor))
-        ext = int(self.tile_sample_min_size * self.tile_overlap_factor)
-        lim = self.tile_sample_min_size - ext
-        rows = []
-        for i in range(0, z4.shape[-2], ov):
-            row = []
-            for j in range(0, z4.shape[-1], ov):
-                buf, T, H, W = self._take_tile(z4[:, :, i:i + self.tile_latent_min_size, j:j + self.tile_latent_min_size])
-                row.append(self._cl_view(buf, T, H, W))
-            rows.append(row)
-        heights = [min(r[0].shape[2], lim) for r in rows]
-        widths = [min(t.shape[3], lim) for t in rows[0]]
-        T = rows[0][0].shape[1]
-        out = torch.empty(3, T, sum(heights), sum(widths), dtype=F16, device=z4.device)
-        y0 = 0
-        for i, row in enumerate(rows):
-            x0 = 0
-            for j, tile in enumerate(row):
-                if i > 0:
-                    a = rows[i - 1][j]
-                    e = min(a.shape[2], tile.shape[2], ext)
-                    V.blend_(a[:, :, a.shape[2] - e:, :], tile[:, :, :e, :], 2, e)
-                if j > 0:
-                    a = row[j - 1]
-                    e = min(a.shape[3], tile.shape[3], ext)
-                    V.blend_(a[:, :, :, a.shape[3] - e:], tile[:, :, :, :e], 3, e)
-                V.copy4d_(tile[:, :, :heights[i], :widths[j]], out[:, :, y0:y0 + heights[i], x0:x0 + widths[j]])
-                x0 += widths[j]
-            y0 += heights[i]
-        return out
-
-    def _temporal_tiled_decode(self, z4):
-        """autoencoder_kl_causal_3d.py:510-541."""
-        T = z4.shape[1]
-        ov = int(self.tile_latent_min_tsize * (1 - self.tile_overlap_factor))
-        ext = int(self.tile_sample_min_tsize * self.tile_overlap_factor)
-        lim = self.tile_sample_min_tsize - ext
-        row = []
-        for i in range(0, T, ov):
-            tile = z4[:, i:i + self.tile_latent_min_tsize + 1]
-            if self.use_spatial_tiling and (tile.shape[-1] > self.tile_latent_min_size or tile.shape[-2] > self.tile_latent_min_size):
-                dec = self._spatial_tiled_decode(tile)
-            else:
-                dec = self._plain_decode(tile)
-            if i > 0:
-                dec = dec[:, 1:]
-            row.append(dec)
-        lens = [min(t.shape[1], lim + (1 if i == 0 else 0)) for i, t in enumerate(row)]
-        out = torch.empty(3, sum(lens), row[0].shape[2], row[0].shape[3], dtype=F16, device=z4.device)
-        t0 = 0
-        for i, tile in enumerate(row):
-            if i > 0:
-                a = row[i - 1]
-                e = min(a.shape[1], tile.shape[1], ext)
-                V.blend_(a[:, a.shape[1] - e:], tile[:, :e], 1, e)
-            V.copy4d_(tile[:, :lens[i]], out[:, t0:t0 + lens[i]])
-            t0 += lens[i]
-        return out
+    def _predecoded(self, tiles):
+        """Tile source over tiles decoded ahead, in the order of _tile_views: hands out the next one (and lets go of it) and checks
+        that it has the size of the view the assembler asks for."""
+        def take(z_view):
+            buf, T, H, W = tiles.pop(0)
+            assert (T, H, W) == self._decoded_size(z_view)
+            return buf, T, H, W
+        return take
 
     def _decode(self, z: torch.Tensor):
         assert len(z.shape) == 5, "The input tensor should have 5 dimensions."
         assert z.shape[0] == 1, "one video per _decode call: decode() steps through a batch"
         z4 = z[0].to(torch.float32)
-        self._tile_queue = None
         if self._t_ops is not None and (self.use_temporal_tiling or self.use_spatial_tiling):
             raise NotImplementedError("t_ops change the compression ratios the tile/blend geometry assumes; the fork runs them untiled")
-        if getattr(self, "_tp_enabled", False):
+        tiles = None          # tiles decoded ahead of the blends (sharded over ranks, else on decode_streams streams), if any
+        if self._tp_enabled:
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized() and dist.get_world_size(self._tp_group) > 1:
-                self._tile_queue = self._decode_tiles_sharded(z4, self._tp_group)
-                if self._tile_queue is None:
+                tiles = self._decode_tiles_sharded(z4, self._tp_group)
+                if tiles is None:
                     # gather-to-rank-0 mode on a non-root rank: the video lives on rank 0; same shape, zeros, here
-                    tc = self.time_compression_ratio
-                    return torch.zeros(1, 3, (z4.shape[1] - 1) * tc + 1, z4.shape[2] * 8, z4.shape[3] * 8, dtype=F16, device=z4.device)
-        if self._tile_queue is None and (self.use_temporal_tiling or self.use_spatial_tiling):
-            self._tile_queue = self._decode_tiles_concurrent(z4)
-        try:
-            return self._decode_assembled(z4)
-        finally:
-            self._tile_queue = None
-
-    def _decode_assembled(self, z4):
-        if self.use_temporal_tiling and z4.shape[1] > self.tile_latent_min_tsize:
-            return self._temporal_tiled_decode(z4)[None]
-        if self.use_spatial_tiling and (z4.shape[-1] > self.tile_latent_min_size or z4.shape[-2] > self.tile_latent_min_size):
-            return self._spatial_tiled_decode(z4)[None]
-        return self._plain_decode(z4)[None]
+                    return torch.zeros(1, 3, *self._decoded_size(z4), dtype=F16, device=z4.device)
+        if tiles is None and (self.use_temporal_tiling or self.use_spatial_tiling):
+            tiles = self._decode_tiles_concurrent(z4)
+        tile = self._decode_tile if tiles is None else self._predecoded(tiles)
+        return self._assemble_temporal(self._tile_plan(decode=True), z4, tile, 3)[None]
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None):

@@ -11,11 +11,8 @@ from .ops import _chk
 F16 = torch.float16
 
 
-def _i64x4(v: Sequence[int]):
-    return [int(x) for x in v]
-
-
-def _i32x4(v: Sequence[int]):
+def _int4(v: Sequence[int]):
+    """The strides (int64[4]) or the shape (int32[4]) of a 4-D view as the C ABI takes them."""
     return [int(x) for x in v]
 
 
@@ -292,8 +289,8 @@ def blend_(a_view, b_view, axis: int, extent: int):
     assert a_view.shape == b_view.shape and a_view.dim() == 4
     if b_view.numel() == 0:
         return b_view          # empty overlap (e.g. a trailing temporal tile of a single latent frame): nothing to blend
-    _lib.call("vae_blend_f16", a_view, _i64x4(a_view.stride()), b_view, _i64x4(b_view.stride()),
-                                            _i32x4(b_view.shape), axis, extent)
+    _lib.call("vae_blend_f16", a_view, _int4(a_view.stride()), b_view, _int4(b_view.stride()),
+                                            _int4(b_view.shape), axis, extent)
     return b_view
 
 
@@ -302,8 +299,8 @@ def copy4d_(src_view, dst_view):
     assert src_view.is_cuda and dst_view.is_cuda
     if dst_view.numel() == 0:
         return dst_view
-    _lib.call("copy4d_16b", src_view, _i64x4(src_view.stride()), dst_view, _i64x4(dst_view.stride()),
-                                         _i32x4(dst_view.shape))
+    _lib.call("copy4d_16b", src_view, _int4(src_view.stride()), dst_view, _int4(dst_view.stride()),
+                                         _int4(dst_view.shape))
     return dst_view
 
 
