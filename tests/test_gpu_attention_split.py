@@ -9,6 +9,7 @@ pytestmark = pytest.mark.gpu
 
 from hunyuanvideo_efficiency_amd import synthetic as syn  # noqa: E402
 from oracle import dit_ref as R  # noqa: E402
+from tests import attention_bounds as AB  # noqa: E402
 
 E = R.Prec(True)
 DEV = "cuda"
@@ -29,6 +30,11 @@ def test_kv_split_equals_single_pass_and_oracle(n_q, n_kv, H):
     torch.testing.assert_close(outs[1], outs[0], rtol=2 ** -7, atol=4e-3)
     ref = R.sdpa(q.float().reshape(1, n_q, H, 128), k.float().reshape(1, n_kv, H, 128), v.float().reshape(1, n_kv, H, 128), E)
     torch.testing.assert_close(outs[1], ref.reshape(n_q, H * 128), rtol=2 ** -7, atol=8e-3)
+    # both paths within the fp64 bound of tests/attention_bounds.py (its gap: the static maximum and the two halves' own maxima)
+    cut = (((n_kv + 63) // 64 + 1) // 2) * 64
+    bound = AB.AttnRef(q.to(DEV), k.to(DEV), v.to(DEV), H, gap=AB.kernel_gap(q.to(DEV), k.to(DEV), H, cuts=(cut,), static=True))
+    bound.check_o(outs[0], "single pass")
+    bound.check_o(outs[1], "kv split")
 
 
 @pytest.mark.parametrize("n_q,chunks,H", [(300, (257, 130, 4096), 2), (777, (1000, 1000, 1000, 11), 1), (64, (64,), 3)])
@@ -57,6 +63,13 @@ def test_ring_partials_and_merge(n_q, chunks, H):
         torch.testing.assert_close(out[:, :H * 128].float().cpu(), full.float().cpu(), rtol=2 ** -7, atol=4e-3)
         ref = R.sdpa(q.float().reshape(1, n_q, H, 128), k.float().reshape(1, n_kv, H, 128), v.float().reshape(1, n_kv, H, 128), E)
         torch.testing.assert_close(out[:, :H * 128].float().cpu(), ref.reshape(n_q, H * 128), rtol=2 ** -7, atol=8e-3)
+        # the merged chunks within the fp64 bound of attention over the concatenated keys; every pass (chunk or half chunk) has its own m
+        cuts, lo = [], 0
+        for c, s in zip(chunks, splits):
+            cuts += [lo + (((c + 63) // 64 + 1) // 2) * 64] if s == 2 else []
+            lo += c
+            cuts.append(lo)
+        AB.AttnRef(qd, kd, vd, H, gap=AB.kernel_gap(qd, kd, H, cuts=sorted(set(cuts)))).check_o(out[:, :H * 128], f"merged, splits {splits}")
     assert ops.attn_suggest_splits(118811, 14850 * 4, 6) in (1, 2)
     with pytest.raises(Exception):
         ops.attn_partial(qd, kd[:64], vd[:64], parts, H, 1)      # no free slot left -> loud failure

@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 
 from hunyuanvideo_efficiency_amd import synthetic as syn  # noqa: E402
 from oracle import dit_ref as R  # noqa: E402
+from tests import attention_bounds as AB  # noqa: E402
 
 E = R.Prec(True)
 DEV = "cuda"
@@ -45,6 +46,13 @@ def _check(ops, q, k, v, H, atol=8e-3):
     ref = _ref(q, k, v)
     got = _run(ops, q, k, v, H)
     torch.testing.assert_close(got.float().cpu(), ref, rtol=2 ** -7, atol=atol)
+    # and the fp64 contract with its per-element bound (tests/attention_bounds.py); from 4096 keys on _run hands the kernel a workspace:
+    # the static maximum and the halves of a KV split widen the gap between its m and the row max
+    n_q, n_kv = q.shape[0], k.shape[0]
+    qd, kd, vd = q.reshape(n_q, -1).to(DEV), k.reshape(n_kv, -1).to(DEV), v.reshape(n_kv, -1).to(DEV)
+    long = n_kv >= 64 * 64
+    gap = AB.kernel_gap(qd, kd, H, cuts=((((n_kv + 63) // 64 + 1) // 2) * 64,) if long else (), static=long)
+    AB.AttnRef(qd, kd, vd, H, gap=gap).check_o(got, f"n_q={n_q} n_kv={n_kv} H={H}")
 
 
 def test_late_spike_raises_max_for_some_rows(ops):
