@@ -93,7 +93,8 @@ extern "C" int hv_ln_modulate_bf16(const void* x, const void* shift_or_bias, con
 
 // ------------------------------------------------------------------------------------------------
 // FP8-MFMA path (opt-in; BASELINE.json config 4): per-token (row) dynamic quantisation of a GEMM A operand to OCP e4m3fn,
-//   s_row = max|y_row| / 448,  q = e4m3(clamp(y / s_row, +-448))  (round to nearest even),  y_row ~= q * s_row.
+//   s_row = max(max|y_row| / 448, 2^-126) (1 for an all-zero row),  q = e4m3(clamp(y / s_row, +-448))  (round to nearest even),
+//   y_row ~= q * s_row.
 // The row scale is applied by the GEMM epilogue (hv_gemm_fp8) together with the per-tensor weight scale of the reference's FP8
 // checkpoints (fp8_optimization.py:85-100).  pack4: four fp32 -> one dword of 4 e4m3 bytes (v_cvt_pk_fp8_f32 x2).
 __device__ __forceinline__ uint32_t pack4_fp8(float a, float b, float c, float d) {
@@ -107,6 +108,9 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// Floor of a row scale: with amax < 448 * 2^-126 the quotient amax / 448 is subnormal (or zero) and its reciprocal +inf, which
+// would turn every zero of the row into 0 * inf = NaN.  At the floor 1 / s = 2^126 is finite and |x| / s <= 448 still holds.
+#define HV_FP8_MIN_ROW_SCALE 1.17549435e-38f   /* 2^-126 */
 __device__ __forceinline__ float clamp448(float v) { return __builtin_amdgcn_fmed3f(v, -448.0f, 448.0f); }
 
 // K1 with an fp8 output: y = bf16(LN(x) * bf16(1 + scale) + shift) exactly as ln_mod_kernel mode 0 (the bf16 rounding of the
@@ -173,7 +177,7 @@ __global__ __launch_bounds__(256) void ln_mod_fp8_kernel(const bf16_t* __restric
         }
     }
     amax = wave_max(amax);
-    const float sc = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+    const float sc = amax > 0.f ? fmaxf(amax * (1.0f / 448.0f), HV_FP8_MIN_ROW_SCALE) : 1.0f;
     const float inv = 1.0f / sc;
     if (lane == 0) row_scale[row] = sc;
     uint8_t* orow = out + row * ldo;
@@ -223,7 +227,7 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
         for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[j]));
     }
     amax = wave_max(amax);
-    const float sc = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+    const float sc = amax > 0.f ? fmaxf(amax * (1.0f / 448.0f), HV_FP8_MIN_ROW_SCALE) : 1.0f;
     const float inv = 1.0f / sc;
     if (lane == 0) row_scale[row] = sc;
     uint8_t* orow = out + row * ldo;

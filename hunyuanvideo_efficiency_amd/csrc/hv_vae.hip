@@ -511,7 +511,7 @@ __global__ __launch_bounds__(256) void copy4d_kernel(const uint16_t* __restrict_
 __global__ __launch_bounds__(256) void postprocess_kernel(const uint16_t* __restrict__ x, float* __restrict__ out, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float v = rh(rh(h2f(x[i]) * 0.5f) + 0.5f);
-        out[i] = fminf(fmaxf(v, 0.f), 1.f);
+        out[i] = v == v ? fminf(fmaxf(v, 0.f), 1.f) : v;             // fmaxf drops a NaN; torch's clamp keeps it
     }
 }
 

@@ -149,10 +149,14 @@ int hv_fp8_dequant_bf16(const void* w_e4m3fn, const void* scale_bf16, void* out_
 /* ---- FP8-MFMA path (opt-in; BASELINE.json configs[3] "fp8 weight path (CDNA4 fp8 MFMA)").  The reference's FP8 is weight-only
  * (fp8_optimization.py:50-80: e4m3fn weights + per-tensor `fp8_scale`, dequantised to bf16 every forward - that path is
  * hv_fp8_dequant_bf16 + hv_gemm_bf16).  Here the SAME stored weights feed v_mfma_scale_f32_16x16x128_f8f6f4 directly and the
- * activations are quantised per token: q = e4m3(clamp(x / s_row, +-448)), s_row = max|x_row| / 448, so
+ * activations are quantised per token: q = e4m3(clamp(x / s_row, +-448)), s_row = max(max|x_row| / 448, 2^-126) (1 for an all-zero
+ * row), so
  *   y[m][n] = (sum_k qa[m][k] * qw[n][k]) * s_row[m] * fp8_scale + bias[n]   followed by hv_gemm_bf16's epilogues.
  * New error vs the reference path: the e4m3 rounding of the activations (2^-4 relative per element, averaging over K);
- * tolerance stated in tests/test_gpu_fp8_mfma.py. */
+ * tolerance stated in tests/test_gpu_fp8_mfma.py.
+ * The floor 2^-126 (the smallest normal fp32) keeps 1 / s_row finite: every code and scale is finite for finite input, also for a row
+ * whose largest magnitude is below 448 * 2^-126 (a subnormal quotient would have a reciprocal of +inf and turn the row's zeros into
+ * NaN codes); |x| / s_row <= 448 holds with the floor as without it.  Such a row quantises coarsely (it is < 2^-117 everywhere). */
 
 /* K1 with an fp8 output: y = bf16(LN(x) * bf16(1 + scale) + shift) (hv_ln_modulate_bf16 mode 0), then per-row quantisation:
  * out_q [M, D] e4m3 bytes (row stride ldq bytes, % 16), out_row_scale [M] fp32. */
@@ -293,7 +297,8 @@ int hv_vae_blend_f16(const void* a, const int64_t* a_strides, void* b, const int
 int hv_copy4d_16b(const void* src, const int64_t* src_strides, void* dst, const int64_t* dst_strides, const int* dims,
                   hipStream_t stream);
 
-/* K20 tail: (image / 2 + 0.5).clamp(0, 1) in fp16 then .float() (pipeline_hunyuan_video.py:1090-1092). */
+/* K20 tail: (image / 2 + 0.5).clamp(0, 1) in fp16 then .float() (pipeline_hunyuan_video.py:1090-1092).  A NaN input gives a NaN, as
+ * torch's clamp keeps it (it is not clamped to 0). */
 int hv_vae_postprocess_f16_f32(const void* x, float* out, int64_t n, hipStream_t stream);
 
 /* Reconstruction scoring (evaluation/compute_metrics.py:31-41 compute_psnr / compute_ssim of the fork, without the mp4 round trip):

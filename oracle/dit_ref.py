@@ -357,11 +357,13 @@ def denoise_loop(sd, cfg, latents: Tensor, n_steps: int, text_states, text_mask,
 # ----------------------------------------------------------------------------- FP8-MFMA path (quantisation-aware oracle)
 def fp8_quant_rows(x: Tensor) -> Tuple[Tensor, Tensor]:
     """Per-token dynamic quantisation of a GEMM A operand on the opt-in FP8-MFMA path (include/hv_kernels.h, hv_quant_rows_fp8 /
-    hv_ln_modulate_fp8): s = max|x_row| * (1/448) (1 for an all-zero row), q = e4m3fn(clamp(x * (1/s), +-448)), round to nearest
-    even.  Not reference arithmetic (the reference's FP8 is weight-only, fp8_optimization.py:50-80): this states OUR contract so
+    hv_ln_modulate_fp8): s = max(max|x_row| * (1/448), 2^-126) (1 for an all-zero row), q = e4m3fn(clamp(x * (1/s), +-448)), round to
+    nearest even.  The floor 2^-126 keeps 1/s finite: without it a row with 0 < max|x| < 448 * 2^-126 has a subnormal s, 1/s = inf,
+    and each of its zeros becomes 0 * inf = NaN; with it every code and scale is finite for finite input and |x| / s <= 448 still
+    holds.  Not reference arithmetic (the reference's FP8 is weight-only, fp8_optimization.py:50-80): this states OUR contract so
     that the kernels can be checked against it; the distance to the reference path is bounded separately in the tests."""
     amax = x.abs().amax(dim=-1, keepdim=True).float()
-    s = torch.where(amax > 0, amax * torch.tensor(1.0 / 448.0, dtype=torch.float32), torch.ones_like(amax))
+    s = torch.where(amax > 0, (amax * torch.tensor(1.0 / 448.0, dtype=torch.float32)).clamp(min=2.0 ** -126), torch.ones_like(amax))
     q = (x.float() * (1.0 / s)).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float()
     return q, s
 

@@ -35,13 +35,11 @@ from hunyuanvideo_efficiency_amd import synthetic as syn  # noqa: E402
 from oracle import dit_ref as R  # noqa: E402
 from oracle import vae_ref as VR  # noqa: E402
 from tests import error_bounds as EB  # noqa: E402
+from tests.guarded_memory import INT, NAN_BITS, SENT, Guarded, Poisoned, bits, poisoned_vec, same_bits  # noqa: E402,F401
 
 DEV = "cuda"
 E = R.Prec(True)
 BF16, F16, F32, FP8 = torch.bfloat16, torch.float16, torch.float32, torch.float8_e4m3fn
-SENT = {2: 0x7E5A, 4: 0x7F5A5A5A}            # sentinel bit patterns of 16- and 32-bit output cells
-INT = {2: torch.int16, 4: torch.int32, 1: torch.uint8}
-NAN_BITS = {4: 0x7FC00000, 2: 0x7FFF, 1: 0x7F}   # a NaN in fp32, in bf16 and fp16 (0x7FFF), in e4m3fn (0x7F)
 RATIOS = {}
 
 
@@ -111,54 +109,6 @@ def kernel_path(name):
     plain = name.replace("(anonymous namespace)::", "")
     hits = [p for p, (dem, mang) in KERNELS.items() if plain.startswith(dem) or (" " + dem) in plain or mang in name]
     return hits[0] if len(hits) == 1 else None
-
-
-# ------------------------------------------------------------------------------------------------------ poisoned / guarded memory
-class Poisoned:
-    """t [R, C] placed at rows [before, before + R), columns [0, C) of a NaN-filled [before + R + after, C + pad] buffer"""
-
-    def __init__(self, t, before=3, after=5, pad=24):
-        es = t.element_size()
-        R_, C_ = t.shape
-        self.buf = torch.full((before + R_ + after, C_ + pad), NAN_BITS[es], dtype=INT[es], device=DEV)
-        self.view = self.buf.view(t.dtype)[before:before + R_, :C_]
-        self.view.copy_(t)
-        self.mask = torch.ones_like(self.buf, dtype=torch.bool)
-        self.mask[before:before + R_, :C_] = False
-
-    def intact(self):
-        return bool((self.buf[self.mask] == NAN_BITS[self.buf.element_size()]).all())
-
-
-def poisoned_vec(v, after=24):
-    """a contiguous vector followed by NaNs"""
-    es = v.element_size()
-    buf = torch.full((v.numel() + after,), NAN_BITS[es], dtype=INT[es], device=DEV).view(v.dtype)
-    buf[:v.numel()].copy_(v)
-    return buf[:v.numel()]
-
-
-class Guarded:
-    """an output [M, n] at rows [before, before + M), columns [c0, c0 + n) of a sentinel-filled buffer"""
-
-    def __init__(self, M, n, dtype, c0=0, before=2, after=3, pad=16):
-        es = torch.empty((), dtype=dtype).element_size()
-        self.sent = SENT[es]
-        self.buf = torch.full((before + M + after, c0 + n + pad), self.sent, dtype=INT[es], device=DEV)
-        self.view = self.buf.view(dtype)[before:before + M, c0:c0 + n]
-        self.mask = torch.ones_like(self.buf, dtype=torch.bool)
-        self.mask[before:before + M, c0:c0 + n] = False
-
-    def intact(self):
-        return bool((self.buf[self.mask] == self.sent).all())
-
-
-def bits(t):
-    return t.contiguous().view(INT[t.element_size()])
-
-
-def same_bits(a, b):
-    return torch.equal(bits(a), bits(b))
 
 
 def within_ulp(got, ref, dtype):
