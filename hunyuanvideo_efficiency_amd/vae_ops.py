@@ -190,14 +190,17 @@ def conv3d_upsampled_subpixel(x, w_sub, table, ntap: int, bias, sT: int, sH: int
     return (out, st) if gn_stats else out
 
 
-def conv3d_causal_strided(x, w_taps, bias, sT: int, sH: int, sW: int, cin: int, cout: int, stride=(1, 1, 1)):
-    """DownsampleCausal3D conv: x channels-last [sT*sH*sW, >=cin] -> ([T*H*W, cout] fp16, T, H, W)."""
+def conv3d_causal_strided(x, w_taps, bias, sT: int, sH: int, sW: int, cin: int, cout: int, stride=(1, 1, 1), out=None):
+    """DownsampleCausal3D conv: x channels-last [sT*sH*sW, >=cin] -> ([T*H*W, cout] fp16, T, H, W); out: a [T*H*W, cout] view to fill."""
     _chk(x, F16, "x"), _chk(w_taps, F16, "w_taps")
     _conv_source_limit(x)
     assert w_taps.is_contiguous() and w_taps.numel() == cout * 27 * cin, (w_taps.shape, cout, cin)
     st, sh, sw = (int(v) for v in stride)
     T, H, W = (sT - 1) // st + 1, (sH - 1) // sh + 1, (sW - 1) // sw + 1
-    out = torch.empty(T * H * W, cout, dtype=F16, device=x.device)
+    if out is None:
+        out = torch.empty(T * H * W, cout, dtype=F16, device=x.device)
+    _chk(out, F16, "out")
+    assert tuple(out.shape) == (T * H * W, cout), (tuple(out.shape), T, H, W, cout)
     _lib.call("conv3d_causal_strided_f16", x, x.stride(0), w_taps, bias, out, out.stride(0),
                                                         sT, sH, sW, cin, cout, st, sh, sw)
     return out, T, H, W

@@ -139,6 +139,69 @@ def copy3d(src, dst, n_batch, rows, cols, src_bs, src_ld, dst_bs, dst_ld):
     return dst
 
 
+# ---- VAE conv entry points (hunyuanvideo_efficiency_amd.vae_ops.*): fp32 emulations in the kernels' own operation order, so that the
+# reference-and-bound logic of the GPU edge tests (tests/conv_bounds.py) runs against them on the CPU (tests/test_conv_bounds_cpu.py)
+def _gather_rows(m, tap, oH, oW, src, stride):
+    _, sH, sW = src
+    t, h, w = m // (oH * oW), (m // oW) % oH, m % oW
+    ti = (t * stride[0] + tap // 9 - 2).clamp(min=0)
+    hi = (h * stride[1] + (tap // 3) % 3 - 1).clamp(0, sH - 1)
+    wi = (w * stride[2] + tap % 3 - 1).clamp(0, sW - 1)
+    return (ti * sH + hi) * sW + wi
+
+
+def conv3d_causal_strided(x, w_taps, bias, sT, sH, sW, cin, cout, stride=(1, 1, 1), out=None):
+    """K-tile by K-tile (64 channels of one tap) into one fp32 accumulator, bias added last, one rounding to fp16"""
+    T, H, W = ((s - 1) // m + 1 for s, m in zip((sT, sH, sW), stride))
+    m = torch.arange(T * H * W)
+    wt = w_taps.float().reshape(cout, 27, cin)
+    acc = torch.zeros(T * H * W, cout)
+    for tap in range(27):
+        a = x[_gather_rows(m, tap, H, W, (sT, sH, sW), stride)][:, :cin].float()
+        for k0 in range(0, cin, 64):
+            acc = acc + a[:, k0:k0 + 64] @ wt[:, tap, k0:k0 + 64].T
+    if bias is not None:
+        acc = acc + bias.float()[None]
+    r = acc.to(torch.float16)
+    if out is None:
+        return r, T, H, W
+    out.copy_(r)
+    return out, T, H, W
+
+
+def cout4_weights_from_fragments(w_frag):
+    """the inverse of vae_ops.cout4_weight_fragments: fp16 [7, 4, 64, 8] -> [tap 28][c 4][channel 128]"""
+    return w_frag.reshape(7, 4, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(28, 4, 128)
+
+
+def conv_cout4(x, affine, silu, w_frag, bias, T, H, W, cin, cout, out=None):
+    """planes[tap][voxel][c] in fp32 (32-channel steps into one accumulator, as the MFMA chain), then bias + the 27 planes at the
+    tap-shifted voxels in the order tap = 0..26, one rounding to fp16; columns cout..7 zero (written only where the row stride is >= 8)"""
+    M = T * H * W
+    h = x[:, :cin].float()
+    if affine is not None:
+        t = h * affine[:, 0][None] + affine[:, 1][None]
+        h = (t / (1.0 + torch.exp(-t)) if silu else t)
+    h = h.to(torch.float16).float()
+    wn = cout4_weights_from_fragments(w_frag).float()
+    planes = torch.zeros(27, M, 3)
+    for tap in range(27):
+        for k0 in range(0, cin, 32):
+            planes[tap] = planes[tap] + h[:, k0:k0 + 32] @ wn[tap, :3, k0:k0 + 32].T
+    acc = torch.zeros(M, 3)
+    acc[:, :cout] = bias[:cout].float()[None]
+    m = torch.arange(M)
+    for tap in range(27):
+        acc = acc + planes[tap][_gather_rows(m, tap, H, W, (T, H, W), (1, 1, 1))]
+    r = torch.zeros(M, 8, dtype=torch.float16)
+    r[:, :3] = acc.to(torch.float16)
+    if out is None:
+        return r
+    n = 8 if out.stride(0) >= 8 else cout          # ldo >= 8: one 16-byte store; below: Cout scalar stores
+    out[:, :n] = r[:, :n]
+    return out
+
+
 NAMES = ["ln_modulate", "qknorm_rope_", "gemm", "linear_smallm", "attn_fwd", "patchify", "unpatchify", "euler_step_",
          "masked_mean", "broadcast_row_", "timestep_embedding", "copy3d"]
 

@@ -232,6 +232,18 @@ def euler_ref(s, v, dt: float):
 
 
 # ---------------------------------------------------------------------------------------------------- GroupNorm apply
+def gn_apply_eval(x, affine, silu: bool):
+    """(y64, e32): the fp64 value of gn_apply_ref and the error of its fp32 evaluation alone (the bound without the store's ulp)"""
+    sc, sh = affine[:, 0].double()[None], affine[:, 1].double()[None]
+    p = x.double() * sc
+    t = p + sh
+    lin = 2.0 ** -23 * (p.abs() + sh.abs())
+    if not silu:
+        return t, lin
+    y = silu64(t)
+    return y, 1.1 * lin + y.abs() * ((t.abs() + 2.0) * EPS32 + 2.0 ** -22)
+
+
 def gn_apply_ref(x, affine, silu: bool):
     """t = x sc + sh from the fp32 affine values, y = silu(t) or t, in fp64.
     t in fp32: the product rounded (2^-24 |x sc|) and the sum (2^-24 |t| <= 2^-24 (|x sc| + |sh|)): 2^-23 (|x sc| + |sh|) covers both
@@ -239,14 +251,8 @@ def gn_apply_ref(x, affine, silu: bool):
     __expf(-t) = exp2(-t log2 e) rounds its argument (|t| 2^-24 relative to the value) and is 1 ulp (2^-23) itself; that relative error
     reaches the sigmoid times (1 - sigmoid) <= 1; the add, v_rcp_f32 (1 ulp) and the multiply: 2^-24 + 2^-23 + 2^-24:
     |y| ((|t| + 2) 2^-24 + 2^-22).  One fp16 ulp for the store."""
-    sc, sh = affine[:, 0].double()[None], affine[:, 1].double()[None]
-    p = x.double() * sc
-    t = p + sh
-    lin = 2.0 ** -23 * (p.abs() + sh.abs())
-    if not silu:
-        return t, ulp_out(t, F16) + lin
-    y = silu64(t)
-    return y, ulp_out(y, F16) + 1.1 * lin + y.abs() * ((t.abs() + 2.0) * EPS32 + 2.0 ** -22)
+    y, e32 = gn_apply_eval(x, affine, silu)
+    return y, ulp_out(y, F16) + e32
 
 
 # ---------------------------------------------------------------------------------------------------- row softmax

@@ -14,10 +14,21 @@ hv_conv3d_upsampled_subpixel_f16); test_path_table_matches_launched_kernels conf
     C5 gemm8_kernel<F16T,true>        conv, Cout > 128, Cin a power of two >= 256
     C6 gemm_kernel<F16T,true,256>     conv, Cout > 128, otherwise
     SP gemm8_kernel<F16T,true,true>   the sub-pixel upsampling conv
+In launch()'s own terms (conv_path): the pipelined loops C2 - C5 need packed coordinates, cT * mt < 256 and clamp extents bH, bW <= 4096
+(conv_fits_packing), else C1 / C6; the W-shift-reuse kernels C3 / C4 need mw == 1 and bW == cW on top of the W conditions.  The strided
+entry point (hv_conv3d_causal_strided_f16: mt / mh / mw of 1 or 2, bH / bW the SOURCE extents) goes through the same launch(), so a
+stride of 2 along W always leaves C3 / C4 for C2.
 
 Shapes: M in {1, 255, 257}; tiles_m in {5, 6, 7, 9} with tiles_n >= 2 and a grid that is not a multiple of 8 (a short last band
 of GROUP_M = 4 M-tiles, and the XCD remap with a remainder); N = 256 k + 8 and N = BN - 8; the smallest K of each main loop and
 an odd K-tile count; convs at T = H = W = 1, M % 256 in {1, 255}, Cout from 8 to 264 across the narrow / 128 / 256 boundaries.
+Strided convs (STRIDED_CASES, source grid and stride): every path with a stride of 2 on each axis it admits (C5: all seven strides that
+are not all ones); 1x1x1 and 2x2x2 sources at stride (2,2,2) (M = 1, every tap clamped); odd and even source extents on each strided
+axis (the odd one makes the last output read one past the source and clamp at the SOURCE extent); several M tiles with M % 256 in
+{1, 255} on C1, C2, C5, C6 and in {4, 252} on C3 / C4, whose W % 4 == 0 makes M a multiple of 4; stride (1,1,1) bit-equal to
+hv_conv3d_causal_f16.  Both sides of the packing guard (PACK_CASES, STRIDED_PACK_CASES, SP_PACK_CASES): T = 255 | 256, H and W = 4096 |
+4097 at unit stride; sT = 254 | 255 with stride_t 2 (cT mt = 254 | 256), source H and W = 4096 | 4097 with a stride of 2 (largest packed
+coordinate 4094); the sub-pixel form at sT = 254 (accepted) and 255 (refused as a bad argument, the output untouched).
 
 Checks per case: the plain output within the fp64 bound; GELU / SiLU within 1 ulp of the oracle's formula on the kernel's own y;
 gate + residual (in place and not) and res bit-equal to the oracle's formula; column splits bit-equal to the unsplit launch;
@@ -33,7 +44,9 @@ pytestmark = pytest.mark.gpu
 
 from hunyuanvideo_efficiency_amd import synthetic as syn  # noqa: E402
 from oracle import dit_ref as R  # noqa: E402
+from oracle import vae_enc_ref as VE  # noqa: E402
 from oracle import vae_ref as VR  # noqa: E402
+from tests import conv_bounds as CB  # noqa: E402
 from tests import error_bounds as EB  # noqa: E402
 from tests.guarded_memory import INT, NAN_BITS, SENT, Guarded, Poisoned, bits, poisoned_vec, same_bits  # noqa: E402,F401
 
@@ -75,12 +88,15 @@ def gemm_path(kind, N, K):
     return p + ("3" if K >= 3 * 64 else "2")       # K >= 3 BK -> gemm8_kernel (HV_GEMM_2STAGE unset)
 
 
-def conv_path(T, H, W, cin, cout):
-    """launch<F16T, true> for hv_conv3d_causal_f16 (unit stride: mw = 1, bW = cW = W, mt = 1)"""
-    pow2, fits = cin & (cin - 1) == 0, T < 256 and H <= 4096 and W <= 4096
+def conv_path(T, H, W, cin, cout, stride=(1, 1, 1), src=None):
+    """launch<F16T, true>: T x H x W is the OUTPUT grid (cT, cH, cW), stride = (mt, mh, mw), src the source extents (sT, sH, sW) of the
+    strided entry point, whose clamp extents bH / bW are the source's; hv_conv3d_causal_f16 (src None) has bH = cH, bW = cW, upsampled or not"""
+    mt, mh, mw = stride
+    bH, bW = (H, W) if src is None else src[1:]
+    pow2, fits = cin & (cin - 1) == 0, T * mt < 256 and bH <= 4096 and bW <= 4096
     if cout <= 128:
         if pow2 and cin >= 128 and (27 * cin // 64) % 3 == 0 and 27 * cin // 64 >= 6 and fits:
-            if W <= 256 and 256 % W == 0 and W % 4 == 0:
+            if mw == 1 and bW == W and W <= 256 and 256 % W == 0 and W % 4 == 0:
                 return "C4" if cout <= 32 else "C3"
             return "C2"
         return "C1"
@@ -235,24 +251,7 @@ def test_gemm_edges(ops, V, kind, M, N, K):
 
 
 # ------------------------------------------------------------------------------------------------------ conv rows
-def conv_ref(x, w_taps, b, T, H, W, cin, cout, up_t=False, up_hw=False):
-    """fp64 im2col reference of hv_conv3d_causal_f16: output voxel (t, h, w), tap (dt, dh, dw) reads source voxel
-    (max(t + dt - 2, 0) [halved causally if up_t], clamp(h + dh - 1) >> up_hw, clamp(w + dw - 1) >> up_hw)"""
-    dev = x.device
-    sH, sW = H >> int(up_hw), W >> int(up_hw)
-    m = torch.arange(T * H * W, device=dev)
-    t, h, w = m // (H * W), (m // W) % H, m % W
-    wt = w_taps.reshape(cout, 27, cin)
-    ref = EB.Ref()
-    for tap in range(27):
-        dt_, dh, dw = tap // 9, (tap // 3) % 3, tap % 3
-        ti = (t + dt_ - 2).clamp(min=0)
-        if up_t:
-            ti = torch.where(ti == 0, ti, 1 + (ti - 1) // 2)
-        hi = (h + dh - 1).clamp(0, H - 1) >> int(up_hw)
-        wi = (w + dw - 1).clamp(0, W - 1) >> int(up_hw)
-        ref.add(x[(ti * sH + hi) * sW + wi], wt[:, tap])
-    return ref.bias(b)
+conv_ref = CB.conv_ref        # the fp64 im2col reference, strided or upsampled (tests/conv_bounds.py)
 
 
 def subpixel_ref(x, w_sub, table, ntap, b, sT, sH, sW, cin, cout, up_t):
@@ -301,16 +300,56 @@ CONV_CASES = [   # T, H, W, cin, cout, up_t, up_hw  (output grid)
     # C6: 2-stage 256 x 256 (Cin 64 / 128)
     (1, 1, 1, 64, 136, 0, 0), (3, 5, 17, 64, 264, 0, 0), (5, 9, 29, 64, 136, 0, 0), (5, 11, 29, 64, 264, 0, 0), (1, 3, 5, 128, 256, 0, 0),
 ]
+# both sides of conv_fits_packing() at unit stride: (T, H, W, cin, cout, the path conv_path must predict)
+PACK_CASES = [
+    (255, 1, 2, 128, 40, "C2"), (256, 1, 2, 128, 40, "C1"), (255, 1, 2, 256, 136, "C5"), (256, 1, 2, 256, 136, "C6"),
+    (255, 1, 4, 128, 40, "C3"), (256, 1, 4, 128, 40, "C1"),
+    (1, 1, 4096, 128, 8, "C2"), (1, 1, 4097, 128, 8, "C1"), (1, 1, 4096, 256, 136, "C5"), (1, 1, 4097, 256, 136, "C6"),
+    (1, 4096, 1, 128, 8, "C2"), (1, 4097, 1, 128, 8, "C1"), (1, 4096, 1, 256, 136, "C5"), (1, 4097, 1, 256, 136, "C6"),
+]
+
+
+def _strided_cases():
+    c = [  # source T, H, W, cin, cout, stride
+        # C1: Cin 64
+        (1, 1, 1, 64, 8, (2, 2, 2)), (2, 2, 2, 64, 40, (2, 2, 2)), (5, 37, 17, 64, 128, (2, 2, 2)), (3, 10, 34, 64, 120, (1, 2, 2)),
+        (7, 6, 17, 64, 40, (2, 1, 1)), (6, 62, 22, 64, 32, (2, 2, 2)),
+        # C2: Cin 128, a stride of 2 along W (never the W-shift-reuse kernel); source W 17 -> 9 (513 rows), 22 -> 11 (1023 rows)
+        (1, 1, 1, 128, 128, (2, 2, 2)), (2, 2, 2, 128, 40, (2, 2, 2)), (5, 37, 17, 128, 120, (2, 2, 2)), (6, 62, 22, 128, 40, (2, 2, 2)),
+        # C5: Cin 256 / 512, the seven strides; 513 / 1023 / 255 rows
+        (1, 1, 1, 256, 136, (2, 2, 2)), (2, 2, 2, 512, 264, (2, 2, 2)), (5, 37, 17, 256, 264, (2, 2, 2)), (6, 62, 22, 512, 136, (2, 2, 2)),
+        (3, 10, 34, 256, 136, (1, 2, 2)), (6, 5, 33, 512, 264, (2, 1, 2)), (5, 10, 17, 256, 264, (2, 2, 1)), (3, 19, 18, 256, 136, (1, 1, 2)),
+        (3, 37, 9, 512, 136, (1, 2, 1)), (5, 19, 9, 256, 264, (2, 1, 1)),
+        # C6: Cin 64 / 128, Cout 136
+        (2, 2, 2, 64, 136, (2, 2, 2)), (1, 1, 1, 128, 136, (2, 2, 2)), (5, 37, 17, 64, 136, (2, 2, 2)), (6, 62, 22, 128, 136, (2, 2, 2)),
+    ]
+    # C3 (Cout 40 / 128) and C4 (Cout 8 / 32): unit stride along W, source W in {4, 16, 64}; odd and even sT / sH; 260, 1020 rows (M % 256
+    # = 4 / 252), 816, 960, 96
+    for co_a, co_b in ((40, 128), (8, 32)):
+        c += [(9, 13, 4, 128, co_a, (2, 1, 1)), (10, 13, 4, 128, co_b, (2, 1, 1)), (3, 170, 4, 128, co_a, (1, 2, 1)),
+              (3, 33, 16, 128, co_b, (1, 2, 1)), (5, 9, 64, 128, co_a, (2, 2, 1)), (4, 6, 16, 128, co_b, (2, 2, 1))]
+    return c
+
+
+STRIDED_CASES = _strided_cases()
+STRIDED_PACK_CASES = [   # source T, H, W, cin, cout, stride, the path: cT mt = 254 | 256; source H, W = 4096 (largest packed 4094) | 4097
+    (254, 1, 2, 128, 40, (2, 1, 1), "C2"), (255, 1, 2, 128, 40, (2, 1, 1), "C1"), (254, 2, 1, 256, 136, (2, 1, 1), "C5"),
+    (255, 2, 1, 256, 136, (2, 1, 1), "C6"), (1, 4096, 1, 128, 8, (1, 2, 1), "C2"), (1, 4097, 1, 128, 8, (1, 2, 1), "C1"),
+    (1, 4096, 2, 256, 136, (1, 2, 1), "C5"), (1, 4097, 2, 256, 136, (1, 2, 1), "C6"), (1, 1, 4096, 128, 8, (1, 1, 2), "C2"),
+    (1, 1, 4097, 128, 8, (1, 1, 2), "C1"),
+]
+UNIT_STRIDE_CASES = [(2, 3, 5, 64, 40), (2, 3, 12, 128, 128), (2, 3, 8, 128, 40), (2, 3, 8, 128, 32), (2, 3, 5, 256, 136), (2, 3, 5, 64, 136)]
+SP_PACK_CASES = [(254, 1, 1, 256, 136, 0), (254, 1, 1, 256, 136, 1)]        # sT + 1 = 255 < 256: accepted; sT = 255 is refused
 SP_CASES = [(1, 1, 1, 256, 136, 1), (2, 3, 5, 256, 264, 1), (3, 5, 7, 256, 136, 0), (3, 9, 13, 256, 264, 1), (2, 5, 6, 512, 256, 0)]
 
 
-def _conv_check(V, path, what, run, ref, M, cout, gn_ok):
+def _conv_check(V, path, what, run, ref, M, cout, gn_ok, label=None):
     """run(x_sel, w_sel, out=..., res=..., gn_stats=...) -> out [, st]; x_sel / w_sel: 'poisoned' or 'dense'"""
     o = Guarded(M, cout, F16, c0=8)
     run("poisoned", out=o.view)
     assert o.intact(), f"{what}: a store outside the output"
     y = o.view.clone()
-    _record(path, EB.check(y, ref, F16, what))
+    _record(label or path, EB.check(y, ref, F16, what))
     run("poisoned", out=o.view)
     assert same_bits(o.view, y), f"{what}: a second launch differs"
     assert same_bits(run("dense"), y), f"{what}: strided NaN-padded operands give other bits than dense ones"
@@ -323,9 +362,7 @@ def _conv_check(V, path, what, run, ref, M, cout, gn_ok):
     return y
 
 
-@pytest.mark.parametrize("T,H,W,cin,cout,up_t,up_hw", CONV_CASES,
-                         ids=[f"{conv_path(*c[:5])}-{'x'.join(map(str, c[:3]))}-{c[3]}to{c[4]}{'-up' if c[5] or c[6] else ''}" for c in CONV_CASES])
-def test_conv_edges(V, T, H, W, cin, cout, up_t, up_hw):
+def _conv_case(V, T, H, W, cin, cout, up_t, up_hw, label=None):
     path = conv_path(T, H, W, cin, cout)
     what = f"{path} conv {T}x{H}x{W} {cin}->{cout} up {up_t}{up_hw}"
     sT, sH, sW = ((T + 1) // 2 if up_t else T), H >> up_hw, W >> up_hw
@@ -349,7 +386,7 @@ def test_conv_edges(V, T, H, W, cin, cout, up_t, up_hw):
         w5 = w.cpu().double().reshape(cout, 3, 3, 3, cin).permute(0, 4, 1, 2, 3)
         o5 = VR.causal_conv3d(x5, w5, b.cpu().double(), VR.FP32)[0].permute(1, 2, 3, 0).reshape(M, cout)
         torch.testing.assert_close(ref.y.cpu(), o5, rtol=1e-12, atol=1e-12)
-    y = _conv_check(V, path, what, run, ref, M, cout, cout % 64 == 0)
+    y = _conv_check(V, path, what, run, ref, M, cout, cout % 64 == 0, label)
     # residual epilogue: fp16(res + y), bit-equal; poison around res untouched
     res = U((M, cout), what + ".res").to(F16)
     Rs = Poisoned(res, 1, 3, 16)
@@ -359,13 +396,100 @@ def test_conv_edges(V, T, H, W, cin, cout, up_t, up_hw):
     assert X.intact() and Wp.intact()
 
 
-@pytest.mark.parametrize("sT,sH,sW,cin,cout,up_t", SP_CASES, ids=[f"SP-{'x'.join(map(str, c[:3]))}-{c[3]}to{c[4]}-t{c[5]}" for c in SP_CASES])
-def test_subpixel_edges(V, sT, sH, sW, cin, cout, up_t):
-    what = f"SP {sT}x{sH}x{sW} {cin}->{cout} up_t {up_t}"
+@pytest.mark.parametrize("T,H,W,cin,cout,up_t,up_hw", CONV_CASES,
+                         ids=[f"{conv_path(*c[:5])}-{'x'.join(map(str, c[:3]))}-{c[3]}to{c[4]}{'-up' if c[5] or c[6] else ''}" for c in CONV_CASES])
+def test_conv_edges(V, T, H, W, cin, cout, up_t, up_hw):
+    _conv_case(V, T, H, W, cin, cout, up_t, up_hw)
+
+
+@pytest.mark.parametrize("T,H,W,cin,cout,path", PACK_CASES, ids=[f"{c[5]}-{'x'.join(map(str, c[:3]))}-{c[3]}to{c[4]}" for c in PACK_CASES])
+def test_conv_packing_guard(V, T, H, W, cin, cout, path):
+    """T = 255 | 256 and H, W = 4096 | 4097: the last coordinates the 8 + 12 + 12 bit packing holds, and the first the 2-stage loops take"""
+    assert conv_path(T, H, W, cin, cout) == path
+    _conv_case(V, T, H, W, cin, cout, 0, 0, label=path + ".pack")
+
+
+def _strided_case(V, sT, sH, sW, cin, cout, stride, label):
+    src = (sT, sH, sW)
+    T, H, W = CB.out_grid(src, stride)
+    path = conv_path(T, H, W, cin, cout, stride, src)
+    what = f"{path} strided conv {sT}x{sH}x{sW} / {stride} {cin}->{cout}"
+    M = T * H * W
+    x = U((sT * sH * sW, cin), what + ".x").to(F16)
+    w = U((cout, 27 * cin), what + ".w", 1.0 / math.sqrt(27 * cin)).to(F16)
+    b = U((cout,), what + ".b", 0.1).to(F16)
+    X, Wp = Poisoned(x, 2, 6, 40), Poisoned(w, 0, 5, 0)
+    bias = poisoned_vec(b)
+    ops_x = {"poisoned": (X.view, Wp.view, bias), "dense": (x, w, b)}
+
+    def run(sel, **kw):
+        xs, ws, bs = ops_x[sel]
+        out, T_, H_, W_ = V.conv3d_causal_strided(xs, ws, bs, sT, sH, sW, cin, cout, stride, **kw)
+        assert (T_, H_, W_) == (T, H, W)
+        return out
+
+    ref = conv_ref(x, w, b, T, H, W, cin, cout, stride=stride, src=src)
+    if M * cout * cin <= 1 << 22:      # against the oracle's own replicate padding + strided Conv3d (fp64, no rounding)
+        x5 = x.cpu().double().reshape(sT, sH, sW, cin).permute(3, 0, 1, 2)[None]
+        w5 = w.cpu().double().reshape(cout, 3, 3, 3, cin).permute(0, 4, 1, 2, 3)
+        o5 = VE.causal_conv3d_strided(x5, w5, b.cpu().double(), stride, VR.FP32)[0].permute(1, 2, 3, 0).reshape(M, cout)
+        torch.testing.assert_close(ref.y.cpu(), o5, rtol=1e-12, atol=1e-12)
+    _conv_check(V, path, what, run, ref, M, cout, False, label=path + label)
+    assert X.intact() and Wp.intact()
+    return path
+
+
+def _sid(c):
+    src, stride = c[:3], c[5]
+    return f"{conv_path(*CB.out_grid(src, stride), c[3], c[4], stride, src)}-{'x'.join(map(str, src))}-s{''.join(map(str, stride))}-{c[3]}to{c[4]}"
+
+
+@pytest.mark.parametrize("sT,sH,sW,cin,cout,stride", STRIDED_CASES, ids=[_sid(c) for c in STRIDED_CASES])
+def test_strided_conv_edges(V, sT, sH, sW, cin, cout, stride):
+    _strided_case(V, sT, sH, sW, cin, cout, stride, ".strided")
+
+
+def test_strided_cases_cover_every_path_and_stride():
+    """the table of the cases, checked: every path with a stride of 2 on each axis it admits, C5 with all seven strides, ragged tiles"""
+    seen = {}
+    for sT, sH, sW, cin, cout, stride in STRIDED_CASES:
+        T, H, W = CB.out_grid((sT, sH, sW), stride)
+        seen.setdefault(conv_path(T, H, W, cin, cout, stride, (sT, sH, sW)), []).append((stride, T * H * W))
+    assert sorted(seen) == ["C1", "C2", "C3", "C4", "C5", "C6"]
+    for path, rows in seen.items():
+        axes = (0, 1) if path in ("C3", "C4") else (0, 1, 2)
+        assert all(any(s[a] == 2 for s, _ in rows) for a in axes), path
+        assert any(m > 256 and m % 256 in ((4, 252) if path in ("C3", "C4") else (1, 255)) for _, m in rows), path
+        assert any(m == 1 for _, m in rows) or path in ("C3", "C4"), path
+    assert len({s for s, _ in seen["C5"]}) == 7
+
+
+@pytest.mark.parametrize("sT,sH,sW,cin,cout,stride,path", STRIDED_PACK_CASES,
+                         ids=[f"{c[6]}-{'x'.join(map(str, c[:3]))}-s{''.join(map(str, c[5]))}-{c[3]}to{c[4]}" for c in STRIDED_PACK_CASES])
+def test_strided_conv_packing_guard(V, sT, sH, sW, cin, cout, stride, path):
+    assert _strided_case(V, sT, sH, sW, cin, cout, stride, ".spack") == path
+
+
+@pytest.mark.parametrize("T,H,W,cin,cout", UNIT_STRIDE_CASES, ids=[f"{conv_path(*c)}-{'x'.join(map(str, c[:3]))}-{c[3]}to{c[4]}" for c in UNIT_STRIDE_CASES])
+def test_strided_entry_at_unit_stride_is_the_plain_conv(V, T, H, W, cin, cout):
+    what = f"unit stride {T}x{H}x{W} {cin}->{cout}"
+    x = U((T * H * W, cin), what + ".x").to(F16)
+    w = U((cout, 27 * cin), what + ".w", 1.0 / math.sqrt(27 * cin)).to(F16)
+    b = U((cout,), what + ".b", 0.1).to(F16)
+    got, T_, H_, W_ = V.conv3d_causal_strided(x, w, b, T, H, W, cin, cout, (1, 1, 1))
+    assert (T_, H_, W_) == (T, H, W) and same_bits(got, V.conv3d_causal(x, w, b, T, H, W, cin, cout)), what
+
+
+def _subpixel_operands(sT, sH, sW, cin, cout, up_t, what, V):
     x = U((sT * sH * sW, cin), what + ".x").to(F16)
     w = U((cout, cin, 3, 3, 3), what + ".w", 1.0 / math.sqrt(27 * cin)).to(F16)
     b = U((cout,), what + ".b", 0.1).to(F16)
-    w_sub, table, ntap = V.subpixel_weights(w, bool(up_t), "fast")
+    return (x, b) + tuple(V.subpixel_weights(w, bool(up_t), "fast"))
+
+
+def _subpixel_case(V, sT, sH, sW, cin, cout, up_t, label="SP"):
+    what = f"SP {sT}x{sH}x{sW} {cin}->{cout} up_t {up_t}"
+    x, b, w_sub, table, ntap = _subpixel_operands(sT, sH, sW, cin, cout, up_t, what, V)
     ncls = w_sub.shape[0]
     T2 = 2 * sT - 1 if up_t else sT
     M = T2 * 4 * sH * sW
@@ -379,8 +503,33 @@ def test_subpixel_edges(V, sT, sH, sW, cin, cout, up_t):
         return V.conv3d_upsampled_subpixel(xs, ws, table, ntap, bs, sT, sH, sW, cin, cout, bool(up_t), **kw)
 
     ref = subpixel_ref(x, w_sub, table, ntap, b, sT, sH, sW, cin, cout, up_t)
-    _conv_check(V, "SP", what, run, ref, M, cout, cout % 64 == 0)
+    _conv_check(V, "SP", what, run, ref, M, cout, cout % 64 == 0, label)
     assert X.intact() and Wb.intact()
+
+
+@pytest.mark.parametrize("sT,sH,sW,cin,cout,up_t", SP_CASES, ids=[f"SP-{'x'.join(map(str, c[:3]))}-{c[3]}to{c[4]}-t{c[5]}" for c in SP_CASES])
+def test_subpixel_edges(V, sT, sH, sW, cin, cout, up_t):
+    _subpixel_case(V, sT, sH, sW, cin, cout, up_t)
+
+
+@pytest.mark.parametrize("sT,sH,sW,cin,cout,up_t", SP_PACK_CASES, ids=[f"SP-{'x'.join(map(str, c[:3]))}-{c[3]}to{c[4]}-t{c[5]}" for c in SP_PACK_CASES])
+def test_subpixel_packing_guard_accepts(V, sT, sH, sW, cin, cout, up_t):
+    """sT = 254: the packed frame coordinate goes up to sT (k = kt + 1 for the odd output frames), 254 + 1 < 256"""
+    _subpixel_case(V, sT, sH, sW, cin, cout, up_t, label="SP.pack")
+
+
+@pytest.mark.parametrize("up_t", [0, 1])
+def test_subpixel_packing_guard_refuses(V, up_t):
+    """sT = 255 would need the frame coordinate 256: refused as a bad argument before anything is launched, the output keeps every bit"""
+    from hunyuanvideo_efficiency_amd._lib import HVKernelError
+    sT, cin, cout = 255, 256, 136
+    x, b, w_sub, table, ntap = _subpixel_operands(sT, 1, 1, cin, cout, up_t, f"SP refuse {up_t}", V)
+    M = (2 * sT - 1 if up_t else sT) * 4
+    o = Guarded(M, cout, F16, c0=8)
+    with pytest.raises(HVKernelError, match="bad argument"):
+        V.conv3d_upsampled_subpixel(x, w_sub, table, ntap, b, sT, 1, 1, cin, cout, bool(up_t), out=o.view)
+    torch.cuda.synchronize()
+    assert bool((o.buf == o.sent).all()), "a refused call wrote to its output"
 
 
 # ------------------------------------------------------------------------------------------------------ production shape
@@ -415,6 +564,21 @@ def test_path_table_matches_launched_kernels(ops, V):
         w = U((cout, 27 * cin), "pt.w", 0.01).to(F16)
         launches.append((conv_path(T, H, W, cin, cout),
                          lambda x=x, w=w, a=(T, H, W, cin, cout): V.conv3d_causal(x, w, None, *a)))
+    # both sides of the packing guard: T = 255 on the pipelined loop, T = 256 on the 2-stage one
+    for T, H, W, cin, cout, want in [(255, 1, 2, 128, 40, "C2"), (256, 1, 2, 128, 40, "C1")]:
+        assert conv_path(T, H, W, cin, cout) == want
+        x = U((T * H * W, cin), "pt.px").to(F16)
+        w = U((cout, 27 * cin), "pt.pw", 0.01).to(F16)
+        launches.append((want, lambda x=x, w=w, a=(T, H, W, cin, cout): V.conv3d_causal(x, w, None, *a)))
+    # one strided launch per conv path
+    strided = [((3, 6, 10), 64, 40, (2, 2, 2)), ((3, 6, 10), 128, 40, (2, 2, 2)), ((4, 3, 8), 128, 40, (2, 1, 1)), ((4, 3, 8), 128, 32, (2, 1, 1)),
+               ((3, 6, 10), 256, 136, (2, 2, 2)), ((3, 6, 10), 64, 136, (2, 2, 2))]
+    for src, cin, cout, stride in strided:
+        x = U((src[0] * src[1] * src[2], cin), "pt.sx").to(F16)
+        w = U((cout, 27 * cin), "pt.sw", 0.01).to(F16)
+        launches.append((conv_path(*CB.out_grid(src, stride), cin, cout, stride, src),
+                         lambda x=x, w=w, a=(*src, cin, cout, stride): V.conv3d_causal_strided(x, w, None, *a)))
+    assert [p for p, _ in launches[-6:]] == ["C1", "C2", "C3", "C4", "C5", "C6"]
     xs = U((2 * 3 * 5, 256), "pt.sx").to(F16)
     w_sub, table, ntap = V.subpixel_weights(U((136, 256, 3, 3, 3), "pt.sw", 0.01).to(F16), True, "fast")
     launches.append(("SP", lambda: V.conv3d_upsampled_subpixel(xs, w_sub, table, ntap, None, 2, 3, 5, 256, 136, True)))
