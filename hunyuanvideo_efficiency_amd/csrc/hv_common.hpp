@@ -50,11 +50,45 @@ __device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
     return w;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// fp16 twins of the bf16 helpers above: raw 16-bit words in memory, fp32 in registers, round to nearest even on the way back
+typedef _Float16 h16;
+__device__ __forceinline__ float h2f(uint16_t v) { return (float)__builtin_bit_cast(h16, v); }
+__device__ __forceinline__ uint16_t f2h(float f) { return __builtin_bit_cast(uint16_t, (h16)f); }
+__device__ __forceinline__ float rh(float f) { return (float)(h16)f; }
+__device__ __forceinline__ void unpack8h(const u32x4& w, float (&f)[8]) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    for (int i = 0; i < 4; ++i) {
+        f[2 * i] = h2f((uint16_t)(w[i] & 0xFFFFu));
+        f[2 * i + 1] = h2f((uint16_t)(w[i] >> 16));
+    }
+}
+__device__ __forceinline__ u32x4 pack8h(const float (&f)[8]) {
+    u32x4 w;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = (uint32_t)f2h(f[2 * i]) | ((uint32_t)f2h(f[2 * i + 1]) << 16);
+    return w;
+}
+
+// Butterfly over the 64 lanes of a wave: every lane ends with op folded over all of them, in one fixed order.
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
     return v;
 }
+struct WaveAdd {
+    template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+};
+struct WaveMax {
+    __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); }
+    __device__ __forceinline__ int operator()(int a, int b) const { return max(a, b); }
+};
+struct WaveMin {
+    __device__ __forceinline__ int operator()(int a, int b) const { return min(a, b); }
+};
+template <typename T> __device__ __forceinline__ T wave_sum(T v) { return wave_reduce(v, WaveAdd{}); }   // float, double, uint64
+template <typename T> __device__ __forceinline__ T wave_max(T v) { return wave_reduce(v, WaveMax{}); }   // float, int
+template <typename T> __device__ __forceinline__ T wave_min(T v) { return wave_reduce(v, WaveMin{}); }   // int
 
 __device__ __forceinline__ float gelu_tanh_f(float x) {
     // nn.GELU(approximate="tanh"): 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3)))

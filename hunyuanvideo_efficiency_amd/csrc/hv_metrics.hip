@@ -47,27 +47,6 @@ template <typename V, int VEC> __device__ __forceinline__ float lane_of(const V&
     else return (float)v[j];
 }
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_min_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 struct Strides {
     int64_t sc, st, sh;
 };
@@ -102,9 +81,9 @@ __global__ __launch_bounds__(kThreads) void metrics_stats_kernel(const T* __rest
         }
         sse += acc;
     }
-    sse = wave_sum_u64(sse);
-    mn1 = wave_min_i32(mn1); mx1 = wave_max_i32(mx1);
-    mn2 = wave_min_i32(mn2); mx2 = wave_max_i32(mx2);
+    sse = wave_sum(sse);
+    mn1 = wave_min(mn1); mx1 = wave_max(mx1);
+    mn2 = wave_min(mn2); mx2 = wave_max(mx2);
     __shared__ unsigned long long s_sse[kThreads / 64];
     __shared__ int s_mm[kThreads / 64][4];
     const int wave = tid >> 6;
@@ -137,9 +116,9 @@ __global__ __launch_bounds__(64) void metrics_stats_fold(const unsigned long lon
         mn1 = min(mn1, mm_part[slot * 4 + 0]); mx1 = max(mx1, mm_part[slot * 4 + 1]);
         mn2 = min(mn2, mm_part[slot * 4 + 2]); mx2 = max(mx2, mm_part[slot * 4 + 3]);
     }
-    s = wave_sum_u64(s);
-    mn1 = wave_min_i32(mn1); mx1 = wave_max_i32(mx1);
-    mn2 = wave_min_i32(mn2); mx2 = wave_max_i32(mx2);
+    s = wave_sum(s);
+    mn1 = wave_min(mn1); mx1 = wave_max(mx1);
+    mn2 = wave_min(mn2); mx2 = wave_max(mx2);
     if (l == 0) {
         sse[t] = (long long)s;
         minmax[t * 4 + 0] = mn1; minmax[t * 4 + 1] = mx1; minmax[t * 4 + 2] = mn2; minmax[t * 4 + 3] = mx2;
@@ -224,7 +203,7 @@ __global__ __launch_bounds__(kThreads) void metrics_ssim_kernel(const T* __restr
             }
         }
     }
-    sum = wave_sum_f64(sum);
+    sum = wave_sum(sum);
     if (col == 0) s_red[wave] = sum;
     __syncthreads();
     if (tid == 0) {
@@ -241,7 +220,7 @@ __global__ __launch_bounds__(64) void metrics_ssim_fold(const double* __restrict
         const double* p = ssim_part + ((int64_t)t * C + c) * tiles;
         double s = 0.0;
         for (int k = l; k < tiles; k += 64) s += p[k];
-        s = wave_sum_f64(s);
+        s = wave_sum(s);
         if (l == 0) ssim_sum[t * C + c] = s;
     }
 }

@@ -4,11 +4,50 @@
 // reshuffles (K10 gather, unpatchify, Euler step K13).  All loads/stores are 16 B per lane.
 #include "hv_common.hpp"
 #include "../../include/hv_kernels.h"
+#include <type_traits>
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm(no affine) * mul + add.   mode 0: mul = bf16(1 + scale[d]), add = shift[d]  (adaLN modulate)
 //                                      mode 1: mul = weight[d],          add = bias[d]   (affine LN)
 // One wave per row, the row lives in registers (D <= 4096, D % 8 == 0).  Two-pass mean/variance in fp32.
+// A lane owns the 8-element chunks lane, lane + 64, ... of its row: chunk slot c of a lane is chunk lane + 64 c.
+
+// row -> v (the slots behind the row's end stay unwritten); returns the lane's sum of its elements
+template <int MAXC>
+__device__ __forceinline__ float ln_load_row(const bf16_t* xr, int lane, int nchunk, float (&v)[MAXC][8]) {
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        const int ch = lane + c * 64;
+        if (ch < nchunk) {
+            unpack8(*reinterpret_cast<const u32x4*>(xr + ch * 8), v[c]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += v[c][j];
+        }
+    }
+    return s;
+}
+// the coefficients of chunk ch: m = bf16(1 + mul) (mode 0) or mul (mode 1), 1 without mul; a = add, 0 without add
+__device__ __forceinline__ void ln_load_coeffs(const bf16_t* mul, const bf16_t* add, int ch, int mode,
+                                               float (&m)[8], float (&a)[8]) {
+    if (mul) {
+        unpack8(*reinterpret_cast<const u32x4*>(mul + ch * 8), m);
+        if (mode == 0) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) m[j] = rbf(1.0f + m[j]);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) m[j] = 1.0f;
+    }
+    if (add) {
+        unpack8(*reinterpret_cast<const u32x4*>(add + ch * 8), a);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a[j] = 0.0f;
+    }
+}
+
 template <int MAXC>
 __global__ __launch_bounds__(256) void ln_mod_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ add,
                                                       const bf16_t* __restrict__ mul, bf16_t* __restrict__ out,
@@ -17,20 +56,8 @@ __global__ __launch_bounds__(256) void ln_mod_kernel(const bf16_t* __restrict__ 
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
     const int nchunk = D >> 3;
-    const bf16_t* xr = x + row * ldx;
     float v[MAXC][8];
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-        const int ch = lane + c * 64;
-        if (ch < nchunk) {
-            u32x4 w = *reinterpret_cast<const u32x4*>(xr + ch * 8);
-            unpack8(w, v[c]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) s += v[c][j];
-        }
-    }
-    const float mean = wave_sum(s) / (float)D;
+    const float mean = wave_sum(ln_load_row<MAXC>(x + row * ldx, lane, nchunk, v)) / (float)D;
     float q = 0.f;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
@@ -50,27 +77,26 @@ __global__ __launch_bounds__(256) void ln_mod_kernel(const bf16_t* __restrict__ 
         const int ch = lane + c * 64;
         if (ch < nchunk) {
             float m[8], a[8], o[8];
-            if (mul) {
-                unpack8(*reinterpret_cast<const u32x4*>(mul + ch * 8), m);
-                if (mode == 0) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) m[j] = rbf(1.0f + m[j]);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) m[j] = 1.0f;
-            }
-            if (add) {
-                unpack8(*reinterpret_cast<const u32x4*>(add + ch * 8), a);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) a[j] = 0.0f;
-            }
+            ln_load_coeffs(mul, add, ch, mode, m, a);
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = (v[c][j] - mean) * rstd * m[j] + a[j];
             *reinterpret_cast<u32x4*>(orow + ch * 8) = pack8(o);
         }
     }
+}
+
+// The row-length ladder of both LN kernels: launch(integral_constant<int, MAXC>) with the smallest MAXC whose 512 * MAXC
+// elements hold a row of D.
+template <typename Launch>
+static inline void ln_dispatch_maxc(int D, Launch launch) {
+    if (D <= 512)
+        launch(std::integral_constant<int, 1>{});
+    else if (D <= 2048)
+        launch(std::integral_constant<int, 4>{});
+    else if (D <= 3072)
+        launch(std::integral_constant<int, 6>{});
+    else
+        launch(std::integral_constant<int, 8>{});
 }
 
 extern "C" int hv_ln_modulate_bf16(const void* x, const void* shift_or_bias, const void* scale_or_weight, void* out,
@@ -80,14 +106,9 @@ extern "C" int hv_ln_modulate_bf16(const void* x, const void* shift_or_bias, con
     if (M == 0) return HV_OK;
     dim3 grid((unsigned)((M + 3) / 4)), block(256);
     const bf16_t *xp = (const bf16_t*)x, *ap = (const bf16_t*)shift_or_bias, *mp = (const bf16_t*)scale_or_weight;
-    if (D <= 512)
-        ln_mod_kernel<1><<<grid, block, 0, stream>>>(xp, ap, mp, (bf16_t*)out, M, D, ldx, ldo, eps, mode);
-    else if (D <= 2048)
-        ln_mod_kernel<4><<<grid, block, 0, stream>>>(xp, ap, mp, (bf16_t*)out, M, D, ldx, ldo, eps, mode);
-    else if (D <= 3072)
-        ln_mod_kernel<6><<<grid, block, 0, stream>>>(xp, ap, mp, (bf16_t*)out, M, D, ldx, ldo, eps, mode);
-    else
-        ln_mod_kernel<8><<<grid, block, 0, stream>>>(xp, ap, mp, (bf16_t*)out, M, D, ldx, ldo, eps, mode);
+    ln_dispatch_maxc(D, [&](auto maxc) {
+        ln_mod_kernel<decltype(maxc)::value><<<grid, block, 0, stream>>>(xp, ap, mp, (bf16_t*)out, M, D, ldx, ldo, eps, mode);
+    });
     return hv_check_launch();
 }
 
@@ -103,18 +124,22 @@ __device__ __forceinline__ uint32_t pack4_fp8(float a, float b, float c, float d
     w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
     return w;
 }
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 // Floor of a row scale: with amax < 448 * 2^-126 the quotient amax / 448 is subnormal (or zero) and its reciprocal +inf, which
 // would turn every zero of the row into 0 * inf = NaN.  At the floor 1 / s = 2^126 is finite and |x| / s <= 448 still holds.
-#define HV_FP8_MIN_ROW_SCALE 1.17549435e-38f   /* 2^-126 */
+constexpr float HV_FP8_MIN_ROW_SCALE = 1.17549435e-38f;   // 2^-126
+__device__ __forceinline__ float fp8_row_scale(float amax) {
+    return amax > 0.f ? fmaxf(amax * (1.0f / 448.0f), HV_FP8_MIN_ROW_SCALE) : 1.0f;
+}
 __device__ __forceinline__ float clamp448(float v) { return __builtin_amdgcn_fmed3f(v, -448.0f, 448.0f); }
-
-// K1 with an fp8 output: y = bf16(LN(x) * bf16(1 + scale) + shift) exactly as ln_mod_kernel mode 0 (the bf16 rounding of the
-// reference contract is kept, so the ONLY new error is the e4m3 rounding), then the per-row quantisation above.
+__device__ __forceinline__ u32x2 pack8_fp8(const float (&v)[8], float inv) {
+    u32x2 w;
+    w[0] = pack4_fp8(clamp448(v[0] * inv), clamp448(v[1] * inv), clamp448(v[2] * inv), clamp448(v[3] * inv));
+    w[1] = pack4_fp8(clamp448(v[4] * inv), clamp448(v[5] * inv), clamp448(v[6] * inv), clamp448(v[7] * inv));
+    return w;
+}
+// K1 with an fp8 output: y = bf16(LN(x) * bf16(1 + scale) + shift) from the same row statistics and coefficients as ln_mod_kernel
+// mode 0 (the bf16 rounding of the reference contract is kept, so the ONLY new error is the e4m3 rounding), then the per-row
+// quantisation above.
 template <int MAXC>
 __global__ __launch_bounds__(256) void ln_mod_fp8_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ add,
                                                           const bf16_t* __restrict__ mul, uint8_t* __restrict__ out,
@@ -124,19 +149,8 @@ __global__ __launch_bounds__(256) void ln_mod_fp8_kernel(const bf16_t* __restric
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
     const int nchunk = D >> 3;
-    const bf16_t* xr = x + row * ldx;
     float v[MAXC][8];
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-        const int ch = lane + c * 64;
-        if (ch < nchunk) {
-            unpack8(*reinterpret_cast<const u32x4*>(xr + ch * 8), v[c]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) s += v[c][j];
-        }
-    }
-    const float mean = wave_sum(s) / (float)D;
+    const float mean = wave_sum(ln_load_row<MAXC>(x + row * ldx, lane, nchunk, v)) / (float)D;
     float q = 0.f;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
@@ -156,19 +170,7 @@ __global__ __launch_bounds__(256) void ln_mod_fp8_kernel(const bf16_t* __restric
         const int ch = lane + c * 64;
         if (ch < nchunk) {
             float m[8], a[8];
-            if (mul) {
-                unpack8(*reinterpret_cast<const u32x4*>(mul + ch * 8), m);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) m[j] = rbf(1.0f + m[j]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) m[j] = 1.0f;
-            }
-            if (add) unpack8(*reinterpret_cast<const u32x4*>(add + ch * 8), a);
-            else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) a[j] = 0.0f;
-            }
+            ln_load_coeffs(mul, add, ch, 0, m, a);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 v[c][j] = rbf((v[c][j] - mean) * rstd * m[j] + a[j]);
@@ -176,20 +178,14 @@ __global__ __launch_bounds__(256) void ln_mod_fp8_kernel(const bf16_t* __restric
             }
         }
     }
-    amax = wave_max(amax);
-    const float sc = amax > 0.f ? fmaxf(amax * (1.0f / 448.0f), HV_FP8_MIN_ROW_SCALE) : 1.0f;
+    const float sc = fp8_row_scale(wave_max(amax));
     const float inv = 1.0f / sc;
     if (lane == 0) row_scale[row] = sc;
     uint8_t* orow = out + row * ldo;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
         const int ch = lane + c * 64;
-        if (ch < nchunk) {
-            u32x2 w;
-            w[0] = pack4_fp8(clamp448(v[c][0] * inv), clamp448(v[c][1] * inv), clamp448(v[c][2] * inv), clamp448(v[c][3] * inv));
-            w[1] = pack4_fp8(clamp448(v[c][4] * inv), clamp448(v[c][5] * inv), clamp448(v[c][6] * inv), clamp448(v[c][7] * inv));
-            *reinterpret_cast<u32x2*>(orow + ch * 8) = w;
-        }
+        if (ch < nchunk) *reinterpret_cast<u32x2*>(orow + ch * 8) = pack8_fp8(v[c], inv);
     }
 }
 
@@ -199,14 +195,9 @@ extern "C" int hv_ln_modulate_fp8(const void* x, const void* shift, const void* 
     if (M == 0) return HV_OK;
     dim3 grid((unsigned)((M + 3) / 4)), block(256);
     const bf16_t *xp = (const bf16_t*)x, *ap = (const bf16_t*)shift, *mp = (const bf16_t*)scale;
-    if (D <= 512)
-        ln_mod_fp8_kernel<1><<<grid, block, 0, stream>>>(xp, ap, mp, (uint8_t*)out_q, out_row_scale, M, D, ldx, ldq, eps);
-    else if (D <= 2048)
-        ln_mod_fp8_kernel<4><<<grid, block, 0, stream>>>(xp, ap, mp, (uint8_t*)out_q, out_row_scale, M, D, ldx, ldq, eps);
-    else if (D <= 3072)
-        ln_mod_fp8_kernel<6><<<grid, block, 0, stream>>>(xp, ap, mp, (uint8_t*)out_q, out_row_scale, M, D, ldx, ldq, eps);
-    else
-        ln_mod_fp8_kernel<8><<<grid, block, 0, stream>>>(xp, ap, mp, (uint8_t*)out_q, out_row_scale, M, D, ldx, ldq, eps);
+    ln_dispatch_maxc(D, [&](auto maxc) {
+        ln_mod_fp8_kernel<decltype(maxc)::value><<<grid, block, 0, stream>>>(xp, ap, mp, (uint8_t*)out_q, out_row_scale, M, D, ldx, ldq, eps);
+    });
     return hv_check_launch();
 }
 
@@ -226,18 +217,14 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
 #pragma unroll
         for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[j]));
     }
-    amax = wave_max(amax);
-    const float sc = amax > 0.f ? fmaxf(amax * (1.0f / 448.0f), HV_FP8_MIN_ROW_SCALE) : 1.0f;
+    const float sc = fp8_row_scale(wave_max(amax));
     const float inv = 1.0f / sc;
     if (lane == 0) row_scale[row] = sc;
     uint8_t* orow = out + row * ldo;
     for (int ch = lane; ch < nchunk; ch += 64) {
         float f[8];
         unpack8(*reinterpret_cast<const u32x4*>(xr + ch * 8), f);
-        u32x2 w;
-        w[0] = pack4_fp8(clamp448(f[0] * inv), clamp448(f[1] * inv), clamp448(f[2] * inv), clamp448(f[3] * inv));
-        w[1] = pack4_fp8(clamp448(f[4] * inv), clamp448(f[5] * inv), clamp448(f[6] * inv), clamp448(f[7] * inv));
-        *reinterpret_cast<u32x2*>(orow + ch * 8) = w;
+        *reinterpret_cast<u32x2*>(orow + ch * 8) = pack8_fp8(f, inv);
     }
 }
 

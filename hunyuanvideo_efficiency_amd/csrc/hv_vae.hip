@@ -5,24 +5,6 @@
 
 namespace {
 
-typedef _Float16 h16;
-__device__ __forceinline__ float h2f(uint16_t v) { return (float)__builtin_bit_cast(h16, v); }
-__device__ __forceinline__ uint16_t f2h(float f) { return __builtin_bit_cast(uint16_t, (h16)f); }
-__device__ __forceinline__ float rh(float f) { return (float)(h16)f; }
-__device__ __forceinline__ void unpack8h(const u32x4& w, float (&f)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = h2f((uint16_t)(w[i] & 0xFFFFu));
-        f[2 * i + 1] = h2f((uint16_t)(w[i] >> 16));
-    }
-}
-__device__ __forceinline__ u32x4 pack8h(const float (&f)[8]) {
-    u32x4 w;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (uint32_t)f2h(f[2 * i]) | ((uint32_t)f2h(f[2 * i + 1]) << 16);
-    return w;
-}
-
 // ---- GroupNorm pass 1: per-workgroup partial (sum, sumsq) per channel of the SHIFTED values d = x - x[0][first channel of the
 // group]: one-pass moments of x itself lose the variance to cancellation (fp32 rounding of sum x^2 ~ n 2^-24 (mean^2 + var) against
 // n var), the shift leaves |mean_d| / std of the order of one sample's distance from the mean.  256 threads = (C/8) channel-threads
@@ -225,6 +207,16 @@ __global__ __launch_bounds__(64) void gn_finalize2_kernel(const double* __restri
     gn_affine_out(mean, q / n - mean * mean, eps, g * cpg + threadIdx.x, (g + 1) * cpg, 64, w, b, affine);
 }
 
+// The normalisation of 8 channels wherever it is applied: fp32 affine, optional SiLU; the caller rounds o once to fp16.
+template <bool SILU>
+__device__ __forceinline__ void gn_affine_act8(const float (&v)[8], const float (&sc)[8], const float (&sh)[8], float (&o)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float t = v[j] * sc[j] + sh[j];
+        o[j] = SILU ? silu_f(t) : t;
+    }
+}
+
 // ---- GroupNorm pass 3: y = [silu](x*sc + sh) -> fp16.  HBM-bound (read + write of the activation): a thread owns ONE 8-channel
 // chunk for the whole launch - its 8 (scale, shift) pairs live in registers - and walks rows with a fixed 32-bit element stride;
 // a block covers 256 / (C/8) consecutive rows per step, so every wave-instruction moves whole contiguous rows (16 B per lane).
@@ -258,11 +250,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const uint16_t* __restric
         if (r0 + u * nrl >= M) break;
         float v[8], o[8];
         unpack8h(w[u], v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float t = v[j] * sc[j] + sh[j];
-            o[j] = SILU ? silu_f(t) : t;
-        }
+        gn_affine_act8<SILU>(v, sc, sh, o);
         *reinterpret_cast<u32x4*>(yp + u * ys) = pack8h(o);
     }
 }
@@ -272,7 +260,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const uint16_t* __restric
 // nine times for a 256 x 8 output tile (conv128s_narrow_kernel: 2.1 ms per 65x256x256 tile, after a 0.39 ms GroupNorm pass that
 // writes what it reads).  Here the GroupNorm affine + SiLU in front of it and the channel contraction run in ONE streaming pass
 //     planes[tap][voxel][c] = sum_ch  w[c][ch][tap] * silu(x[voxel][ch] * scale[ch] + shift[ch])        (fp32, c < 3)
-// - every activation read once, normalised in registers exactly as gn_apply_kernel does (fp32 affine, SiLU, one rounding to fp16),
+// - every activation read once, normalised in registers by the gn_affine_act8 of gn_apply_kernel (fp32 affine, SiLU, one rounding to fp16),
 // contracted by v_mfma_f32_16x16x32_f16 with the whole weight set (28 fragments) resident in registers - and a second pass sums the
 // 27 planes at the tap-shifted voxels (replicate padding in H/W, causal in T = clamped indices, the conv kernels' gather rule):
 //     out[v][c] = bias[c] + sum_tap planes[tap][shift_tap(v)][c]         in the fixed order tap = 0..26, fp32, one rounding to fp16.
@@ -326,11 +314,7 @@ __global__ __launch_bounds__(256, 2) void conv_cout4_planes_kernel(const uint16_
 #pragma unroll
                 for (int j = 0; j < 4; ++j) sc[j] = ap[0][j], sc[4 + j] = ap[1][j], sh[j] = ap[2][j], sh[4 + j] = ap[3][j];
                 unpack8h(b, v);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float t = v[j] * sc[j] + sh[j];
-                    o[j] = SILU ? silu_f(t) : t;
-                }
+                gn_affine_act8<SILU>(v, sc, sh, o);
                 b = pack8h(o);
             }
 #pragma unroll
@@ -408,8 +392,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
     } else {
         for (int c = threadIdx.x; c < valid; c += 256) m = fmaxf(m, s[c]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) redm[threadIdx.x >> 6] = m;
     __syncthreads();
     m = fmaxf(fmaxf(redm[0], redm[1]), fmaxf(redm[2], redm[3])) * scale;
@@ -517,6 +500,23 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const uint16_t* __rest
 
 inline unsigned grid_for(int64_t n) { return (unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256); }
 
+// The operands of a strided 4-D op: two stride sets and the extents (all > 0, else false); n = number of elements.
+inline bool views4(const int64_t* s0, const int64_t* s1, const int* dims, View4& v0, View4& v1, Dims4& d, int64_t& n) {
+    n = 1;
+    for (int i = 0; i < 4; ++i) {
+        if (dims[i] <= 0) return false;
+        v0.s[i] = s0[i], v1.s[i] = s1[i], d.d[i] = dims[i];
+        n *= dims[i];
+    }
+    return true;
+}
+
+// kernel<SILU> picked by the runtime flag, 256 threads
+template <typename... P, typename... A>
+inline void launch_silu(int silu, void (*k_silu)(P...), void (*k_plain)(P...), dim3 grid, hipStream_t stream, A... args) {
+    (silu ? k_silu : k_plain)<<<grid, dim3(256), 0, stream>>>(args...);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Temporal resampling of a channels-last activation [T, HW, C] (the fork's "t_ops": unet_causal_3d_blocks.py:657-672,
 // 764-783,884-907).  mode 0: replicate-pad k-1 frames in front, then average k frames with stride s (avg_pool3d (k,1,1)/(s,1,1),
@@ -611,10 +611,7 @@ extern "C" int hv_groupnorm_apply_f16(const void* x, int64_t ldx, void* y, int64
     const int64_t nblk = (M + 4 * nrl - 1) / (4 * nrl);             // four steps per block
     if (nblk > 0x7fffffff) return HV_ERR_ARG;
     const dim3 grid((unsigned)nblk);
-    if (silu)
-        gn_apply_kernel<true><<<grid, dim3(256), 0, stream>>>((const uint16_t*)x, ldx, (uint16_t*)y, ldy, M, C, affine);
-    else
-        gn_apply_kernel<false><<<grid, dim3(256), 0, stream>>>((const uint16_t*)x, ldx, (uint16_t*)y, ldy, M, C, affine);
+    launch_silu(silu, gn_apply_kernel<true>, gn_apply_kernel<false>, grid, stream, (const uint16_t*)x, ldx, (uint16_t*)y, ldy, M, C, affine);
     return hv_check_launch();
 }
 
@@ -630,10 +627,8 @@ extern "C" int hv_conv3d_cout4_f16(const void* x, int64_t ldx, const float* affi
     const int64_t ngrp = (M + 15) >> 4;
     const int64_t want = (ngrp + 3) / 4;
     const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);      // 4 waves per block, each walks 16-voxel groups grid-stride
-    if (silu)
-        conv_cout4_planes_kernel<true><<<dim3(blocks), dim3(256), 0, stream>>>((const uint16_t*)x, ldx, affine, (const u32x4*)w_frag, planes, M, Cin / 32);
-    else
-        conv_cout4_planes_kernel<false><<<dim3(blocks), dim3(256), 0, stream>>>((const uint16_t*)x, ldx, affine, (const u32x4*)w_frag, planes, M, Cin / 32);
+    launch_silu(silu, conv_cout4_planes_kernel<true>, conv_cout4_planes_kernel<false>, dim3(blocks), stream, (const uint16_t*)x, ldx, affine,
+                (const u32x4*)w_frag, planes, M, Cin / 32);
     if (int rc = hv_check_launch(); rc != HV_OK) return rc;
     const int64_t gblk = (M + 255) / 256;
     if (gblk > 0x7fffffff) return HV_ERR_ARG;
@@ -671,8 +666,9 @@ extern "C" int hv_vae_blend_f16(const void* a, const int64_t* a_strides, void* b
     if (!a || !b || !a_strides || !b_strides || !dims || axis < 0 || axis > 3 || extent <= 0 || dims[axis] > extent) return HV_ERR_ARG;
     View4 sa, sb;
     Dims4 d;
-    for (int i = 0; i < 4; ++i) { sa.s[i] = a_strides[i]; sb.s[i] = b_strides[i]; d.d[i] = dims[i]; if (dims[i] <= 0) return HV_ERR_ARG; }
-    blend_kernel<<<dim3(grid_for((int64_t)d.d[0] * d.d[1] * d.d[2] * d.d[3])), dim3(256), 0, stream>>>((const uint16_t*)a, sa, (uint16_t*)b, sb, d, axis, extent);
+    int64_t n;
+    if (!views4(a_strides, b_strides, dims, sa, sb, d, n)) return HV_ERR_ARG;
+    blend_kernel<<<dim3(grid_for(n)), dim3(256), 0, stream>>>((const uint16_t*)a, sa, (uint16_t*)b, sb, d, axis, extent);
     return hv_check_launch();
 }
 
@@ -681,8 +677,9 @@ extern "C" int hv_copy4d_16b(const void* src, const int64_t* src_strides, void* 
     if (!src || !dst || !src_strides || !dst_strides || !dims) return HV_ERR_ARG;
     View4 ss, sd;
     Dims4 d;
-    for (int i = 0; i < 4; ++i) { ss.s[i] = src_strides[i]; sd.s[i] = dst_strides[i]; d.d[i] = dims[i]; if (dims[i] <= 0) return HV_ERR_ARG; }
-    copy4d_kernel<<<dim3(grid_for((int64_t)d.d[0] * d.d[1] * d.d[2] * d.d[3])), dim3(256), 0, stream>>>((const uint16_t*)src, ss, (uint16_t*)dst, sd, d);
+    int64_t n;
+    if (!views4(src_strides, dst_strides, dims, ss, sd, d, n)) return HV_ERR_ARG;
+    copy4d_kernel<<<dim3(grid_for(n)), dim3(256), 0, stream>>>((const uint16_t*)src, ss, (uint16_t*)dst, sd, d);
     return hv_check_launch();
 }
 

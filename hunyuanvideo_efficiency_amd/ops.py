@@ -40,6 +40,14 @@ def _rows(t: torch.Tensor, name: str):
     return n, d, ld
 
 
+def _chk_mod_vectors(shift, scale, d: int):
+    """the optional shift / scale operands of the ln_modulate* kernels: contiguous bf16 [d] vectors"""
+    for t, n in ((shift, "shift"), (scale, "scale")):
+        if t is not None:
+            _chk(t, BF16, n)
+            assert t.numel() == d and t.is_contiguous(), f"{n} must be a contiguous [{d}] vector (batch 1)"
+
+
 def ln_modulate(x, shift=None, scale=None, out=None, eps: float = 1e-6, affine: bool = False):
     """mode 0: LN(x)*bf16(1+scale)+shift ; affine=True: LN(x)*scale(weight)+shift(bias)."""
     _chk(x, BF16, "x")
@@ -49,10 +57,7 @@ def ln_modulate(x, shift=None, scale=None, out=None, eps: float = 1e-6, affine: 
     _chk(out, BF16, "out")
     mo, do, ldo = _rows(out, "out")
     assert (mo, do) == (m, d)
-    for t, n in ((shift, "shift"), (scale, "scale")):
-        if t is not None:
-            _chk(t, BF16, n)
-            assert t.numel() == d and t.is_contiguous(), f"{n} must be a contiguous [{d}] vector (batch 1)"
+    _chk_mod_vectors(shift, scale, d)
     _lib.call("ln_modulate_bf16", x, shift, scale, out, m, d, ldx, ldo, eps,
                                                1 if affine else 0)
     return out
@@ -80,16 +85,12 @@ def qknorm_rope_(qkv, q_weight, k_weight, cos, sin, n_rope: int, n_heads: int, k
     return qkv
 
 
-def gemm(a, w, bias=None, out=None, act: int = ACT_NONE, n_split: int = 0, out1=None, act1: int = ACT_NONE,
-         gate=None, res=None):
-    """out = a @ w.T + bias with the fused epilogues of hv_gemm_bf16.  a:[M,K] w:[N,K] (row strides free)."""
-    _chk(a, BF16, "a"), _chk(w, BF16, "w")
-    m, k, lda = _rows(a, "a")
-    n, kw, ldw = _rows(w, "w")
-    assert k == kw, (a.shape, w.shape)
+def _gemm_epilogue(out_shape, device, m: int, n: int, n_split: int, out, out1, bias, gate, res):
+    """The epilogue operands shared by gemm and gemm_fp8: validates out / out1 (second output behind column n_split) / bias / gate /
+    res against the [m, n] product and allocates a missing `out` as out_shape + (n0,).  Returns (out, n0, ld0, ld1, ld_res)."""
     n0 = n_split if 0 < n_split < n else n
     if out is None:
-        out = torch.empty(*a.shape[:-1], n0, dtype=BF16, device=a.device)
+        out = torch.empty(*out_shape, n0, dtype=BF16, device=device)
     _chk(out, BF16, "out")
     mo, no, ld0 = _rows(out, "out")
     assert mo == m and no >= n0
@@ -107,6 +108,17 @@ def gemm(a, w, bias=None, out=None, act: int = ACT_NONE, n_split: int = 0, out1=
         _chk(res, BF16, "res")
         mr, nr, ld_res = _rows(res, "res")
         assert mr == m and nr == n
+    return out, n0, ld0, ld1, ld_res
+
+
+def gemm(a, w, bias=None, out=None, act: int = ACT_NONE, n_split: int = 0, out1=None, act1: int = ACT_NONE,
+         gate=None, res=None):
+    """out = a @ w.T + bias with the fused epilogues of hv_gemm_bf16.  a:[M,K] w:[N,K] (row strides free)."""
+    _chk(a, BF16, "a"), _chk(w, BF16, "w")
+    m, k, lda = _rows(a, "a")
+    n, kw, ldw = _rows(w, "w")
+    assert k == kw, (a.shape, w.shape)
+    out, n0, ld0, ld1, ld_res = _gemm_epilogue(a.shape[:-1], a.device, m, n, n_split, out, out1, bias, gate, res)
     _lib.call("gemm_bf16", a, lda, w, ldw, bias, m, n, k, out, ld0, act, n0,
                                         out1, ld1, act1, gate, res, ld_res)
     return out
@@ -300,10 +312,7 @@ def ln_modulate_fp8(x, shift=None, scale=None, out_q=None, out_scale=None, eps: 
     if out_scale is None:
         out_scale = torch.empty(m, dtype=torch.float32, device=x.device)
     assert out_q.dtype == FP8 and out_q.is_cuda and out_q.shape[-1] == d and out_q.stride(-1) == 1 and out_scale.numel() >= m
-    for t, n in ((shift, "shift"), (scale, "scale")):
-        if t is not None:
-            _chk(t, BF16, n)
-            assert t.numel() == d and t.is_contiguous()
+    _chk_mod_vectors(shift, scale, d)
     _lib.call("ln_modulate_fp8", x, shift, scale, out_q, out_scale, m, d, ldx, out_q.stride(-2) if out_q.dim() > 1 else d, eps)
     return out_q, out_scale
 
@@ -331,26 +340,7 @@ def gemm_fp8(a_q, a_scale, w_q, w_scale, bias=None, out=None, act: int = ACT_NON
     m, k, lda = _rows(a_q, "a_q")
     n, kw, ldw = _rows(w_q, "w_q")
     assert k == kw and a_scale.numel() >= m and w_scale.numel() == 1
-    n0 = n_split if 0 < n_split < n else n
-    if out is None:
-        out = torch.empty(m, n0, dtype=BF16, device=a_q.device)
-    _chk(out, BF16, "out")
-    mo, no, ld0 = _rows(out, "out")
-    assert mo == m and no >= n0
-    ld1 = 0
-    if n0 < n:
-        _chk(out1, BF16, "out1")
-        m1, n1, ld1 = _rows(out1, "out1")
-        assert m1 == m and n1 >= n - n0
-    for t, nm in ((bias, "bias"), (gate, "gate")):
-        if t is not None:
-            _chk(t, BF16, nm)
-            assert t.numel() == n and t.is_contiguous()
-    ld_res = 0
-    if res is not None:
-        _chk(res, BF16, "res")
-        mr, nr, ld_res = _rows(res, "res")
-        assert mr == m and nr == n
+    out, n0, ld0, ld1, ld_res = _gemm_epilogue((m,), a_q.device, m, n, n_split, out, out1, bias, gate, res)
     _lib.call("gemm_fp8", a_q, lda, a_scale, w_q, ldw, w_scale, bias, m, n, k, out, ld0, act, n0, out1, ld1, act1, gate, res, ld_res)
     return out
 
