@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""PSNR / SSIM between two folders of videos, on the GPU (the fork's evaluation/compute_metrics.py and, for a --root2 that holds one
+"""PSNR / SSIM / LPIPS between two folders of videos, on the GPU (the fork's evaluation/compute_metrics.py and, for a --root2 that holds one
 sub-folder per experiment, its compute_metrics_threads.py; the kernel needs no thread pool).
 
 Files are paired by name.  `.pt` (torch.load(weights_only=True); [C,T,H,W] or [1,C,T,H,W], values in [-1, 1] as infer.py writes
 them) and `.npy` (the same layouts, or uint8 frames [T,H,W,C] as save_videos_grid's fallback writes them) are read directly; `.mp4`
 only if imageio is importable - otherwise an .mp4 pair is an error, not a silent skip.  Scores are per frame over the common frames
-and averaged over all frames of all pairs; the result file has the reference's lines.  No LPIPS: it needs AlexNet + LPIPS weights,
-so result files carry no `LPIPS` key."""
+and averaged over all frames of all pairs; the result file has the reference's lines.  LPIPS (AlexNet, the reference's
+compute_lpips) is scored only with --lpips-alexnet PATH [--lpips-linear PATH]: the weights are user-supplied (a torchvision AlexNet
+state dict plus the LPIPS linear file, or one full LPIPS state dict), none are shipped or fetched; without them the result file has no
+`LPIPS` line.  uint8 frames (.npy, .mp4) go through the rescale=False path, so the network sees exactly those bytes."""
 import argparse
 import os
 import sys
@@ -22,11 +24,17 @@ EXTS = (".pt", ".npy", ".mp4")
 
 
 def parse_args(argv=None):
-    p = argparse.ArgumentParser(description="Compute PSNR / SSIM between two sets of videos on the GPU.")
+    p = argparse.ArgumentParser(description="Compute PSNR / SSIM (and LPIPS, given weights) between two sets of videos on the GPU.")
     p.add_argument("--root1", type=str, required=True, help="Directory of reference/original videos (.pt, .npy; .mp4 with imageio).")
     p.add_argument("--root2", type=str, required=True, help="Directory of reconstructed videos, or of one sub-folder per experiment.")
     p.add_argument("--results-dir", type=str, required=True, help="Directory to store the metric results.")
-    return p.parse_args(argv)
+    p.add_argument("--lpips-alexnet", type=str, default=None, help="score LPIPS too: a torchvision AlexNet state dict (needs --lpips-linear), "
+                                                                   "or one full LPIPS state dict (.pt / .pth / .safetensors; weights are not shipped)")
+    p.add_argument("--lpips-linear", type=str, default=None, help="the LPIPS linear layers (lin{0..4}.model.1.weight)")
+    a = p.parse_args(argv)
+    if a.lpips_linear and not a.lpips_alexnet:
+        p.error("--lpips-linear needs --lpips-alexnet")
+    return a
 
 
 def list_videos(root):
@@ -68,14 +76,14 @@ def read_video(path):
     return x, True
 
 
-def score_folders(root1, root2, results_dir, device="cuda"):
+def score_folders(root1, root2, results_dir, device="cuda", lpips=None):
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator
     names = pair_files(root1, root2)
     if not names:
         print(f"No matching video files between {root1} and {root2}.")
         return None
     print(f"Found {len(names)} matching pairs.")
-    acc = MetricsAccumulator()
+    acc = MetricsAccumulator(lpips=lpips)
     for name in names:
         v1, r1 = read_video(os.path.join(root1, name))
         v2, r2 = read_video(os.path.join(root2, name))
@@ -83,7 +91,8 @@ def score_folders(root1, root2, results_dir, device="cuda"):
             raise ValueError(f"{name}: one side holds uint8 frames and the other float video")
         dt = torch.float16 if v1.dtype == torch.float16 and v2.dtype == torch.float16 else torch.float32
         m = acc.add_video(v1.to(device, dtype=dt), v2.to(device, dtype=dt), rescale=r1)
-        print(f"{name}: PSNR {m['psnr_mean']:.4f} SSIM {m['ssim_mean']:.6f} ({len(m['psnr'])} frames)")
+        print(f"{name}: PSNR {m['psnr_mean']:.4f} SSIM {m['ssim_mean']:.6f}" + (f" LPIPS {m['lpips_mean']:.6f}" if lpips is not None else "")
+              + f" ({len(m['psnr'])} frames)")
     results = acc.result()
     path = acc.save(results_dir, root1, root2)
     print(f"Results: {results}\nSaved to {path}")
@@ -92,10 +101,14 @@ def score_folders(root1, root2, results_dir, device="cuda"):
 
 def main(argv=None):
     a = parse_args(argv)
+    lpips = None
+    if a.lpips_alexnet:
+        from hunyuanvideo_efficiency_amd.metrics import LpipsAlex
+        lpips = LpipsAlex.from_files(a.lpips_alexnet, a.lpips_linear)
     subdirs = sorted(d for d in os.listdir(a.root2) if os.path.isdir(os.path.join(a.root2, d)))
     if subdirs and not list_videos(a.root2):            # one folder per experiment: one result file each
-        return [score_folders(a.root1, os.path.join(a.root2, d), os.path.join(a.results_dir, d)) for d in subdirs]
-    return [score_folders(a.root1, a.root2, a.results_dir)]
+        return [score_folders(a.root1, os.path.join(a.root2, d), os.path.join(a.results_dir, d), lpips=lpips) for d in subdirs]
+    return [score_folders(a.root1, a.root2, a.results_dir, lpips=lpips)]
 
 
 if __name__ == "__main__":

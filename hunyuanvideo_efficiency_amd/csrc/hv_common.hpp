@@ -103,6 +103,15 @@ __device__ __forceinline__ float gelu_tanh_f(float x) {
 }
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
+// The 8-bit frame value of the scoring kernels (hv_metrics.hip, hv_lpips.hip), utils/file_utils.py:frames_uint8: x.float();
+// (x + 1.0) / 2.0 if rescale; clamp(0, 1); * 255; astype(uint8) - each step rounded to fp32 on its own (the intrinsics keep hipcc
+// from contracting the add and a multiply into one FMA).  NaN quantises to 0.
+__device__ __forceinline__ uint32_t quantise(float x, int rescale) {
+    if (rescale) x = __fmul_rn(__fadd_rn(x, 1.0f), 0.5f);
+    x = fminf(fmaxf(x, 0.0f), 1.0f);
+    return (uint32_t)(int)__fmul_rn(x, 255.0f);
+}
+
 // Raising a kernel's dynamic-LDS limit is a per-DEVICE attribute: one process may drive several GPUs, so the "already done"
 // flag is kept per device ordinal (hipGetDevice is a thread-local read, no driver call).
 struct HvPerDeviceOnce { bool done[64] = {}; };

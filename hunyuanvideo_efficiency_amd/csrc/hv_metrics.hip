@@ -26,14 +26,6 @@ constexpr int kInH = kTileH + kHalo;         // 38
 constexpr int kPxPitch = 72;                 // uint16 per LDS pixel row
 constexpr int kRowsPerWave = kTileH / (kThreads / 64);   // 8 output rows per wave in the vertical pass
 
-// frames_uint8: x.float(); (x + 1.0) / 2.0 if rescale; clamp(0, 1); * 255; astype(uint8) - each step rounded to fp32 on its own
-// (the intrinsics keep hipcc from contracting the add and a multiply into one FMA).  NaN quantises to 0.
-__device__ __forceinline__ uint32_t quantise(float x, int rescale) {
-    if (rescale) x = __fmul_rn(__fadd_rn(x, 1.0f), 0.5f);
-    x = fminf(fmaxf(x, 0.0f), 1.0f);
-    return (uint32_t)(int)__fmul_rn(x, 255.0f);
-}
-
 template <typename T> __device__ __forceinline__ float load1(const T* p) { return (float)*p; }
 
 template <typename T, int VEC> struct Vec;

@@ -1,11 +1,17 @@
-"""PSNR / SSIM of a reconstruction against its input, scored on the device (csrc/hv_metrics.hip).
+"""PSNR / SSIM / LPIPS of a reconstruction against its input, scored on the device (csrc/hv_metrics.hip, csrc/hv_lpips.hip).
 
 The fork's study scores reconstructions with evaluation/compute_metrics.py: per frame `compute_psnr` / `compute_ssim` (skimage) on
 the 8-bit frames of an mp4 that `save_videos_grid(..., rescale=True)` wrote, averaged over all frames of an experiment.  Here the
 same per-frame numbers come from one kernel call on the fp16 tensors still on the card: quantisation to 8 bits in registers (bit for
 bit `utils.file_utils.frames_uint8`), exact integer moments, and the host rules of the reference on top (`scores_from_stats`).
-What it is not: there is no video codec in between (the reference's frames went through libx264), and there is no LPIPS (it needs
-AlexNet + LPIPS weights; result files carry no `LPIPS` key).  CPU tensors are refused like everywhere else in the package."""
+LPIPS (`LpipsAlex`, `lpips_video`) restates the reference's lpips.LPIPS(net="alex") on the same 8-bit frames in fp32: AlexNet's five
+conv layers as fp32-MFMA implicit GEMMs, the first one reading the videos themselves.  Its weights are USER-SUPPLIED (a torchvision
+AlexNet state dict plus the LPIPS linear file, or one full LPIPS state dict); none ship with the package, and without them nothing
+changes: result files carry an `LPIPS` line only when LPIPS values were added.  `LpipsAlex.synthetic` gives deterministic weights for
+tests and timing, whose scores are not comparable with published LPIPS.  Parity rests on this restatement (tests/lpips_ref.py):
+neither torchvision nor the `lpips` package is part of this environment.
+What it is not: there is no video codec in between (the reference's frames went through libx264).  CPU tensors are refused like
+everywhere else in the package."""
 from __future__ import annotations
 
 import math
@@ -84,15 +90,18 @@ def video_stats(ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True) -> d
     return {"sse": sse, "minmax": minmax, "ssim_sum": ssim_sum, "shape": (B, C, T, H, W)}
 
 
-def video_metrics(ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True) -> dict:
+def video_metrics(ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True, lpips: "LpipsAlex" = None) -> dict:
     """PSNR / SSIM per frame of `rec` against `ref` ([C,T,H,W] or [B,C,T,H,W] GPU tensors, fp16 or fp32, values in [-1, 1] with
     rescale=True, [0, 1] without).  One host synchronisation.  Returns float64 numpy arrays `psnr`, `ssim` ([T], or [B,T] for a batch),
-    their means `psnr_mean`, `ssim_mean`, and the raw integers `sse`, `minmax` the scores were formed from."""
+    their means `psnr_mean`, `ssim_mean`, and the raw integers `sse`, `minmax` the scores were formed from.  With `lpips` (an
+    LpipsAlex) also `lpips` (per frame) and `lpips_mean`."""
     batched = ref.dim() == 5
     st = video_stats(ref, rec, rescale)
     B, C, T, H, W = st["shape"]
+    if lpips is not None:
+        st["lpips_sums"], lp_pixels = _lpips_enqueue(ref, rec, lpips, rescale, None)
     host = {}
-    for k in ("sse", "minmax", "ssim_sum"):
+    for k in ("sse", "minmax", "ssim_sum") + (("lpips_sums",) if lpips is not None else ()):
         host[k] = torch.empty(st[k].shape, dtype=st[k].dtype, pin_memory=True)
         host[k].copy_(st[k], non_blocking=True)
     torch.cuda.current_stream(ref.device).synchronize()
@@ -103,8 +112,243 @@ def video_metrics(ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True) ->
         psnr[b], ssim[b] = scores_from_stats(sse[b], minmax[b], ssim_sum[b], C, H, W)
     if not batched:
         psnr, ssim, sse, minmax, ssim_sum = psnr[0], ssim[0], sse[0], minmax[0], ssim_sum[0]
-    return {"psnr": psnr, "ssim": ssim, "psnr_mean": float(psnr.mean()), "ssim_mean": float(ssim.mean()),
-            "sse": sse, "minmax": minmax, "ssim_sum": ssim_sum}
+    out = {"psnr": psnr, "ssim": ssim, "psnr_mean": float(psnr.mean()), "ssim_mean": float(ssim.mean()),
+           "sse": sse, "minmax": minmax, "ssim_sum": ssim_sum}
+    if lpips is not None:
+        lp = lpips_from_sums(host["lpips_sums"].numpy(), lp_pixels)[0]
+        out["lpips"] = lp if batched else lp[0]
+        out["lpips_mean"] = float(lp.mean())
+    return out
+
+
+# ---- LPIPS (AlexNet) ------------------------------------------------------------------------------------------------------------------
+# torchvision alexnet features[0:12] as lpips/pretrained_networks.py:56-94 slices it: (features index, Cin, Cout, kernel, stride, pad);
+# a maxpool 3/2 follows taps 1 and 2, the trailing one is unused
+LPIPS_CONVS = ((0, 3, 64, 11, 4, 2), (3, 64, 192, 5, 1, 2), (6, 192, 384, 3, 1, 1), (8, 384, 256, 3, 1, 1), (10, 256, 256, 3, 1, 1))
+LPIPS_CHNS = tuple(c[2] for c in LPIPS_CONVS)
+LPIPS_MIN_SIZE = 31          # the smallest input whose tap 3-5 maps are 1 x 1
+_LPIPS_CHUNK_BYTES = 1 << 29   # default bound of the two feature buffers together
+
+
+def lpips_lut() -> torch.Tensor:
+    """float32 [3, 256]: the network input of 8-bit value q in channel c, with exactly the reference's operations -
+    compute_metrics.py:44-60 `torch.from_numpy(img / 255.0).float() * 2 - 1` (the division in float64, the rest in fp32), then the
+    ScalingLayer `(x - shift) / scale` (lpips.py:147-154)."""
+    q = torch.arange(256, dtype=torch.float64)
+    x = (q / 255.0).float() * 2 - 1
+    shift = torch.Tensor([-.030, -.088, -.188])[:, None]
+    scale = torch.Tensor([.458, .448, .450])[:, None]
+    return (x[None, :] - shift) / scale
+
+
+def lpips_map_sizes(H: int, W: int):
+    """[(h, w)] of the five taps for an H x W input"""
+    h1, w1 = (H - 7) // 4 + 1, (W - 7) // 4 + 1
+    h2, w2 = (h1 - 3) // 2 + 1, (w1 - 3) // 2 + 1
+    h3, w3 = (h2 - 3) // 2 + 1, (w2 - 3) // 2 + 1
+    return [(h1, w1), (h2, w2), (h3, w3), (h3, w3), (h3, w3)]
+
+
+def lpips_buffer_plan(H: int, W: int):
+    """-> (pixels of the five taps, floats per image of a ping-pong feature buffer - the largest of the taps and the two pooled maps,
+    default frames per chunk: as many as keep the two buffers, 2 images per frame each, within _LPIPS_CHUNK_BYTES)"""
+    pixels = [h * w for h, w in lpips_map_sizes(H, W)]
+    per_image = max(max(p * c for p, c in zip(pixels, LPIPS_CHNS)), pixels[1] * LPIPS_CHNS[0], pixels[2] * LPIPS_CHNS[1])
+    return pixels, per_image, max(1, _LPIPS_CHUNK_BYTES // (2 * 2 * per_image * 4))
+
+
+def lpips_pack_conv(w: torch.Tensor, first: bool) -> torch.Tensor:
+    """torch [Cout, Cin, k, k] -> the kernels' k-major [Kpad, Cout]: first layer k = (c * 11 + ky) * 11 + kx with zero rows up to 384,
+    the others k = (ky * ksize + kx) * Cin + ci"""
+    co = w.shape[0]
+    if first:
+        out = torch.zeros(384, co, dtype=torch.float32)
+        out[:363] = w.reshape(co, 363).T
+        return out
+    return w.permute(2, 3, 1, 0).reshape(-1, co).contiguous()
+
+
+class LpipsAlex:
+    """Weights of lpips.LPIPS(net="alex", version="0.1"): five conv layers (torch layout, fp32) and five non-negative `lin` vectors.
+    Built on the host; the packed device copies are made on first use per device."""
+
+    def __init__(self, convs, lins, label: str = "user"):
+        if len(convs) != 5 or len(lins) != 5:
+            raise ValueError("LpipsAlex needs 5 conv layers and 5 lin vectors")
+        self.convs, self.lins, self.label = [], [], label
+        for i, ((w, b), lin, (_, ci, co, k, _, _)) in enumerate(zip(convs, lins, LPIPS_CONVS)):
+            w, b, lin = w.detach().float().cpu(), b.detach().float().cpu(), lin.detach().float().cpu().reshape(-1)
+            if tuple(w.shape) != (co, ci, k, k) or tuple(b.shape) != (co,) or lin.numel() != co:
+                raise ValueError(f"LPIPS layer {i + 1}: expected weight {(co, ci, k, k)}, bias {(co,)}, lin {co} values; got "
+                                 f"{tuple(w.shape)}, {tuple(b.shape)}, {lin.numel()}")
+            self.convs.append((w.contiguous(), b.contiguous()))
+            self.lins.append(lin.contiguous())
+        self._dev = {}
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, linear_sd: dict = None, label: str = "user") -> "LpipsAlex":
+        """`sd`: a torchvision AlexNet state dict (features.{0,3,6,8,10}.{weight,bias}; other keys ignored) with the LPIPS linear
+        layers in `linear_sd` (lin{0..4}.model.1.weight, [1,C,1,1]) - or one full LPIPS state dict (net.slice{1..5}.{0,3,6,8,10}.* and
+        lin*) on its own."""
+        merged = dict(sd)
+        if linear_sd is not None:
+            merged.update(linear_sd)
+        convs, lins, missing = [], [], []
+        for i, (idx, *_rest) in enumerate(LPIPS_CONVS):
+            names = [(f"features.{idx}.weight", f"features.{idx}.bias"), (f"net.slice{i + 1}.{idx}.weight", f"net.slice{i + 1}.{idx}.bias")]
+            got = [n for n in names if n[0] in merged and n[1] in merged]
+            if got:
+                convs.append((merged[got[0][0]], merged[got[0][1]]))
+            else:
+                missing.append(f"features.{idx}.{{weight,bias}} (or net.slice{i + 1}.{idx}.*)")
+            if f"lin{i}.model.1.weight" in merged:
+                lins.append(merged[f"lin{i}.model.1.weight"])
+            else:
+                missing.append(f"lin{i}.model.1.weight")
+        if missing:
+            raise ValueError("LPIPS weights are incomplete, missing: " + ", ".join(missing))
+        return cls(convs, lins, label)
+
+    @classmethod
+    def from_files(cls, alexnet_path, linear_path=None) -> "LpipsAlex":
+        """Tensor files read without executing anything from them (checkpoint.read_tensors: .pt / .pth with weights_only, .safetensors)."""
+        from .checkpoint import read_tensors
+        return cls.from_state_dict(read_tensors(alexnet_path), read_tensors(linear_path) if linear_path else None)
+
+    @classmethod
+    def synthetic(cls, seed: int = 0) -> "LpipsAlex":
+        """Deterministic stand-in weights: conv hashed_uniform * sqrt(6 / fan_in), bias 0.1 * hashed_uniform, lin 0.5 * |hashed_uniform|.
+        Scores under them are NOT comparable with published LPIPS."""
+        from .synthetic import hashed_uniform
+        convs, lins = [], []
+        for i, (_, ci, co, k, _, _) in enumerate(LPIPS_CONVS):
+            convs.append((hashed_uniform((co, ci, k, k), f"lpips.conv{i}.weight", seed) * math.sqrt(6.0 / (ci * k * k)),
+                          0.1 * hashed_uniform((co,), f"lpips.conv{i}.bias", seed)))
+            lins.append(0.5 * hashed_uniform((co,), f"lpips.lin{i}", seed).abs())
+        return cls(convs, lins, label="synthetic")
+
+    def on(self, device) -> dict:
+        """{"w": [5 packed], "b": [5], "lin": [5], "lut": [3,256]} on `device`"""
+        device = torch.device(device)
+        if device not in self._dev:
+            self._dev[device] = {"w": [lpips_pack_conv(w, i == 0).to(device) for i, (w, _) in enumerate(self.convs)],
+                                 "b": [b.to(device) for _, b in self.convs], "lin": [v.to(device) for v in self.lins],
+                                 "lut": lpips_lut().contiguous().to(device)}
+        return self._dev[device]
+
+
+def _lpips_chunk(a, r, wts, rescale, Tc, H, W, bufs, ws, out):
+    """the launches of frames [0, Tc) of one video pair; out [Tc, 5] float64 layer sums"""
+    N = 2 * Tc
+    sizes = lpips_map_sizes(H, W)
+    src, dst = bufs
+
+    def dist(layer, f):
+        h, w = sizes[layer]
+        _lib.call("lpips_distance_f32", f, wts["lin"][layer], Tc, h * w, LPIPS_CHNS[layer], layer, out, ws, ws.numel())
+
+    _lib.call("lpips_conv1_f32", a, a.stride(0), a.stride(1), a.stride(2), r, r.stride(0), r.stride(1), r.stride(2), _DTYPES[a.dtype],
+              Tc, H, W, 1 if rescale else 0, wts["lut"], wts["w"][0], wts["b"][0], src)
+    dist(0, src)
+    for layer in range(1, 5):
+        _, ci, co, k, _, pad = LPIPS_CONVS[layer]
+        h, w = sizes[layer]
+        if layer <= 2:                        # taps 1 and 2 are pooled before the next conv
+            ph, pw = sizes[layer - 1]
+            _lib.call("lpips_maxpool_f32", src, dst, N, ph, pw, ci)
+            src, dst = dst, src
+        _lib.call("lpips_conv2d_f32", src, wts["w"][layer], wts["b"][layer], dst, N, h, w, ci, co, k, pad)
+        src, dst = dst, src
+        dist(layer, src)
+
+
+def _lpips_enqueue(ref, rec, model, rescale, frames_per_chunk):
+    """-> (device float64 [B, T, 5] layer sums, pixel counts of the five taps); nothing is synchronised"""
+    if not isinstance(model, LpipsAlex):
+        raise TypeError(f"lpips: expected an LpipsAlex, got {type(model).__name__}")
+    _check_video(ref, "ref"), _check_video(rec, "rec")
+    if ref.dim() == 4:
+        ref = ref[None]
+    if rec.dim() == 4:
+        rec = rec[None]
+    if ref.dtype != rec.dtype:
+        raise _lib.HVKernelError(f"ref and rec must have one dtype, got {ref.dtype} and {rec.dtype}")
+    if ref.device != rec.device:
+        raise _lib.HVKernelError(f"ref and rec are on different devices: {ref.device}, {rec.device}")
+    B, C, _, H, W = ref.shape
+    if (rec.shape[0], rec.shape[1], rec.shape[3], rec.shape[4]) != (B, C, H, W):
+        raise _lib.HVKernelError(f"ref {tuple(ref.shape)} and rec {tuple(rec.shape)} differ in more than the frame count")
+    if C != 3:
+        raise _lib.HVKernelError(f"LPIPS reads RGB videos, got C = {C}")
+    if H < LPIPS_MIN_SIZE or W < LPIPS_MIN_SIZE:
+        raise _lib.HVKernelError(f"LPIPS (AlexNet) needs H, W >= {LPIPS_MIN_SIZE}, got {H} x {W}")
+    T = min(ref.shape[2], rec.shape[2])
+    dev = ref.device
+    pixels, per_image, default_chunk = lpips_buffer_plan(H, W)
+    Tc = max(1, min(T, int(default_chunk if frames_per_chunk is None else frames_per_chunk)))
+    wts = model.on(dev)
+    bufs = [torch.empty(2 * Tc * per_image, dtype=torch.float32, device=dev) for _ in range(2)]
+    ws = torch.empty(max(_lib.host("lpips_distance_workspace_bytes", Tc, pixels[0]), 16), dtype=torch.uint8, device=dev)
+    out = torch.empty(B, T, 5, dtype=torch.float64, device=dev)
+    for b in range(B):                        # one stream: each launch reuses the buffers after the launches before it
+        for t0 in range(0, T, Tc):
+            n = min(Tc, T - t0)
+            _lpips_chunk(ref[b][:, t0:t0 + n], rec[b][:, t0:t0 + n], wts, rescale, n, H, W, bufs, ws, out[b, t0:t0 + n])
+    return out, pixels
+
+
+def lpips_from_sums(sums, pixels):
+    """layer sums [..., 5] (numpy float64) -> (LPIPS [...], per-layer values [..., 5]): spatial_average and the sum over taps
+    (lpips.py:130,137-139)"""
+    layers = np.asarray(sums, dtype=np.float64) / np.asarray(pixels, dtype=np.float64)
+    return layers.sum(axis=-1), layers
+
+
+def lpips_video(ref: torch.Tensor, rec: torch.Tensor, model: LpipsAlex, rescale: bool = True, frames_per_chunk: int = None,
+                return_layers: bool = False):
+    """LPIPS (AlexNet) per frame of `rec` against `ref`, under the input rules of `video_stats` (GPU only, fp16 / fp32, C = 3, the
+    first min(T_ref, T_rec) frames, W contiguous, strided views allowed; H, W >= 31).  Frames go through the network `frames_per_chunk`
+    at a time (default: as many as keep the two feature buffers within 512 MiB), all on the current stream, with one host
+    synchronisation at the end; a frame's value does not depend on the chunking.  Returns float64 [T] ([B,T] for a batch); with
+    return_layers also the per-tap values [T,5]."""
+    batched = ref.dim() == 5 if isinstance(ref, torch.Tensor) else False
+    sums, pixels = _lpips_enqueue(ref, rec, model, rescale, frames_per_chunk)
+    host = torch.empty(sums.shape, dtype=sums.dtype, pin_memory=True)
+    host.copy_(sums, non_blocking=True)
+    torch.cuda.current_stream(sums.device).synchronize()
+    total, layers = lpips_from_sums(host.numpy().copy(), pixels)
+    if not batched:
+        total, layers = total[0], layers[0]
+    return (total, layers) if return_layers else total
+
+
+def add_lpips_arguments(parser, synthetic: bool = False):
+    """--lpips-alexnet PATH [--lpips-linear PATH] (and --lpips-synthetic for the tools that have a synthetic-weight mode)"""
+    parser.add_argument("--lpips-alexnet", type=str, default=None, help="score LPIPS too: a torchvision AlexNet state dict (needs "
+                        "--lpips-linear), or one full LPIPS state dict (.pt / .pth / .safetensors; weights are not shipped)")
+    parser.add_argument("--lpips-linear", type=str, default=None, help="the LPIPS linear layers (lin{0..4}.model.1.weight), e.g. lpips' weights/v0.1/alex.pth")
+    if synthetic:
+        parser.add_argument("--lpips-synthetic", action="store_true", help="score LPIPS under deterministic synthetic weights: exercises the "
+                            "kernels; the value is NOT comparable with published LPIPS")
+
+
+def lpips_from_args(args, parser=None):
+    """the LpipsAlex the flags of add_lpips_arguments ask for, or None"""
+    def fail(msg):
+        if parser is not None:
+            parser.error(msg)
+        raise ValueError(msg)
+    synthetic = bool(getattr(args, "lpips_synthetic", False))
+    if args.lpips_linear and not args.lpips_alexnet:
+        fail("--lpips-linear needs --lpips-alexnet")
+    if synthetic and args.lpips_alexnet:
+        fail("--lpips-synthetic and --lpips-alexnet exclude each other")
+    if synthetic:
+        print("LPIPS: synthetic weights - the LPIPS value is not comparable with published LPIPS")
+        return LpipsAlex.synthetic(0)
+    if args.lpips_alexnet:
+        return LpipsAlex.from_files(args.lpips_alexnet, args.lpips_linear)
+    return None
 
 
 def save_results(results: dict, root1: str, root2: str, results_dir: str, timestamp: str = None) -> str:
@@ -125,22 +369,28 @@ def save_results(results: dict, root1: str, root2: str, results_dir: str, timest
 
 class MetricsAccumulator:
     """Per-frame scores of many videos; the experiment's number is the mean over all FRAMES (compute_metrics.py:150-154), so a long
-    video weighs more than a short one."""
+    video weighs more than a short one.  `lpips` (an LpipsAlex): add_video scores LPIPS too (compute_metrics.py:142-146,153-154)."""
 
-    def __init__(self):
-        self.psnr, self.ssim = [], []
+    def __init__(self, lpips: "LpipsAlex" = None):
+        self.psnr, self.ssim, self.lpips = [], [], []
+        self.lpips_model = lpips
 
-    def add(self, psnr, ssim):
-        """per-frame arrays of one video (or a [B,T] batch), e.g. video_metrics(...)["psnr"], ["ssim"]"""
+    def add(self, psnr, ssim, lpips=None):
+        """per-frame arrays of one video (or a [B,T] batch), e.g. video_metrics(...)["psnr"], ["ssim"] (and ["lpips"])"""
         psnr, ssim = np.asarray(psnr, dtype=np.float64).ravel(), np.asarray(ssim, dtype=np.float64).ravel()
         if psnr.shape != ssim.shape:
             raise ValueError(f"psnr has {psnr.size} frames, ssim {ssim.size}")
+        if lpips is not None:
+            lpips = np.asarray(lpips, dtype=np.float64).ravel()
+            if lpips.shape != psnr.shape:
+                raise ValueError(f"psnr has {psnr.size} frames, lpips {lpips.size}")
+            self.lpips.extend(lpips.tolist())
         self.psnr.extend(psnr.tolist())
         self.ssim.extend(ssim.tolist())
 
     def add_video(self, ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True) -> dict:
-        m = video_metrics(ref, rec, rescale)
-        self.add(m["psnr"], m["ssim"])
+        m = video_metrics(ref, rec, rescale, lpips=self.lpips_model)
+        self.add(m["psnr"], m["ssim"], m.get("lpips"))
         return m
 
     @property
@@ -148,11 +398,14 @@ class MetricsAccumulator:
         return len(self.psnr)
 
     def result(self) -> dict:
-        """{"PSNR": ..., "SSIM": ...}; empty when nothing was added (the reference writes no key then)."""
+        """{"PSNR": ..., "SSIM": ...} and, only if LPIPS values were added, "LPIPS"; empty when nothing was added (the reference
+        writes no key then)."""
         out = {}
         if self.psnr:
             out["PSNR"] = sum(self.psnr) / len(self.psnr)
             out["SSIM"] = sum(self.ssim) / len(self.ssim)
+        if self.lpips:
+            out["LPIPS"] = sum(self.lpips) / len(self.lpips)
         return out
 
     def save(self, results_dir: str, root1: str, root2: str, timestamp: str = None) -> str:

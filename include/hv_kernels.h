@@ -317,6 +317,41 @@ int hv_video_metrics(const void* a, int64_t a_sc, int64_t a_st, int64_t a_sh, co
                      void* ssim_sum, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 int64_t hv_video_metrics_workspace_bytes(int C, int T, int H, int W);
 
+/* LPIPS, AlexNet trunk (the fork's evaluation/compute_metrics.py:43-62,116,142-146 calling lpips.LPIPS(net="alex"):
+ * rebuttal/common_metrics_on_video_quality/lpips/lpips.py:112-144,147-167, lpips/__init__.py:13-15, lpips/pretrained_networks.py:56-94),
+ * one entry point per kernel; every step is fp32 as in the reference, the convolutions run on the fp32-input MFMA (each output element
+ * one k-ordered fmaf chain).  Features are channels-last fp32 [image][h][w][C]; the 2T images of a call are the T frames of the first
+ * video followed by the T frames of the second.  Conv weights are k-major [Kpad][Cout] (Kpad = K rounded up to 32, zero rows behind K),
+ * 16-byte aligned.
+ *
+ * First layer (pretrained_networks.py:66-67,78-80 slice1 = Conv2d(3, 64, 11, 4, 2) + ReLU on the ScalingLayer's output, lpips.py:118,
+ * 147-154, and the input scaling of compute_metrics.py:44-60): reads the two videos a, b [3,T,H,W] as hv_video_metrics does (dtype,
+ * element strides, rescale, the same 8-bit quantiser) and feeds the conv lut[c][q], a host-built float [3][256] holding
+ * ((float32(q / 255.0) * 2 - 1) - shift[c]) / scale[c]; padding is zero in that scaled domain.  k = (c * 11 + ky) * 11 + kx, K = 363
+ * (w is [384][64]).  y: [2T][(H - 7) / 4 + 1][(W - 7) / 4 + 1][64].  H or W < 31 (the smallest input with a tap-5 pixel) is HV_ERR_ARG. */
+int hv_lpips_conv1_f32(const void* a, int64_t a_sc, int64_t a_st, int64_t a_sh, const void* b, int64_t b_sc, int64_t b_st,
+                       int64_t b_sh, int dtype, int T, int H, int W, int rescale, const float* lut, const float* w,
+                       const float* bias, float* y, hipStream_t stream);
+
+/* Layers 2-5 (pretrained_networks.py:68-77,82-90: Conv2d(64, 192, 5, padding=2), Conv2d(192, 384, 3, padding=1), Conv2d(384, 256, 3,
+ * padding=1), Conv2d(256, 256, 3, padding=1), each + ReLU): y[N][OH][OW][Cout] = relu(conv(x[N][H][W][Cin], stride 1, zero padding
+ * `pad`) + bias), OH = H + 2 pad - ksize + 1.  k = (ky * ksize + kx) * Cin + ci.  Cin % 32 == 0, Cout % 64 == 0, pad < ksize <= 11. */
+int hv_lpips_conv2d_f32(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                        int ksize, int pad, hipStream_t stream);
+
+/* MaxPool2d(kernel_size=3, stride=2) between taps 1-2 and 2-3 (torchvision alexnet features[2], [5]; pretrained_networks.py:66-71):
+ * x [N][H][W][C] -> y [N][(H - 3) / 2 + 1][(W - 3) / 2 + 1][C], C % 4 == 0, H, W >= 3. */
+int hv_lpips_maxpool_f32(const float* x, float* y, int N, int H, int W, int C, hipStream_t stream);
+
+/* One tap's distance (lpips.py:122-130 with lpips/__init__.py:13-15 normalize_tensor and the NetLinLayer 1x1 conv of lpips.py:157-167):
+ * f [2T][P][C] (P pixels), lin [C]; out[t * 5 + layer] = sum over pixels of sum_c lin[c] (f0 / (sqrt(sum f0^2) + 1e-10) - f1 / (...))^2
+ * in fp64, frame t comparing image t with image T + t (the caller divides by P: spatial_average, and adds the five taps).  C <= 384.
+ * Workgroup partials go to `workspace` (>= hv_lpips_distance_workspace_bytes(T, P) bytes, 8-byte aligned) and are folded in a fixed
+ * order: no atomics, run-to-run identical, and a frame's bits do not depend on T. */
+int hv_lpips_distance_f32(const float* f, const float* lin, int T, int64_t P, int C, int layer, double* out, void* workspace,
+                          int64_t workspace_bytes, hipStream_t stream);
+int64_t hv_lpips_distance_workspace_bytes(int T, int64_t P);
+
 #ifdef __cplusplus
 }
 #endif

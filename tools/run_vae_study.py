@@ -2,12 +2,14 @@
 """The VAE efficiency study in one process: enumerate temporal-op configurations (dynamic_enumeration.py), and for each one build
 the VAE under it, reconstruct every video of --tensor-dir and score it on the GPU (PSNR / SSIM per frame, nothing copied to the host
 or written per video: infer.py --score --no-save).  One line per configuration is appended to <output-dir>/study.jsonl:
-{"config", "PSNR", "SSIM", "frames", "compression": T_latent / T_in} - or {"config", "refused": message} for a configuration the
+{"config", "PSNR", "SSIM", ("LPIPS" with --lpips-alexnet / --lpips-synthetic,) "frames", "compression": T_latent / T_in} - or {"config", "refused": message} for a configuration the
 VAE refuses (a ValueError of its list-length checks, NotImplementedError).  Configurations run one after another on one GPU: the
 fork's shell drivers' background batches over several cards are not reproduced.
 
   python tools/run_vae_study.py --tensor-dir D --output-dir O [--base-config t_ops_config.json] [--mode pool] [--limit N] [--reduced]
-  python tools/run_vae_study.py --tensor-dir D --output-dir O --config-dir DIR_OF_JSONS"""
+  python tools/run_vae_study.py --tensor-dir D --output-dir O --config-dir DIR_OF_JSONS
+  ... --lpips-alexnet ALEXNET.pth --lpips-linear ALEX_LIN.pth   (user-supplied weights; --lpips-synthetic: stand-in weights, the
+                                                                 record then carries "lpips_weights": "synthetic")"""
 import argparse
 import json
 import os
@@ -33,13 +35,13 @@ def build_vae(config_json, vae_path, reduced, device):
     return vae
 
 
-def run_config(config_json, dataset, vae_path, reduced, device, max_files=None):
+def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, lpips=None):
     """-> the study.jsonl record of one configuration"""
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator
     rec = {"config": os.path.basename(config_json)}
     try:
         vae = build_vae(config_json, vae_path, reduced, device)
-        acc = MetricsAccumulator()
+        acc = MetricsAccumulator(lpips=lpips)
         t_in = t_lat = 0
         n = len(dataset) if max_files is None else min(len(dataset), max_files)
         for idx in range(n):
@@ -52,6 +54,8 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None):
             t_in += video.shape[2]
             t_lat += z.shape[2]
         rec.update(acc.result())
+        if lpips is not None and lpips.label == "synthetic":
+            rec["lpips_weights"] = "synthetic"          # not comparable with published LPIPS
         rec["frames"] = acc.frames
         rec["compression"] = t_lat / t_in if t_in else None
     except (ValueError, NotImplementedError) as e:
@@ -64,7 +68,7 @@ def _exp_order(name):
     return (int(m.group(1)) if m else 0, name)
 
 
-def main(argv=None):
+def parse_args(argv=None):
     p = argparse.ArgumentParser(description="VAE temporal-op study: enumerate, reconstruct and score on one GPU.")
     p.add_argument("--tensor-dir", required=True, help="input .pt video tensors [C,T,H,W]")
     p.add_argument("--output-dir", required=True, help="study.jsonl and the enumerated configurations go here")
@@ -75,9 +79,22 @@ def main(argv=None):
     p.add_argument("--max-files", type=int, default=None)
     p.add_argument("--vae-path", default=None, help="VAE checkpoint directory; default: synthetic weights")
     p.add_argument("--reduced", action="store_true", help="synthetic-weight mode only: reduced channel widths")
+    from hunyuanvideo_efficiency_amd.metrics import add_lpips_arguments
+    add_lpips_arguments(p, synthetic=True)
     a = p.parse_args(argv)
     if (a.base_config is None) == (a.config_dir is None):
         p.error("give exactly one of --base-config (enumerate) or --config-dir (ready-made configurations)")
+    if a.lpips_linear and not a.lpips_alexnet:
+        p.error("--lpips-linear needs --lpips-alexnet")
+    if a.lpips_synthetic and a.lpips_alexnet:
+        p.error("--lpips-synthetic and --lpips-alexnet exclude each other")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    from hunyuanvideo_efficiency_amd.metrics import lpips_from_args
+    lpips = lpips_from_args(a)
     import dynamic_enumeration
     from infer import VideoTensorDataset
     os.makedirs(a.output_dir, exist_ok=True)
@@ -90,7 +107,7 @@ def main(argv=None):
     out = os.path.join(a.output_dir, "study.jsonl")
     records = []
     for cfg in configs:
-        rec = run_config(cfg, dataset, a.vae_path, a.reduced, "cuda", a.max_files)
+        rec = run_config(cfg, dataset, a.vae_path, a.reduced, "cuda", a.max_files, lpips)
         records.append(rec)
         with open(out, "a") as f:
             f.write(json.dumps(rec) + "\n")
