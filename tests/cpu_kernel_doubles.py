@@ -202,6 +202,113 @@ def conv_cout4(x, affine, silu, w_frag, bias, T, H, W, cin, cout, out=None):
     return out
 
 
+# ---- VAE mid-block attention entry points (vae_ops.gemm_f16, softmax_rows, transpose_16b, groupnorm_affine, groupnorm_apply): fp32
+# emulations in the kernels' own operation order and with the wrappers' argument meaning (n, k, `out` views with their row strides,
+# cols_pad, causal_block, out_f32, res), so that AutoencoderKLCausal3D._mid_attention itself runs on device="cpu"
+# (tests/test_mid_attention_cpu.py).  `mutant` selects one changed line of the softmax (the ways such a kernel can be subtly wrong).
+F16 = torch.float16
+
+
+def vae_gemm_f16(a, w, bias=None, out=None, out_f32=False, res=None, n=None, k=None):
+    """64-wide K-tiles into one fp32 accumulator, bias added last; fp32 store, or one rounding to fp16 and then fp16(res + y)"""
+    m = a.shape[0]
+    k = a.shape[1] if k is None else k
+    n = w.shape[0] if n is None else n
+    assert k >= 64 and k % 64 == 0 and n % 8 == 0 and not (out_f32 and res is not None), (m, n, k)
+    acc = torch.zeros(m, n)
+    for k0 in range(0, k, 64):
+        acc = acc + a[:, k0:k0 + 64].float() @ w[:n, k0:k0 + 64].float().T
+    if bias is not None:
+        acc = acc + bias[:n].float()[None]
+    if out is None:
+        out = torch.empty(m, n, dtype=torch.float32 if out_f32 else F16)
+    if out_f32:
+        out[:, :n] = acc
+    elif res is not None:
+        out[:, :n] = (res[:, :n].float() + acc.to(F16).float()).to(F16)
+    else:
+        out[:, :n] = acc.to(F16)
+    return out
+
+
+def vae_softmax_rows(s_f32, cols, cols_pad, scale, out=None, causal_block=0, mutant=None):
+    """valid(r) = cols, or min(cols, (r / causal_block + 1) * causal_block); m = max over the valid columns * scale; p = fp16(exp(s *
+    scale - m) * (1 / sum)); +0 in [valid, cols_pad)"""
+    rows = s_f32.shape[0]
+    assert 0 < cols <= cols_pad and causal_block >= 0
+    if out is None:
+        out = torch.empty(rows, cols_pad, dtype=F16)
+    r = torch.arange(rows)
+    valid = torch.full((rows,), cols)
+    if causal_block > 0:
+        frames = r // causal_block if mutant == "frame_index" else r // causal_block + 1
+        valid = torch.clamp(frames * causal_block, max=cols)
+    if mutant == "drop_last_key":
+        valid = valid - 1
+    ok = torch.arange(cols_pad)[None] < valid[:, None]
+    sc = torch.tensor(scale, dtype=torch.float32)
+    width = min(cols_pad, s_f32.shape[1])
+    s = torch.full((rows, cols_pad), -math.inf)
+    s[:, :width] = s_f32[:, :width]
+    seen = s_f32 if mutant == "max_over_masked" else torch.where(ok, s, torch.tensor(-math.inf))
+    m = seen.max(-1, keepdim=True).values * sc
+    e = torch.where(ok, torch.exp(s * sc - m), torch.zeros(()))
+    if mutant == "sum_after_rounding":
+        e = e.to(F16).float()
+    p = e * (1.0 / e.sum(-1, keepdim=True))
+    out[:, :cols_pad] = p.to(torch.bfloat16).to(F16) if mutant == "bf16_p" else p.to(F16)
+    return out
+
+
+def vae_transpose_16b(src, dst):
+    r, c = src.shape
+    dst[:c, :r] = src.T
+    return dst
+
+
+def vae_groupnorm_affine(x, weight, bias, groups=32, eps=1e-6):
+    """sums of d = x - pivot (the group's first value of row 0) and of d^2 in fp32, folded in fp64; sc = fp32(rstd w),
+    sh = fp32(b - mean sc) (gn_affine_out)"""
+    m, c = x.shape
+    cpg = c // groups
+    xf = x[:, :c].float().reshape(m, groups, cpg)
+    pivot = xf[0, :, 0]
+    d = xf - pivot[None, :, None]
+    s, q = d.sum(0).double().sum(-1), (d * d).sum(0).double().sum(-1)
+    n = float(m * cpg)
+    md = s / n
+    mean, var = pivot.double() + md, (q / n - md * md).clamp(min=0.0)
+    rstd = 1.0 / torch.sqrt(var + float(torch.tensor(eps, dtype=torch.float32)))
+    sc = (rstd.repeat_interleave(cpg) * weight.double()).float()
+    sh = (bias.double() - mean.repeat_interleave(cpg) * sc.double()).float()
+    return torch.stack([sc, sh], 1).contiguous()
+
+
+def vae_groupnorm_apply(x, affine, silu, out=None):
+    t = x.float() * affine[:, 0][None] + affine[:, 1][None]
+    y = (t / (1.0 + torch.exp(-t)) if silu else t).to(F16)
+    if out is None:
+        return y
+    out.copy_(y)
+    return out
+
+
+VAE_MID_ATTENTION_NAMES = ["gemm_f16", "softmax_rows", "transpose_16b", "groupnorm_affine", "groupnorm_apply"]
+
+
+def install_vae_mid_attention(monkeypatch, softmax_mutant=None):
+    """Install the five doubles on hunyuanvideo_efficiency_amd.vae_ops for the length of a test (pytest's monkeypatch undoes it)."""
+    import functools
+    from hunyuanvideo_efficiency_amd import vae_ops
+    g = globals()
+    for n in VAE_MID_ATTENTION_NAMES:
+        f = g["vae_" + n]
+        if n == "softmax_rows" and softmax_mutant is not None:
+            f = functools.partial(f, mutant=softmax_mutant)
+        monkeypatch.setattr(vae_ops, n, f)
+    return vae_ops
+
+
 NAMES = ["ln_modulate", "qknorm_rope_", "gemm", "linear_smallm", "attn_fwd", "patchify", "unpatchify", "euler_step_",
          "masked_mean", "broadcast_row_", "timestep_embedding", "copy3d"]
 
