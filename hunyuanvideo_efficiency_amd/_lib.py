@@ -18,7 +18,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libhv_kernels.so")
 TORCH_OPS_PATH = os.path.join(_HERE, "lib", "libhv_torch_ops.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -73,6 +73,8 @@ SIGNATURES = {
     "hv_lpips_maxpool_f32": [_p, _p, _i, _i, _i, _i, _p],
     "hv_lpips_distance_f32": [_p, _p, _i, _l, _i, _i, _p, _p, _l, _p],
     "hv_lpips_distance_workspace_bytes": [_i, _l],
+    "hv_temporal_spectrum": [_p, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _l, _p, _p, _p, _l, _p],
+    "hv_temporal_spectrum_workspace_bytes": [_i, _i, _i, _i, _i],
 }
 
 
@@ -100,7 +102,7 @@ def load():
             raise HVKernelError(f"{LIB_PATH} does not export {name}") from e
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name in ("hv_attn_workspace_bytes", "hv_gn_partial_rows", "hv_subpixel_gn_partial_rows", "hv_conv3d_cout4_planes_floats",
-                                            "hv_video_metrics_workspace_bytes", "hv_lpips_distance_workspace_bytes") else C.c_int
+                                            "hv_video_metrics_workspace_bytes", "hv_lpips_distance_workspace_bytes", "hv_temporal_spectrum_workspace_bytes") else C.c_int
     v = lib.hv_abi_version()
     if v != ABI_VERSION:
         raise HVKernelError(f"libhv_kernels ABI {v} != expected {ABI_VERSION}: rebuild the extension")

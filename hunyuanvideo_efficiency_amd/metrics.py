@@ -1,4 +1,5 @@
-"""PSNR / SSIM / LPIPS of a reconstruction against its input, scored on the device (csrc/hv_metrics.hip, csrc/hv_lpips.hip).
+"""PSNR / SSIM / LPIPS of a reconstruction against its input and temporal spectra, on the device (csrc/hv_metrics.hip, hv_lpips.hip,
+hv_spectrum.hip).
 
 The fork's study scores reconstructions with evaluation/compute_metrics.py: per frame `compute_psnr` / `compute_ssim` (skimage) on
 the 8-bit frames of an mp4 that `save_videos_grid(..., rescale=True)` wrote, averaged over all frames of an experiment.  Here the
@@ -10,6 +11,8 @@ AlexNet state dict plus the LPIPS linear file, or one full LPIPS state dict); no
 changes: result files carry an `LPIPS` line only when LPIPS values were added.  `LpipsAlex.synthetic` gives deterministic weights for
 tests and timing, whose scores are not comparable with published LPIPS.  Parity rests on this restatement (tests/lpips_ref.py):
 neither torchvision nor the `lpips` package is part of this environment.
+Temporal spectra (`temporal_spectrum`, `spectrum_report`; csrc/hv_spectrum.hip) restate the fork's theory_analysis.ipynb: the mean
+|FFT| over all pixel time series of the gray frames and over all latent series, as one fp32-MFMA DFT whose product never leaves the chip.
 What it is not: there is no video codec in between (the reference's frames went through libx264).  CPU tensors are refused like
 everywhere else in the package."""
 from __future__ import annotations
@@ -320,6 +323,181 @@ def lpips_video(ref: torch.Tensor, rec: torch.Tensor, model: LpipsAlex, rescale:
     if not batched:
         total, layers = total[0], layers[0]
     return (total, layers) if return_layers else total
+
+
+# ---- temporal spectra (csrc/hv_spectrum.hip) --------------------------------------------------------------------------------------------
+# The fork's theory_analysis.ipynb, cells 2, 4 and 5: `np.abs(np.fft.fft(signal, axis=0)).mean(axis=1)` over every pixel time series of
+# the 8-bit gray frames of a clip (cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY)), and the same over every (channel, h, w) series of
+# `latent_dist.mean`, plotted against fftfreq(T, 1 / fps) and fftfreq(T_lat, 4 / fps).
+SPECTRUM_MAX_T = 1024
+SPECTRUM_BK, SPECTRUM_BINS = 32, 32          # frames per k-chunk, bins per column tile (cos block | sin block) of the kernel
+# (wr, wg, wb, round, shift) of the integer luma.  UNPINNED RESTATEMENT: OpenCV's 8-bit BGR2GRAY fixed-point rule as far as it can be
+# established without cv2 (not part of this environment) - 0.299 / 0.587 / 0.114 in 15 fractional bits, round to nearest.  OpenCV
+# builds that take the 14-bit rule (4899, 9617, 1868, 1 << 13, 14) differ by one grey level on a few pixels; pass `luma=` to choose.
+GRAY_LUMA = (9798, 19235, 3735, 1 << 14, 15)
+_SPECTRUM_MODES = {"gray": 0, "raw": 1}
+_twiddle_cache = {}
+
+
+def spectrum_twiddles(T: int) -> torch.Tensor:
+    """The kernel's B operand, float32 [T rounded up to 32, 64 * ncol] on the host: column 64 j + c is cos (c < 32) or sin (c >= 32) of
+    2 pi ((k t) mod T) / T for bin k = 1 + 32 j + (c & 31) - the cos and the sin block of the same 32 bins side by side, so that re_k and
+    im_k of a series land in one lane.  Every entry is computed in float64 from the integer-reduced k t mod T and rounded once; columns
+    of bins behind T // 2 and rows behind T are zero."""
+    if not 1 <= T <= SPECTRUM_MAX_T:
+        raise _lib.HVKernelError(f"temporal spectrum: 1 <= T <= {SPECTRUM_MAX_T}, got {T}")
+    nb = T // 2
+    ncol = max(1, -(-nb // SPECTRUM_BINS))
+    tpad = -(-T // SPECTRUM_BK) * SPECTRUM_BK
+    tab = np.zeros((tpad, ncol, 2, SPECTRUM_BINS), dtype=np.float64)
+    k = np.arange(1, ncol * SPECTRUM_BINS + 1, dtype=np.int64)
+    ang = 2.0 * np.pi * ((np.arange(T, dtype=np.int64)[:, None] * k[None, :]) % T).astype(np.float64) / T
+    live = (k <= nb)[None, :]
+    tab[:T, :, 0] = np.where(live, np.cos(ang), 0.0).reshape(T, ncol, SPECTRUM_BINS)
+    tab[:T, :, 1] = np.where(live, np.sin(ang), 0.0).reshape(T, ncol, SPECTRUM_BINS)
+    return torch.from_numpy(tab.reshape(tpad, ncol * 2 * SPECTRUM_BINS).astype(np.float32))
+
+
+def _twiddles_on(T: int, device) -> torch.Tensor:
+    key = (T, torch.device(device))
+    if key not in _twiddle_cache:
+        _twiddle_cache[key] = spectrum_twiddles(T).to(device)
+    return _twiddle_cache[key]
+
+
+def mirror_spectrum(half, T: int) -> np.ndarray:
+    """bins 0 .. T // 2 ([..., T // 2 + 1]) -> the full length-T spectrum of a real series: bin T - k repeats bin k, the Nyquist bin of
+    an even T appears once"""
+    half = np.asarray(half, dtype=np.float64)
+    if half.shape[-1] != T // 2 + 1:
+        raise ValueError(f"a real series of {T} samples has {T // 2 + 1} bins, got {half.shape[-1]}")
+    return np.concatenate([half, half[..., 1:(T + 1) // 2][..., ::-1]], axis=-1)
+
+
+def spectrum_sums(x: torch.Tensor, mode: str = "gray", rescale: bool = True, luma=GRAY_LUMA):
+    """The kernel's raw output, left on the device: (mag_sum, pow_sum) float64 [B, T // 2 + 1] - per-bin sums of |X_k| and |X_k|^2 over
+    all series - and the series count (H W in gray mode, C H W in raw mode).  Nothing is synchronised."""
+    _check_video(x, "x")
+    if mode not in _SPECTRUM_MODES:
+        raise _lib.HVKernelError(f"temporal spectrum: mode is 'gray' or 'raw', got {mode!r}")
+    if x.dim() == 4:
+        x = x[None]
+    B, C, T, H, W = x.shape
+    if mode == "gray" and C != 3:
+        raise _lib.HVKernelError(f"temporal spectrum: gray mode reads RGB videos, got C = {C}")
+    if not 1 <= T <= SPECTRUM_MAX_T:
+        raise _lib.HVKernelError(f"temporal spectrum: 1 <= T <= {SPECTRUM_MAX_T}, got {T}")
+    m = _SPECTRUM_MODES[mode]
+    ws_bytes = _lib.host("temporal_spectrum_workspace_bytes", m, C, T, H, W)
+    if ws_bytes <= 0:
+        raise _lib.HVKernelError(f"temporal spectrum: unsupported shape {tuple(x.shape)} in {mode} mode")
+    dev = x.device
+    tw = _twiddles_on(T, dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    mag = torch.empty(B, T // 2 + 1, dtype=torch.float64, device=dev)
+    pw = torch.empty(B, T // 2 + 1, dtype=torch.float64, device=dev)
+    wr, wg, wb, rnd, shift = (int(v) for v in luma)
+    for b in range(B):                        # one stream: video b + 1 reuses the workspace after video b's fold
+        v = x[b]
+        _lib.call("temporal_spectrum", v, v.stride(0), v.stride(1), v.stride(2), _DTYPES[x.dtype], m, C, T, H, W, 1 if rescale else 0,
+                  wr, wg, wb, rnd, shift, tw, tw.numel(), mag[b], pw[b], ws, ws.numel())
+    return mag, pw, (H * W if mode == "gray" else C * H * W)
+
+
+def _spectra_to_host(jobs, fps_of):
+    """jobs: [(mag_sum, pow_sum, series, T, batched)] on one device -> one synchronisation, then the host rules: divide by the series
+    count, mirror"""
+    host = []
+    for mag, pw, _, _, _ in jobs:
+        pair = []
+        for t in (mag, pw):
+            h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+            h.copy_(t, non_blocking=True)
+            pair.append(h)
+        host.append(pair)
+    torch.cuda.current_stream(jobs[0][0].device).synchronize()
+    out = []
+    for i, ((_, _, n, T, batched), (hm, hp)) in enumerate(zip(jobs, host)):
+        mag, pw = mirror_spectrum(hm.numpy() / float(n), T), mirror_spectrum(hp.numpy() / float(n), T)
+        if not batched:
+            mag, pw = mag[0], pw[0]
+        d = {"magnitude": mag, "power": pw}
+        dt = fps_of(i)
+        if dt is not None:
+            d["freq"] = np.fft.fftfreq(T, dt)
+        out.append(d)
+    return out
+
+
+def temporal_spectrum(x: torch.Tensor, mode: str = "gray", rescale: bool = True, fps: float = None, luma=GRAY_LUMA) -> dict:
+    """Mean temporal spectrum of `x` ([C,T,H,W] or [B,C,T,H,W]; GPU tensors only, fp16 or fp32, W contiguous, strided views allowed, T <=
+    1024), theory_analysis.ipynb cells 2 / 4.  mode "gray" (C = 3): one series per pixel of the 8-bit gray frame - the bytes
+    `frames_uint8` writes (rescale: values in [-1, 1], else [0, 1]) under the integer luma `luma` = (wr, wg, wb, round, shift), default
+    GRAY_LUMA: OpenCV's 8-bit BGR2GRAY rule as restated here, NOT pinned against cv2 (which this environment lacks).  mode "raw": one
+    series per (c, h, w), values as they are (the latent mean).  Returns float64 numpy arrays `magnitude` [T] ([B,T] for a batch) - the
+    reference's np.abs(np.fft.fft(signal, axis=0)).mean(axis=1), bin 0 included, mirrored to full length -, `power` [T], the mean
+    |X_k|^2, and with `fps` `freq` = np.fft.fftfreq(T, 1 / fps).  One host synchronisation."""
+    batched = isinstance(x, torch.Tensor) and x.dim() == 5
+    mag, pw, n = spectrum_sums(x, mode, rescale, luma)
+    T = x.shape[-3]
+    return _spectra_to_host([(mag, pw, n, T, batched)], lambda i: None if fps is None else 1.0 / fps)[0]
+
+
+def high_band_share(power, cutoff_bin: int) -> float:
+    """Share of the non-DC power of a full-length spectrum `power` [T] that sits at bins cutoff_bin <= k <= T - cutoff_bin (both mirror
+    images of the band; the Nyquist bin of an even T is counted once).  0.0 when there is no non-DC power or the band is empty."""
+    p = np.asarray(power, dtype=np.float64)
+    if p.ndim != 1:
+        raise ValueError(f"high_band_share takes one spectrum [T], got shape {p.shape}")
+    T = p.shape[0]
+    if cutoff_bin < 1:
+        raise ValueError(f"cutoff_bin must be >= 1 (bin 0 is the DC term), got {cutoff_bin}")
+    total = float(p[1:].sum())
+    if total <= 0.0 or cutoff_bin > T - cutoff_bin:
+        return 0.0
+    return float(p[cutoff_bin:T - cutoff_bin + 1].sum()) / total
+
+
+def latent_nyquist_bin(T: int, T_in: int, T_lat: int) -> int:
+    """The first bin k of a length-T spectrum with k / T >= 1 / (2 T_in / T_lat): the Nyquist frequency of a latent that keeps T_lat
+    samples of T_in frames, in cycles per frame"""
+    return max(1, -(-T * T_lat // (2 * T_in)))
+
+
+def spectrum_report(clip: torch.Tensor, latent: torch.Tensor, recon: torch.Tensor, fps: float = None, t_ratio: int = 4,
+                    rescale: bool = True) -> dict:
+    """The three spectra of one reconstruction and what each loses: {"input", "reconstruction", "latent"}, each the dict of
+    `temporal_spectrum` (gray mode for `clip` and `recon`, raw mode for `latent`) plus `high_band_share` and `cutoff_bin`.  The videos'
+    cutoff is the Nyquist bin of the latent rate (`latent_nyquist_bin` with T_in, T_lat of `clip` and `latent`): what a temporal
+    pool, stride or interpolation down to T_lat samples cannot carry.  The latent's own cutoff is the upper half of its band (the first
+    bin with k / T_lat >= 1 / 4).  With `fps` the videos get freq = fftfreq(T, 1 / fps) and the latent fftfreq(T_lat, t_ratio / fps), as
+    cell 4.  Batches give one share per video.  All launches are enqueued first: one host synchronisation."""
+    items = (("input", clip, "gray"), ("latent", latent, "raw"), ("reconstruction", recon, "gray"))
+    jobs = []
+    for _, x, mode in items:
+        mag, pw, n = spectrum_sums(x, mode, rescale)
+        jobs.append((mag, pw, n, x.shape[-3], x.dim() == 5))
+    dts = [None if fps is None else (t_ratio / fps if mode == "raw" else 1.0 / fps) for _, _, mode in items]
+    out = {name: d for (name, _, _), d in zip(items, _spectra_to_host(jobs, lambda i: dts[i]))}
+    return add_high_band_shares(out)
+
+
+def add_high_band_shares(spectra: dict) -> dict:
+    """`cutoff_bin` and `high_band_share` for the {"input", "latent", "reconstruction"} spectra of `spectrum_report` (pure numpy): the
+    frame counts are the lengths of the spectra themselves"""
+    T_in, T_lat = spectra["input"]["power"].shape[-1], spectra["latent"]["power"].shape[-1]
+    for name, d in spectra.items():
+        T = d["power"].shape[-1]
+        cut = max(1, -(-T // 4)) if name == "latent" else latent_nyquist_bin(T, T_in, T_lat)
+        d["cutoff_bin"] = cut
+        d["high_band_share"] = (float(high_band_share(d["power"], cut)) if d["power"].ndim == 1
+                                else np.array([high_band_share(p, cut) for p in d["power"]]))
+    return spectra
+
+
+def spectrum_json(report: dict) -> dict:
+    """a `spectrum_report` of ONE video as plain lists and floats (the <name>_spectrum.json of infer.py --spectrum)"""
+    return {name: {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in d.items()} for name, d in report.items()}
 
 
 def add_lpips_arguments(parser, synthetic: bool = False):

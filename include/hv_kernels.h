@@ -352,6 +352,28 @@ int hv_lpips_distance_f32(const float* f, const float* lin, int T, int64_t P, in
                           int64_t workspace_bytes, hipStream_t stream);
 int64_t hv_lpips_distance_workspace_bytes(int T, int64_t P);
 
+/* Temporal spectra (the fork's theory_analysis.ipynb cells 2, 4, 5: np.abs(np.fft.fft(signal, axis=0)).mean(axis=1) over the pixel time
+ * series of the 8-bit gray frames of a clip, and over every (channel, h, w) series of latent_dist.mean): per-bin SUMS over all series of
+ * one x [C,T,H,W] (dtype 0 = fp16, 1 = fp32; element strides sc, st, sh, W contiguous, as hv_video_metrics) of |X_k| and |X_k|^2,
+ * k = 0 .. T/2 (K = T/2 + 1 bins; the caller divides by the series count and mirrors bin T - k from bin k).
+ * mode 0 (gray8, C = 3): one series per pixel; R, G, B are quantised to the byte save_videos_grid would write (the quantiser of
+ * hv_video_metrics) and combined to the integer luma (wr R + wg G + wb B + round) >> shift, which must stay a byte: weights and round
+ * >= 0, shift <= 22, (wr + wg + wb) * 255 + round < 256 << shift.  mode 1 (raw, any C): one series per (c, h, w), the value cast to fp32.
+ * Arithmetic: bin 0 is sum_t x_t itself (mode 0: exact integers, also in pow_sum while a partial sum stays below 2^53; mode 1: an fp32
+ * chain in frame order, its square rounded to fp32).  Bins k >= 1 transform d_t = x_t - x_0 (exact in mode 0, one fp32 rounding in
+ * mode 1; the DFT of the constant x_0 vanishes there): re_k, im_k = sum_t d_t * twiddle, each one fp32 fmaf chain on the fp32-input MFMA;
+ * |X_k|^2 = fl(fl(re^2) + fl(im^2)), |X_k| = sqrtf of it; both summed over series in fp64 through workgroup partials folded in a fixed
+ * order (no atomics: run-to-run identical).
+ * twiddle: host-built fp32 [Tpad][64 * ncol], Tpad = T rounded up to 32, ncol = max(1, ceil((T/2) / 32)), 16-byte aligned,
+ * twiddle_floats >= Tpad * 64 * ncol: column 64 j + c holds cos (c < 32) or sin (c >= 32) of 2 pi ((k t) mod T) / T for bin
+ * k = 1 + 32 j + (c & 31), zero for k > T/2 and in rows t >= T.
+ * workspace: >= hv_temporal_spectrum_workspace_bytes(mode, C, T, H, W) bytes, 8-byte aligned.  T < 1, T > 1024, C != 3 in mode 0, H or W
+ * outside [1, 65536], negative or overlapping strides are HV_ERR_ARG (the workspace query returns 0 for the shapes among them). */
+int hv_temporal_spectrum(const void* x, int64_t sc, int64_t st, int64_t sh, int dtype, int mode, int C, int T, int H, int W,
+                         int rescale, int wr, int wg, int wb, int round, int shift, const float* twiddle, int64_t twiddle_floats,
+                         double* mag_sum, double* pow_sum, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int64_t hv_temporal_spectrum_workspace_bytes(int mode, int C, int T, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 """The VAE efficiency study in one process: enumerate temporal-op configurations (dynamic_enumeration.py), and for each one build
 the VAE under it, reconstruct every video of --tensor-dir and score it on the GPU (PSNR / SSIM per frame, nothing copied to the host
 or written per video: infer.py --score --no-save).  One line per configuration is appended to <output-dir>/study.jsonl:
-{"config", "PSNR", "SSIM", ("LPIPS" with --lpips-alexnet / --lpips-synthetic,) "frames", "compression": T_latent / T_in} - or {"config", "refused": message} for a configuration the
+{"config", "PSNR", "SSIM", ("LPIPS" with --lpips-alexnet / --lpips-synthetic,) "frames", "compression": T_latent / T_in, ("spectrum" with
+--spectrum: the high-band shares of input, latent and reconstruction averaged over clips; the mean spectra go to spectra_<config>.json)} - or {"config", "refused": message} for a configuration the
 VAE refuses (a ValueError of its list-length checks, NotImplementedError).  Configurations run one after another on one GPU: the
 fork's shell drivers' background batches over several cards are not reproduced.
 
@@ -35,14 +36,16 @@ def build_vae(config_json, vae_path, reduced, device):
     return vae
 
 
-def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, lpips=None):
-    """-> the study.jsonl record of one configuration"""
+def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, lpips=None, spectra=None, fps=None):
+    """-> the study.jsonl record of one configuration.  `spectra` (a dict, --spectrum): temporal spectra are taken too - the record gains
+    "spectrum" and the dict is filled with the configuration's mean spectra (`mean_spectra`)"""
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator
     rec = {"config": os.path.basename(config_json)}
     try:
         vae = build_vae(config_json, vae_path, reduced, device)
         acc = MetricsAccumulator(lpips=lpips)
         t_in = t_lat = 0
+        reports = []
         n = len(dataset) if max_files is None else min(len(dataset), max_files)
         for idx in range(n):
             video, _ = dataset[idx]
@@ -51,6 +54,9 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
                 z = vae.encode(video).latent_dist.mode()
                 recon = vae.decode(z).sample
             acc.add_video(video, recon, rescale=True)
+            if spectra is not None:
+                from hunyuanvideo_efficiency_amd.metrics import spectrum_report
+                reports.append(spectrum_report(video[0], z[0], recon[0], fps=fps))
             t_in += video.shape[2]
             t_lat += z.shape[2]
         rec.update(acc.result())
@@ -58,9 +64,34 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
             rec["lpips_weights"] = "synthetic"          # not comparable with published LPIPS
         rec["frames"] = acc.frames
         rec["compression"] = t_lat / t_in if t_in else None
+        if spectra is not None:
+            rec["spectrum"] = {f"{name}_high_band_share": (sum(r[name]["high_band_share"] for r in reports) / len(reports) if reports else None)
+                               for name in ("input", "latent", "reconstruction")}
+            spectra.update(mean_spectra(reports))
     except (ValueError, NotImplementedError) as e:
         rec["refused"] = f"{type(e).__name__}: {e}"
     return rec
+
+
+def mean_spectra(reports):
+    """per part (input / latent / reconstruction) the spectra averaged over the clips of one frame count (clips of different lengths have
+    different bins: one entry per length), as plain lists: the spectra_<config>.json of --spectrum"""
+    import numpy as np
+    out = {}
+    for name in ("input", "latent", "reconstruction"):
+        by_len = {}
+        for r in reports:
+            by_len.setdefault(len(r[name]["power"]), []).append(r[name])
+        out[name] = []
+        for T, rs in sorted(by_len.items()):
+            e = {"frames": T, "clips": len(rs), "cutoff_bin": rs[0]["cutoff_bin"],
+                 "magnitude": np.mean([r["magnitude"] for r in rs], axis=0).tolist(),
+                 "power": np.mean([r["power"] for r in rs], axis=0).tolist(),
+                 "high_band_share": float(np.mean([r["high_band_share"] for r in rs]))}
+            if "freq" in rs[0]:
+                e["freq"] = rs[0]["freq"].tolist()
+            out[name].append(e)
+    return out
 
 
 def _exp_order(name):
@@ -79,9 +110,14 @@ def parse_args(argv=None):
     p.add_argument("--max-files", type=int, default=None)
     p.add_argument("--vae-path", default=None, help="VAE checkpoint directory; default: synthetic weights")
     p.add_argument("--reduced", action="store_true", help="synthetic-weight mode only: reduced channel widths")
+    p.add_argument("--spectrum", action="store_true", help="temporal spectra of input, latent and reconstruction: each record gains "
+                   "\"spectrum\" (three high-band shares, averaged over clips), each configuration a spectra_<config>.json")
+    p.add_argument("--fps", type=float, default=None, help="with --spectrum: frame rate of the clips, adds the frequency axes")
     from hunyuanvideo_efficiency_amd.metrics import add_lpips_arguments
     add_lpips_arguments(p, synthetic=True)
     a = p.parse_args(argv)
+    if a.fps is not None and not (a.spectrum and a.fps > 0):
+        p.error("--fps needs --spectrum and a positive rate")
     if (a.base_config is None) == (a.config_dir is None):
         p.error("give exactly one of --base-config (enumerate) or --config-dir (ready-made configurations)")
     if a.lpips_linear and not a.lpips_alexnet:
@@ -107,7 +143,11 @@ def main(argv=None):
     out = os.path.join(a.output_dir, "study.jsonl")
     records = []
     for cfg in configs:
-        rec = run_config(cfg, dataset, a.vae_path, a.reduced, "cuda", a.max_files, lpips)
+        spectra = {} if a.spectrum else None
+        rec = run_config(cfg, dataset, a.vae_path, a.reduced, "cuda", a.max_files, lpips, spectra, a.fps)
+        if spectra:
+            with open(os.path.join(a.output_dir, f"spectra_{os.path.splitext(os.path.basename(cfg))[0]}.json"), "w") as f:
+                json.dump(spectra, f)
         records.append(rec)
         with open(out, "a") as f:
             f.write(json.dumps(rec) + "\n")
