@@ -1,0 +1,35 @@
+"""include/hv_kernels.h read once: the declarations of the C ABI and its integer `#define HV_*` constants.  Everything that has to
+agree with the header (the ctypes table of _lib.py, the generated csrc/hv_torch_ops.cpp, the sizes ops.py / vae_ops.py / metrics.py
+share with the kernels, tests/test_capi_cpu.py) takes it from here.  Standard library only."""
+import os
+import re
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "hv_kernels.h")
+
+
+class HVKernelError(RuntimeError):
+    pass
+
+
+def parse(text):
+    """-> (decls, macros): decls = [(return C type, name, [(C type, parameter name), ...]), ...] in header order,
+    macros = {"HV_...": int} of the `#define HV_* <integer>` lines."""
+    macros = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"^#define\s+(HV_\w+)\s+(\d\w*)\s*$", text, flags=re.M)}
+    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    decls = []
+    for m in re.finditer(r"\b(int|int64_t)\s+(hv_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
+        ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())
+        params = []
+        if args not in ("", "void"):
+            for a in args.split(","):
+                pm = re.match(r"(.*?)(\w+)$", a.strip())
+                params.append((pm.group(1).strip(), pm.group(2)))
+        decls.append((ret, name, params))
+    return decls, macros
+
+
+if not os.path.exists(HEADER):
+    raise HVKernelError(f"{HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout (the header is the one "
+                        "description of the C ABI its bindings are derived from)")
+with open(HEADER) as _f:
+    DECLS, MACROS = parse(_f.read())

@@ -15,74 +15,36 @@ import ctypes as C
 import os
 import re
 
+from . import _abi
+from ._abi import HVKernelError
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libhv_kernels.so")
 TORCH_OPS_PATH = os.path.join(_HERE, "lib", "libhv_torch_ops.so")
-ABI_VERSION = 9
+LOOP_INC = os.path.join(_HERE, "csrc", "hv_attention_w4_loop.inc")
+ABI_VERSION = _abi.MACROS["HV_ABI_VERSION"]
 
-_p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
-
-# name -> argtypes (restype is always int); mirrors include/hv_kernels.h one to one
-SIGNATURES = {
-    "hv_abi_version": [],
-    "hv_ln_modulate_bf16": [_p, _p, _p, _p, _l, _i, _l, _l, _f, _i, _p],
-    "hv_qknorm_rope_bf16": [_p, _p, _p, _p, _p, _l, _l, _i, _i, _l, _l, _f, _p],
-    "hv_qknorm_rope_scatter_bf16": [_p, _p, _p, _p, _p, _l, _l, _i, _i, _l, _l, _f, _p, _l, _i, _l, _p],
-    "hv_gemm_bf16": [_p, _l, _p, _l, _p, _i, _i, _i, _p, _l, _i, _i, _p, _l, _i, _p, _p, _l, _p],
-    "hv_linear_smallm_bf16": [_p, _p, _p, _p, _p, _i, _i, _i, _l, _l, _i, _p],
-    "hv_timestep_embedding_bf16": [_p, _p, _i, _i, _f, _p],
-    "hv_attn_fwd_bf16": [_p, _p, _p, _p, _l, _l, _l, _l, _i, _i, _i, _i, _f, _p, _l, _p],
-    "hv_attn_workspace_bytes": [_i, _i, _i],
-    "hv_attn_w4_loop_signature": [],
-    "hv_attn_partial_bf16": [_p, _p, _p, _l, _l, _l, _i, _i, _i, _i, _f, _p, _p, _i, _i, _i, _p],
-    "hv_attn_merge_bf16": [_p, _p, _p, _l, _i, _i, _i, _p],
-    "hv_attn_suggest_splits": [_i, _i, _i],
-    "hv_patchify_f32_bf16": [_p, _p, _i, _i, _i, _i, _p],
-    "hv_unpatchify_bf16": [_p, _p, _i, _i, _i, _i, _l, _p],
-    "hv_euler_step_f32": [_p, _p, _f, _l, _p],
-    "hv_euler_step_f32_f32": [_p, _p, _f, _l, _p],
-    "hv_masked_mean_bf16": [_p, _p, _p, _i, _i, _p],
-    "hv_broadcast_row_bf16": [_p, _p, _l, _i, _l, _p],
-    "hv_copy3d_bf16": [_p, _p, _i, _l, _i, _l, _l, _l, _l, _p],
-    "hv_fp8_dequant_bf16": [_p, _p, _p, _l, _p],
-    "hv_ln_modulate_fp8": [_p, _p, _p, _p, _p, _l, _i, _l, _l, _f, _p],
-    "hv_quant_rows_fp8": [_p, _l, _p, _l, _p, _l, _i, _p],
-    "hv_gemm_fp8": [_p, _l, _p, _p, _l, _p, _p, _i, _i, _i, _p, _l, _i, _i, _p, _l, _i, _p, _p, _l, _p],
-    "hv_gemm_f16": [_p, _l, _p, _l, _p, _i, _i, _i, _p, _l, _i, _p, _l, _p],
-    "hv_conv3d_causal_f16": [_p, _l, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _p, _l, _p, _l, _p],
-    "hv_gn_partial_rows": [_l],
-    "hv_subpixel_gn_partial_rows": [_i, _i, _i, _i],
-    "hv_groupnorm_finalize_f16": [_p, _l, _l, _l, _i, _i, _f, _p, _p, _p, _p],
-    "hv_groupnorm_affine_f16": [_p, _l, _l, _i, _i, _f, _p, _p, _p, _l, _p, _p],
-    "hv_groupnorm_apply_f16": [_p, _l, _p, _l, _l, _i, _p, _i, _p],
-    "hv_softmax_rows_f32_f16": [_p, _l, _p, _l, _i, _i, _i, _f, _i, _p],
-    "hv_transpose_16b": [_p, _l, _p, _l, _i, _i, _p],
-    "hv_conv3d_upsampled_subpixel_f16": [_p, _l, _p, _p, _i, _p, _p, _l, _i, _i, _i, _i, _i, _i, _p, _l, _p],
-    "hv_conv3d_cout4_f16": [_p, _l, _p, _i, _p, _p, _p, _l, _i, _i, _i, _i, _i, _p, _l, _p],
-    "hv_conv3d_cout4_planes_floats": [_l],
-    "hv_conv3d_causal_strided_f16": [_p, _l, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "hv_temporal_resample_f16": [_p, _l, _p, _l, _i, _l, _i, _i, _i, _i, _p],
-    "hv_vae_latent_tile_f16": [_p, _l, _l, _l, _l, _i, _i, _i, _i, _i, _p, _p],
-    "hv_vae_blend_f16": [_p, _p, _p, _p, _p, _i, _i, _p],
-    "hv_copy4d_16b": [_p, _p, _p, _p, _p, _p],
-    "hv_vae_postprocess_f16_f32": [_p, _p, _l, _p],
-    "hv_video_metrics": [_p, _l, _l, _l, _p, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _l, _p],
-    "hv_video_metrics_workspace_bytes": [_i, _i, _i, _i],
-    "hv_lpips_conv1_f32": [_p, _l, _l, _l, _p, _l, _l, _l, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p],
-    "hv_lpips_conv2d_f32": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "hv_lpips_maxpool_f32": [_p, _p, _i, _i, _i, _i, _p],
-    "hv_lpips_distance_f32": [_p, _p, _i, _l, _i, _i, _p, _p, _l, _p],
-    "hv_lpips_distance_workspace_bytes": [_i, _l],
-    "hv_temporal_spectrum": [_p, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _l, _p, _p, _p, _l, _p],
-    "hv_temporal_spectrum_workspace_bytes": [_i, _i, _i, _i, _i],
-}
+_CTYPES = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "hipStream_t": C.c_void_p}
 
 
-class HVKernelError(RuntimeError):
-    pass
+def _ctype(ctype: str, where: str):
+    t = C.c_void_p if ctype.endswith("*") else _CTYPES.get(ctype)
+    if t is None:
+        raise HVKernelError(f"include/hv_kernels.h: {where}: no ctypes mapping for C type {ctype!r}")
+    return t
 
 
-_lib = None
+# the header's declarations as ctypes: name -> argtypes, name -> restype
+SIGNATURES = {name: [_ctype(t, f"{name}({p})") for t, p in params] for _, name, params in _abi.DECLS}
+RESTYPES = {name: _ctype(ret, name) for ret, name, _ in _abi.DECLS}
+_lib = _hv = None       # the loaded ctypes handle / torch.ops.hv namespace
+
+
+def loop_signature_in_tree():
+    """HV_W4_LOOP_SIGNATURE of csrc/hv_attention_w4_loop.inc (the generated attention iteration); None if it carries none"""
+    with open(LOOP_INC) as f:
+        m = re.search(r"#define HV_W4_LOOP_SIGNATURE 0x([0-9a-f]{8})u", f.read(600))
+    return None if m is None else int(m.group(1), 16)
 
 
 def load():
@@ -101,19 +63,15 @@ def load():
         except AttributeError as e:
             raise HVKernelError(f"{LIB_PATH} does not export {name}") from e
         fn.argtypes = argtypes
-        fn.restype = C.c_int64 if name in ("hv_attn_workspace_bytes", "hv_gn_partial_rows", "hv_subpixel_gn_partial_rows", "hv_conv3d_cout4_planes_floats",
-                                            "hv_video_metrics_workspace_bytes", "hv_lpips_distance_workspace_bytes", "hv_temporal_spectrum_workspace_bytes") else C.c_int
+        fn.restype = RESTYPES[name]
     v = lib.hv_abi_version()
     if v != ABI_VERSION:
         raise HVKernelError(f"libhv_kernels ABI {v} != expected {ABI_VERSION}: rebuild the extension")
     # the attention kernel's steady-state iteration is generated code (csrc/hv_attention_w4_loop.inc): a library compiled from another
     # iteration - a stale file or a timing experiment's, which computes garbage by design - must not pass for the product
-    inc = os.path.join(_HERE, "csrc", "hv_attention_w4_loop.inc")
-    if os.path.exists(inc) and os.environ.get("HV_ALLOW_EXPERIMENT_LIB") != "1":
-        with open(inc) as f:
-            m = re.search(r"#define HV_W4_LOOP_SIGNATURE 0x([0-9a-f]{8})u", f.read(600))
-        if m is None or (lib.hv_attn_w4_loop_signature() & 0xFFFFFFFF) != int(m.group(1), 16):
-            raise HVKernelError(f"{LIB_PATH} was not compiled from {inc}: rebuild the extension (make -C hunyuanvideo_efficiency_amd/csrc); "
+    if os.path.exists(LOOP_INC) and os.environ.get("HV_ALLOW_EXPERIMENT_LIB") != "1":
+        if (lib.hv_attn_w4_loop_signature() & 0xFFFFFFFF) != loop_signature_in_tree():
+            raise HVKernelError(f"{LIB_PATH} was not compiled from {LOOP_INC}: rebuild the extension (make -C hunyuanvideo_efficiency_amd/csrc); "
                                 "HV_ALLOW_EXPERIMENT_LIB=1 admits a library built from another checkout (same-box A/Bs: tools/ab_attn.sh, tools/ab_run.sh)")
     _lib = lib
     return lib
@@ -123,9 +81,6 @@ def check(code: int, what: str):
     if code != 0:
         raise HVKernelError(f"{what} failed with code {code} "
                             f"({'bad argument' if code == -1 else 'launch failure' if code == -2 else 'unknown'})")
-
-
-_hv = None
 
 
 def torch_ops():

@@ -27,7 +27,7 @@ struct AttnArgs {
     // max, run the whole key range against the bound as a STATIC maximum: no row max per tile, never a rescale.
     const unsigned* kmax2;
 };
-constexpr int KMAX_BYTES = 256;      // head of the workspace: 62 heads x 4 bytes + two mode flags (words 62, 63)
+constexpr int KMAX_BYTES = HV_ATTN_MIN_WORKSPACE_BYTES;      // head of the workspace: 62 heads x 4 bytes + two mode flags (words 62, 63)
 constexpr int KMAX_HEADS = 62;       // word 62: some wave ran against the static bound; word 63: some wave kept the online maximum (tests)
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;

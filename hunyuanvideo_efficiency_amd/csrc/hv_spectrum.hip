@@ -25,9 +25,10 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int BM = 256, BN = 64, BK = 32;
-constexpr int kBins = BN / 2;                // bins per column tile
-constexpr int kMaxT = 1024;
+constexpr int BM = 256, BN = 64, BK = HV_SPECTRUM_BK;
+constexpr int kBins = HV_SPECTRUM_BINS;      // bins per column tile
+static_assert(kBins == BN / 2, "a column tile is the cos block and the sin block of the same bins");
+constexpr int kMaxT = HV_SPECTRUM_MAX_T;
 constexpr int kMaxRowWgs = 1024;             // row workgroups of a launch; row tile g + i * 1024 is trip i of workgroup g
 
 struct Luma {

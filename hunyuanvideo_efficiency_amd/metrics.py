@@ -24,7 +24,7 @@ from datetime import datetime
 import numpy as np
 import torch
 
-from . import _lib
+from . import _abi, _lib
 
 WIN = 7                     # skimage.metrics.structural_similarity default window
 
@@ -329,8 +329,8 @@ def lpips_video(ref: torch.Tensor, rec: torch.Tensor, model: LpipsAlex, rescale:
 # The fork's theory_analysis.ipynb, cells 2, 4 and 5: `np.abs(np.fft.fft(signal, axis=0)).mean(axis=1)` over every pixel time series of
 # the 8-bit gray frames of a clip (cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY)), and the same over every (channel, h, w) series of
 # `latent_dist.mean`, plotted against fftfreq(T, 1 / fps) and fftfreq(T_lat, 4 / fps).
-SPECTRUM_MAX_T = 1024
-SPECTRUM_BK, SPECTRUM_BINS = 32, 32          # frames per k-chunk, bins per column tile (cos block | sin block) of the kernel
+# longest series; frames per k-chunk, bins per column tile (cos block | sin block) of the kernel
+SPECTRUM_MAX_T, SPECTRUM_BK, SPECTRUM_BINS = (_abi.MACROS["HV_SPECTRUM_" + k] for k in ("MAX_T", "BK", "BINS"))
 # (wr, wg, wb, round, shift) of the integer luma.  UNPINNED RESTATEMENT: OpenCV's 8-bit BGR2GRAY fixed-point rule as far as it can be
 # established without cv2 (not part of this environment) - 0.299 / 0.587 / 0.114 in 15 fractional bits, round to nearest.  OpenCV
 # builds that take the 14-bit rule (4899, 9617, 1868, 1 << 13, 14) differ by one grey level on a few pixels; pass `luma=` to choose.

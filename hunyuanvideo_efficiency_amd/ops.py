@@ -8,7 +8,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 
 BF16 = torch.bfloat16
 ACT_NONE, ACT_GELU_TANH, ACT_SILU = 0, 1, 2
@@ -143,18 +143,24 @@ def linear_smallm(x, w, bias=None, silu_in: bool = False, silu_out: bool = False
 
 
 _attn_ws = {}
+ATTN_MIN_WORKSPACE = _abi.MACROS["HV_ATTN_MIN_WORKSPACE_BYTES"]   # the per-head key-norm bound alone (static-maximum mode of the kernel)
 
 
-ATTN_MIN_WORKSPACE = 256      # hv_attention.hpp KMAX_BYTES: the per-head key-norm bound alone (static-maximum mode of the kernel)
+def _attn_workspace_bytes(n_q: int, n_kv: int, n_heads: int) -> int:
+    """Scratch hv_attn_fwd_bf16 can use for this shape: none below the key range at which the key-norm pre-pass pays, the 256 bytes of
+    the per-head bound, + the partials of the KV split where the kernel's own rule (hv_attn_suggest_splits) takes it."""
+    if n_kv < _abi.MACROS["HV_ATTN_BOUND_MIN_KV"]:
+        return 0
+    if attn_suggest_splits(n_q, n_kv, n_heads) == 2:
+        return int(_lib.host("attn_workspace_bytes", n_q, n_kv, n_heads))
+    return ATTN_MIN_WORKSPACE
 
 
 def _attn_workspace(n_q, n_kv, n_heads, device):
-    """Scratch of hv_attn_fwd_bf16: 256 bytes for the per-head key-norm bound (always, when the key range is long enough for the
-    pre-pass to pay) + the partials of the optional KV split (load balance; only allocated for shallow grids)."""
-    if n_kv < 64 * 64:
+    """The per-device grow-only scratch of hv_attn_fwd_bf16, at least _attn_workspace_bytes long (None where that is 0)."""
+    need = _attn_workspace_bytes(n_q, n_kv, n_heads)
+    if need == 0:
         return None
-    n_wg = ((n_q + 255) // 256) * n_heads
-    need = ATTN_MIN_WORKSPACE if n_wg >= 16 * 256 else int(_lib.host("attn_workspace_bytes", n_q, n_kv, n_heads))
     key = str(device)
     ws = _attn_ws.get(key)
     if ws is None or ws.numel() < need:

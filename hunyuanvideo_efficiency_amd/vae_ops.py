@@ -5,7 +5,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from .ops import _chk
 
 F16 = torch.float16
@@ -52,7 +52,7 @@ class GNStats:
         self.partial, self.rows, self.M, self.C = partial, rows, M, C
 
 
-GN_FOLD_WS_FLOATS = 16384          # include/hv_kernels.h HV_GN_FOLD_WS_FLOATS: workspace hv_groupnorm_finalize_f16 expects behind the partials
+GN_FOLD_WS_FLOATS = _abi.MACROS["HV_GN_FOLD_WS_FLOATS"]          # workspace hv_groupnorm_finalize_f16 expects behind the partials
 
 
 def _gn_stats_buffer(rows: int, c: int, device):

@@ -22,8 +22,20 @@ extern "C" {
 typedef struct ihipStream_t* hipStream_t;
 #endif
 
-/* ABI version of this header (bumped on any signature change, or a change of what a caller-visible buffer holds). */
-int hv_abi_version(void);
+/* ABI version of this header (bumped on any signature change, or a change of what a caller-visible buffer holds);
+ * tests/golden/abi_v<N>.json records the declarations of version N (python tools/gen_torch_ops.py --record-abi).
+ *   2: + hv_euler_step_f32_f32, hv_gemm_fp8 family
+ *   3: conv gn_partial, sub-pixel upsampler conv
+ *   4: hv_groupnorm_finalize_f16 takes partial_floats
+ *   5: gn_partial entries (sum, centred sum of squares) + (0, count) per column pair
+ *   6: + hv_video_metrics, hv_video_metrics_workspace_bytes
+ *   7: fp8 row scales floored at 2^-126 (finite codes for rows with 0 < amax < 448 * 2^-126), hv_vae_postprocess_f16_f32 keeps a NaN
+ *   8: + hv_lpips_conv1_f32, hv_lpips_conv2d_f32, hv_lpips_maxpool_f32, hv_lpips_distance_f32, hv_lpips_distance_workspace_bytes
+ *   9: + hv_temporal_spectrum, hv_temporal_spectrum_workspace_bytes
+ * The integer `#define HV_*` constants of this header are what a caller shares with the kernels (sizes, limits, table layouts);
+ * the Python side reads them from here (hunyuanvideo_efficiency_amd/_abi.py). */
+#define HV_ABI_VERSION 9
+int hv_abi_version(void);       /* HV_ABI_VERSION of the header the library was compiled from */
 
 /* K1: nn.LayerNorm(elementwise_affine=False, eps) followed by modulate()
  *     (modules/models.py:161-164,182-185,235,246,338; modules/modulate_layers.py:31-49; mlp_layers.py:115-117)
@@ -80,7 +92,7 @@ int hv_timestep_embedding_bf16(const float* t, void* out, int n_t, int dim, floa
  * issues one call per cu_seqlens segment).  q/k/v/o: token-major, head h at column h*128 of each row;
  * strides in elements (so q,k,v may point into one fused QKV buffer and o into a wider concat buffer).
  * workspace (nullable): caller-owned scratch, used in two steps:
- *   >= HV_ATTN_MIN_WORKSPACE_BYTES (256) and n_kv >= 4096, n_heads <= 62: a pre-pass leaves max_k |k|^2 per head in its first 256
+ *   >= HV_ATTN_MIN_WORKSPACE_BYTES (256) and n_kv >= HV_ATTN_BOUND_MIN_KV (4096), n_heads <= 62: a pre-pass leaves max_k |k|^2 per head in its first 256
  *      bytes and the kernel bounds every score of a query row by |q'| |k|_max; a wave whose rows all have that bound within 90
  *      (log2 units) of their first tile's row max runs against it as a STATIC maximum (no row max per tile, never a rescale:
  *      +4 % at S = 119,056), any other wave keeps the online running maximum - same result up to the rounding of P;
@@ -90,6 +102,7 @@ int hv_timestep_embedding_bf16(const float* t, void* out, int n_t, int dim, floa
  * Without a workspace the single-pass kernel with the online maximum always runs.  A workspace must not be shared by launches
  * that can run concurrently (different streams). */
 #define HV_ATTN_MIN_WORKSPACE_BYTES 256
+#define HV_ATTN_BOUND_MIN_KV 4096
 int hv_attn_fwd_bf16(const void* q, const void* k, const void* v, void* o, int64_t stride_q, int64_t stride_k,
                      int64_t stride_v, int64_t stride_o, int n_q, int n_kv, int n_heads, int head_dim,
                      float scale, void* workspace, int64_t workspace_bytes, hipStream_t stream);
@@ -364,11 +377,15 @@ int64_t hv_lpips_distance_workspace_bytes(int T, int64_t P);
  * mode 1; the DFT of the constant x_0 vanishes there): re_k, im_k = sum_t d_t * twiddle, each one fp32 fmaf chain on the fp32-input MFMA;
  * |X_k|^2 = fl(fl(re^2) + fl(im^2)), |X_k| = sqrtf of it; both summed over series in fp64 through workgroup partials folded in a fixed
  * order (no atomics: run-to-run identical).
- * twiddle: host-built fp32 [Tpad][64 * ncol], Tpad = T rounded up to 32, ncol = max(1, ceil((T/2) / 32)), 16-byte aligned,
- * twiddle_floats >= Tpad * 64 * ncol: column 64 j + c holds cos (c < 32) or sin (c >= 32) of 2 pi ((k t) mod T) / T for bin
- * k = 1 + 32 j + (c & 31), zero for k > T/2 and in rows t >= T.
- * workspace: >= hv_temporal_spectrum_workspace_bytes(mode, C, T, H, W) bytes, 8-byte aligned.  T < 1, T > 1024, C != 3 in mode 0, H or W
- * outside [1, 65536], negative or overlapping strides are HV_ERR_ARG (the workspace query returns 0 for the shapes among them). */
+ * twiddle: host-built fp32 [Tpad][64 * ncol], Tpad = T rounded up to HV_SPECTRUM_BK (32), ncol = max(1, ceil((T/2) / HV_SPECTRUM_BINS)),
+ * 16-byte aligned, twiddle_floats >= Tpad * 64 * ncol: column 64 j + c holds cos (c < 32) or sin (c >= 32) of 2 pi ((k t) mod T) / T for
+ * bin k = 1 + 32 j + (c & 31) (HV_SPECTRUM_BINS = 32 bins per column tile), zero for k > T/2 and in rows t >= T.
+ * workspace: >= hv_temporal_spectrum_workspace_bytes(mode, C, T, H, W) bytes, 8-byte aligned.  T < 1, T > HV_SPECTRUM_MAX_T, C != 3 in
+ * mode 0, H or W outside [1, 65536], negative or overlapping strides are HV_ERR_ARG (the workspace query returns 0 for the shapes among
+ * them). */
+#define HV_SPECTRUM_MAX_T 1024
+#define HV_SPECTRUM_BK 32
+#define HV_SPECTRUM_BINS 32
 int hv_temporal_spectrum(const void* x, int64_t sc, int64_t st, int64_t sh, int dtype, int mode, int C, int T, int H, int W,
                          int rescale, int wr, int wg, int wb, int round, int shift, const float* twiddle, int64_t twiddle_floats,
                          double* mag_sum, double* pow_sum, void* workspace, int64_t workspace_bytes, hipStream_t stream);

@@ -1,7 +1,9 @@
-"""CPU: the C-ABI library loads and exports exactly the symbols include/hv_kernels.h declares, and the
-ctypes table mirrors the header (argument counts).  No compute calls (no GPU here)."""
+"""CPU: the C-ABI library loads and exports exactly the symbols include/hv_kernels.h declares; the ctypes table derived from the
+header equals hand-written pins and the recorded ABI of this version; the constants and the workspace sizing the Python side
+shares with the kernels agree with the built library.  No compute calls (no GPU here)."""
+import ctypes as C
+import json
 import os
-import re
 
 import pytest
 
@@ -9,21 +11,93 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _header_decls():
-    src = open(os.path.join(ROOT, "include", "hv_kernels.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    decls = {}
-    for m in re.finditer(r"\b(?:int|int64_t)\s+(hv_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else len(args.split(","))
-    return decls
+    from hunyuanvideo_efficiency_amd import _abi
+    return {name: len(params) for _, name, params in _abi.DECLS}
 
 
 def test_header_matches_ctypes_table():
+    """The table _lib derives from the header against signatures typed in here by hand from the C declarations: every C type class
+    (device pointers, host arrays, int, int64_t, float, hipStream_t) and both return types, so the parser cannot merely agree with
+    itself."""
     from hunyuanvideo_efficiency_amd import _lib
+    p, i, l, f = C.c_void_p, C.c_int, C.c_int64, C.c_float
+    pins = {
+        "hv_gemm_bf16": ([p, l, p, l, p, i, i, i, p, l, i, i, p, l, i, p, p, l, p], i),
+        "hv_vae_blend_f16": ([p, p, p, p, p, i, i, p], i),
+        "hv_temporal_spectrum": ([p, l, l, l, i, i, i, i, i, i, i, i, i, i, i, i, p, l, p, p, p, l, p], i),
+        "hv_attn_workspace_bytes": ([i, i, i], l),
+        "hv_abi_version": ([], i),
+    }
+    for name, (argtypes, restype) in pins.items():
+        assert _lib.SIGNATURES[name] == argtypes, name
+        assert _lib.RESTYPES[name] is restype, name
     decls = _header_decls()
-    assert set(decls) == set(_lib.SIGNATURES), (set(decls) ^ set(_lib.SIGNATURES))
+    assert set(decls) == set(_lib.SIGNATURES) == set(_lib.RESTYPES), (set(decls) ^ set(_lib.SIGNATURES))
     for name, n in decls.items():
         assert len(_lib.SIGNATURES[name]) == n, name
+    lib = _lib.load()
+    for name in decls:
+        fn = getattr(lib, name)
+        assert fn.argtypes == _lib.SIGNATURES[name] and fn.restype is _lib.RESTYPES[name], name
+
+
+def test_header_equals_recorded_abi():
+    """tests/golden/abi_v<N>.json (written by `python tools/gen_torch_ops.py --record-abi`) holds name, return type and parameter C
+    types of every declaration as of ABI version N: the header's rule "bumped on any signature change" as a test."""
+    from hunyuanvideo_efficiency_amd import _abi, _lib
+    path = os.path.join(ROOT, "tests", "golden", f"abi_v{_lib.ABI_VERSION}.json")
+    hint = (f"include/hv_kernels.h no longer declares what {os.path.relpath(path, ROOT)} recorded for HV_ABI_VERSION {_lib.ABI_VERSION}: "
+            "bump HV_ABI_VERSION (add the change to the list next to it) and record a new file with python tools/gen_torch_ops.py --record-abi")
+    assert os.path.exists(path), hint
+    with open(path) as fh:
+        rec = json.load(fh)
+    assert rec["abi_version"] == _lib.ABI_VERSION, hint
+    now = [{"name": name, "returns": ret, "params": [t for t, _ in params]} for ret, name, params in _abi.DECLS]
+    assert rec["declarations"] == now, hint
+
+
+def test_constants_agree_with_built_library():
+    import torch  # noqa: F401
+    from hunyuanvideo_efficiency_amd import _abi, _lib, metrics, ops, vae_ops
+    M = _abi.MACROS
+    lib = _lib.load()
+    assert lib.hv_abi_version() == M["HV_ABI_VERSION"] == _lib.ABI_VERSION
+    assert ops.ATTN_MIN_WORKSPACE == M["HV_ATTN_MIN_WORKSPACE_BYTES"] == 256 == lib.hv_attn_workspace_bytes(0, 4096, 1)
+    assert vae_ops.GN_FOLD_WS_FLOATS == M["HV_GN_FOLD_WS_FLOATS"] == 16384
+    max_t, bk, bins = M["HV_SPECTRUM_MAX_T"], M["HV_SPECTRUM_BK"], M["HV_SPECTRUM_BINS"]
+    assert (metrics.SPECTRUM_MAX_T, metrics.SPECTRUM_BK, metrics.SPECTRUM_BINS) == (max_t, bk, bins) == (1024, 32, 32)
+    # the kernel's own limit on T is the header's: the workspace query returns 0 for a shape it refuses
+    assert lib.hv_temporal_spectrum_workspace_bytes(1, 4, max_t, 8, 8) > 0
+    assert lib.hv_temporal_spectrum_workspace_bytes(1, 4, max_t + 1, 8, 8) == 0
+    with pytest.raises(_lib.HVKernelError):
+        metrics.spectrum_twiddles(max_t + 1)
+    # layout of the twiddle table the caller builds: k-chunks of BK frames, per column tile a cos and a sin block of BINS bins
+    for T in (1, 33, 1024):
+        ncol = max(1, -(-(T // 2) // bins))
+        assert tuple(metrics.spectrum_twiddles(T).shape) == (-(-T // bk) * bk, 2 * bins * ncol), T
+
+
+def test_attention_workspace_sizing_follows_the_kernels_split_rule():
+    """ops._attn_workspace_bytes: nothing below HV_ATTN_BOUND_MIN_KV keys, the full split workspace exactly where the kernel's rule
+    (hv_attn_suggest_splits) splits, the 256-byte key-norm bound elsewhere."""
+    from hunyuanvideo_efficiency_amd import _abi, _lib, ops
+    assert _abi.MACROS["HV_ATTN_BOUND_MIN_KV"] == 4096
+    assert _lib.host("attn_suggest_splits", 118811, 118811, 3) == 2 and _lib.host("attn_suggest_splits", 118811, 118811, 24) == 1
+    kinds = set()
+    for n_q in (1, 255, 256, 257, 4133, 65537, 118811):
+        for heads in (1, 2, 3, 6, 24, 62):
+            for n_kv in (4095, 4096, 12345, 118811):
+                got = ops._attn_workspace_bytes(n_q, n_kv, heads)
+                if n_kv < 4096:
+                    want = 0
+                elif ops.attn_suggest_splits(n_q, n_kv, heads) == 2:
+                    want = 256 + 2 * n_q * heads * 130 * 4
+                    assert want == _lib.host("attn_workspace_bytes", n_q, n_kv, heads)
+                else:
+                    want = 256
+                assert got == want, (n_q, n_kv, heads, got, want)
+                kinds.add(min(want, 257))
+    assert kinds == {0, 256, 257}            # the grid reaches all three answers
 
 
 def test_library_loads_and_exports_every_symbol():
@@ -93,9 +167,9 @@ def test_generated_attention_iteration_ignores_env_and_is_up_to_date_and_consist
     # ... and the built library was compiled from exactly this file (not from a stale one, not from a timing experiment's)
     import ctypes
     from hunyuanvideo_efficiency_amd import _lib
-    sig = int(re.search(r"#define HV_W4_LOOP_SIGNATURE 0x([0-9a-f]{8})u", open(g.OUT).read()).group(1), 16)
+    assert os.path.samefile(g.OUT, _lib.LOOP_INC)
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    assert (lib.hv_attn_w4_loop_signature() & 0xFFFFFFFF) == sig, "libhv_kernels.so is not built from the in-tree iteration: make -C hunyuanvideo_efficiency_amd/csrc"
+    assert (lib.hv_attn_w4_loop_signature() & 0xFFFFFFFF) == _lib.loop_signature_in_tree(), "libhv_kernels.so is not built from the in-tree iteration: make -C hunyuanvideo_efficiency_amd/csrc"
     body = g.gen_iter(0)
     gaps, cur = [], None
     for ln in body:
