@@ -8,7 +8,10 @@ only if imageio is importable - otherwise an .mp4 pair is an error, not a silent
 and averaged over all frames of all pairs; the result file has the reference's lines.  LPIPS (AlexNet, the reference's
 compute_lpips) is scored only with --lpips-alexnet PATH [--lpips-linear PATH]: the weights are user-supplied (a torchvision AlexNet
 state dict plus the LPIPS linear file, or one full LPIPS state dict), none are shipped or fetched; without them the result file has no
-`LPIPS` line.  uint8 frames (.npy, .mp4) go through the rescale=False path, so the network sees exactly those bytes."""
+`LPIPS` line.  --fvd-i3d PATH (the I3D state dict i3d_pretrained_400.pt, user-supplied) adds an `FVD:` line when at least two pairs were
+scored; with an --fvd-* flag a pair of fewer than ten common frames is an error that stops the run (the reference asserts the same), it is
+not skipped: "FVD (videogpt I3D logits)", the fork's calculate_fvd with method='videogpt' - not interchangeable with
+the styleganv variant; --fvd-synthetic runs it under stand-in weights (not comparable with any published value).  uint8 frames (.npy, .mp4) go through the rescale=False path, so the network sees exactly those bytes."""
 import argparse
 import os
 import sys
@@ -31,9 +34,13 @@ def parse_args(argv=None):
     p.add_argument("--lpips-alexnet", type=str, default=None, help="score LPIPS too: a torchvision AlexNet state dict (needs --lpips-linear), "
                                                                    "or one full LPIPS state dict (.pt / .pth / .safetensors; weights are not shipped)")
     p.add_argument("--lpips-linear", type=str, default=None, help="the LPIPS linear layers (lin{0..4}.model.1.weight)")
+    from hunyuanvideo_efficiency_amd.metrics import add_fvd_arguments
+    add_fvd_arguments(p)
     a = p.parse_args(argv)
     if a.lpips_linear and not a.lpips_alexnet:
         p.error("--lpips-linear needs --lpips-alexnet")
+    if a.fvd_i3d and a.fvd_synthetic:
+        p.error("--fvd-synthetic and --fvd-i3d exclude each other")
     return a
 
 
@@ -76,14 +83,14 @@ def read_video(path):
     return x, True
 
 
-def score_folders(root1, root2, results_dir, device="cuda", lpips=None):
+def score_folders(root1, root2, results_dir, device="cuda", lpips=None, fvd=None):
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator
     names = pair_files(root1, root2)
     if not names:
         print(f"No matching video files between {root1} and {root2}.")
         return None
     print(f"Found {len(names)} matching pairs.")
-    acc = MetricsAccumulator(lpips=lpips)
+    acc = MetricsAccumulator(lpips=lpips, fvd=fvd)
     for name in names:
         v1, r1 = read_video(os.path.join(root1, name))
         v2, r2 = read_video(os.path.join(root2, name))
@@ -95,7 +102,7 @@ def score_folders(root1, root2, results_dir, device="cuda", lpips=None):
               + f" ({len(m['psnr'])} frames)")
     results = acc.result()
     path = acc.save(results_dir, root1, root2)
-    print(f"Results: {results}\nSaved to {path}")
+    print(f"Results: {results}{acc.fvd_note()}\nSaved to {path}")
     return path
 
 
@@ -105,10 +112,12 @@ def main(argv=None):
     if a.lpips_alexnet:
         from hunyuanvideo_efficiency_amd.metrics import LpipsAlex
         lpips = LpipsAlex.from_files(a.lpips_alexnet, a.lpips_linear)
+    from hunyuanvideo_efficiency_amd.metrics import fvd_from_args
+    fvd = fvd_from_args(a)
     subdirs = sorted(d for d in os.listdir(a.root2) if os.path.isdir(os.path.join(a.root2, d)))
     if subdirs and not list_videos(a.root2):            # one folder per experiment: one result file each
-        return [score_folders(a.root1, os.path.join(a.root2, d), os.path.join(a.results_dir, d), lpips=lpips) for d in subdirs]
-    return [score_folders(a.root1, a.root2, a.results_dir, lpips=lpips)]
+        return [score_folders(a.root1, os.path.join(a.root2, d), os.path.join(a.results_dir, d), lpips=lpips, fvd=fvd) for d in subdirs]
+    return [score_folders(a.root1, a.root2, a.results_dir, lpips=lpips, fvd=fvd)]
 
 
 if __name__ == "__main__":

@@ -112,6 +112,33 @@ __device__ __forceinline__ uint32_t quantise(float x, int rescale) {
     return (uint32_t)(int)__fmul_rn(x, 255.0f);
 }
 
+// The fp32-input MFMA block tile of the scoring networks' implicit-GEMM convolutions (hv_lpips.hip, hv_i3d.hip): 128 output rows x 64
+// output channels x 32 k per step, four waves of 64 x 32 with two independent 32x32 accumulators each, on v_mfma_f32_32x32x2_f32 (fp32
+// in, fp32 accumulate: every output element is one k-ordered fmaf chain, whatever tile it falls in).  LDS tiles are k-major: the 32 lanes
+// that share a k read 32 consecutive dwords (conflict-free ds_read_b32); the A rows are 130 dwords long so that a loader's 8 rows x 8
+// k-quads of one wave spread over all banks.
+namespace f32tile {
+constexpr int kThreads = 256;
+constexpr int BM = 128, BN = 64, BK = 32;
+constexpr int LDA = BM + 2;
+
+// the MFMAs of one staged k-chunk: sA [BK][LDA], sB [BK][BN]; wave tile at rows wm, columns wn
+__device__ __forceinline__ void mma_chunk(const float* sA, const float* sB, int wm, int wn, int lr, int lk, f32x16& acc0, f32x16& acc1) {
+#pragma unroll
+    for (int ks = 0; ks < BK / 2; ++ks) {
+        const int k = ks * 2 + lk;
+        const float a0 = sA[k * LDA + wm + lr], a1 = sA[k * LDA + wm + 32 + lr];
+        const float b = sB[k * BN + wn + lr];
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b, acc1, 0, 0, 0);
+    }
+}
+// C/D map of the 32x32 forms: column = lane & 31, row of register r = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+__device__ __forceinline__ int acc_row(int r, int lk) { return (r & 3) + 8 * (r >> 2) + 4 * lk; }
+}  // namespace f32tile
+
+static inline bool hv_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // Raising a kernel's dynamic-LDS limit is a per-DEVICE attribute: one process may drive several GPUs, so the "already done"
 // flag is kept per device ordinal (hipGetDevice is a thread-local read, no driver call).
 struct HvPerDeviceOnce { bool done[64] = {}; };

@@ -10,19 +10,16 @@
 //   lpips_distance_kernel / fold  per pixel: both channel norms, sum_c lin[c] (f0/(|f0|+1e-10) - f1/(|f1|+1e-10))^2; fp64 workgroup
 //                                 partials to a workspace, one wave per frame folds them in a fixed order (no atomics)
 //
-// The convolutions are implicit GEMMs on v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate: every output element is one k-ordered fmaf
-// chain, whatever tile it falls in).  Block tile 128 (output pixels, across image boundaries) x 64 (output channels) x 32 (k); four
-// waves of 64 x 32, two independent 32x32 accumulators each.  LDS tiles are k-major: the 32 lanes that share a k read 32 consecutive
-// dwords (conflict-free ds_read_b32); the A rows are 130 dwords long so that the loader's 8 rows x 8 k-quads of one wave spread over
-// all banks (2-way at most, free for ds_write_b32).  The next k-chunk is fetched into registers while the MFMAs of this one run.
+// The convolutions are implicit GEMMs on the fp32-input MFMA block tile of hv_common.hpp (f32tile: 128 output pixels, across image
+// boundaries, x 64 output channels x 32 k; every output element is one k-ordered fmaf chain, whatever tile it falls in).  The loader's
+// 8 rows x 8 k-quads of one wave spread over all LDS banks (2-way at most, free for ds_write_b32).  The next k-chunk is fetched into
+// registers while the MFMAs of this one run.
 #include "hv_common.hpp"
 #include "../../include/hv_kernels.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int BM = 128, BN = 64, BK = 32;
-constexpr int LDA = BM + 2;
+using namespace f32tile;
 constexpr int kK1 = 3 * 11 * 11;             // 363: k = (c * 11 + ky) * 11 + kx of the first layer, zero-padded to 384
 constexpr int kMaxC = 384;                   // widest tap
 constexpr int kDistMaxWg = 256;              // distance workgroups per frame
@@ -175,23 +172,15 @@ __global__ __launch_bounds__(kThreads) void lpips_conv_kernel(const Loader ld, c
             ld.fetch(st, kc + 1, tid);
             fetch_b(kc + 1);
         }
-#pragma unroll
-        for (int ks = 0; ks < BK / 2; ++ks) {
-            const int k = ks * 2 + lk;
-            const float a0 = sA[k * LDA + wm + lr], a1 = sA[k * LDA + wm + 32 + lr];
-            const float b = sB[k * BN + wn + lr];
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b, acc1, 0, 0, 0);
-        }
+        mma_chunk(sA, sB, wm, wn, lr, lk, acc0, acc1);
         __syncthreads();
     }
 
-    // C/D map of the 32x32 forms: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
     const int n = n0 + wn + lr;
     const float bv = bias[n];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * lk;
+        const int row = acc_row(r, lk);
         const int64_t ma = m0 + wm + row, mb = ma + 32;
         if (ma < M) y[ma * Cout + n] = fmaxf(acc0[r] + bv, 0.f);
         if (mb < M) y[mb * Cout + n] = fmaxf(acc1[r] + bv, 0.f);
@@ -279,7 +268,6 @@ inline int dist_wgs(int64_t P) {
     const int64_t n = (P + 63) / 64;
     return (int)(n < 1 ? 1 : n > kDistMaxWg ? kDistMaxWg : n);
 }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 template <typename Loader>
 int launch_conv(const Loader& ld, const float* w, const float* bias, float* y, const float* lut, int64_t M, int OH, int OW, int pad, int Cout,
@@ -308,7 +296,7 @@ extern "C" int hv_lpips_conv1_f32(const void* a, int64_t a_sc, int64_t a_st, int
     if (!a || !b || !lut || !w || !bias || !y || (dtype != 0 && dtype != 1) || (rescale != 0 && rescale != 1)) return HV_ERR_ARG;
     if (T < 1 || T > 32767 || H < 31 || W < 31 || H > (1 << 16) || W > (1 << 16)) return HV_ERR_ARG;
     if (a_sh < W || b_sh < W || a_sc < 0 || a_st < 0 || b_sc < 0 || b_st < 0) return HV_ERR_ARG;
-    if (!aligned16(w)) return HV_ERR_ARG;
+    if (!hv_aligned16(w)) return HV_ERR_ARG;
     const Strides sa{a_sc, a_st, a_sh}, sb{b_sc, b_st, b_sh};
     if (dtype == 0) return launch_conv1<_Float16>(a, sa, b, sb, T, H, W, rescale, lut, w, bias, y, stream);
     return launch_conv1<float>(a, sa, b, sb, T, H, W, rescale, lut, w, bias, y, stream);
@@ -321,7 +309,7 @@ extern "C" int hv_lpips_conv2d_f32(const float* x, const float* w, const float* 
     if (ksize < 1 || ksize > 11 || pad < 0 || pad >= ksize) return HV_ERR_ARG;
     const int OH = H + 2 * pad - ksize + 1, OW = W + 2 * pad - ksize + 1;
     if (OH < 1 || OW < 1 || (int64_t)N * H * W > 0x7fffffff || (int64_t)N * OH * OW > 0x7fffffff) return HV_ERR_ARG;
-    if (!aligned16(x) || !aligned16(w)) return HV_ERR_ARG;
+    if (!hv_aligned16(x) || !hv_aligned16(w)) return HV_ERR_ARG;
     Feature ld;
     ld.x = x; ld.H = H; ld.W = W; ld.Cin = Cin; ld.KS = ksize;
     return launch_conv(ld, w, bias, y, nullptr, (int64_t)N * OH * OW, OH, OW, pad, Cout, ksize * ksize * Cin / BK, stream);
@@ -329,7 +317,7 @@ extern "C" int hv_lpips_conv2d_f32(const float* x, const float* w, const float* 
 
 extern "C" int hv_lpips_maxpool_f32(const float* x, float* y, int N, int H, int W, int C, hipStream_t stream) {
     if (!x || !y || N < 1 || H < 3 || W < 3 || H > (1 << 16) || W > (1 << 16) || C < 4 || C % 4 != 0 || C > 4096) return HV_ERR_ARG;
-    if (!aligned16(x) || !aligned16(y)) return HV_ERR_ARG;
+    if (!hv_aligned16(x) || !hv_aligned16(y)) return HV_ERR_ARG;
     const int OH = (H - 3) / 2 + 1, OW = (W - 3) / 2 + 1;
     const int64_t total = (int64_t)N * OH * OW * (C / 4);
     const int64_t blocks = (total + kThreads - 1) / kThreads;

@@ -1,5 +1,5 @@
-"""PSNR / SSIM / LPIPS of a reconstruction against its input and temporal spectra, on the device (csrc/hv_metrics.hip, hv_lpips.hip,
-hv_spectrum.hip).
+"""PSNR / SSIM / LPIPS of a reconstruction against its input, temporal spectra and FVD, on the device (csrc/hv_metrics.hip, hv_lpips.hip,
+hv_spectrum.hip, hv_i3d.hip).
 
 The fork's study scores reconstructions with evaluation/compute_metrics.py: per frame `compute_psnr` / `compute_ssim` (skimage) on
 the 8-bit frames of an mp4 that `save_videos_grid(..., rescale=True)` wrote, averaged over all frames of an experiment.  Here the
@@ -13,6 +13,9 @@ tests and timing, whose scores are not comparable with published LPIPS.  Parity 
 neither torchvision nor the `lpips` package is part of this environment.
 Temporal spectra (`temporal_spectrum`, `spectrum_report`; csrc/hv_spectrum.hip) restate the fork's theory_analysis.ipynb: the mean
 |FFT| over all pixel time series of the gray frames and over all latent series, as one fp32-MFMA DFT whose product never leaves the chip.
+FVD (`I3D`, `fvd_logits`, `frechet_distance`; csrc/hv_i3d.hip) is the `method='videogpt'` path of the fork's calculate_fvd: Inception-I3D
+logits of every input clip and every reconstruction as fp32-MFMA 3-D convolutions, then the Frechet distance on the host.  Its weights are
+user-supplied too.  The value is "FVD (videogpt I3D logits)", not interchangeable with the styleganv variant (a TorchScript archive).
 What it is not: there is no video codec in between (the reference's frames went through libx264).  CPU tensors are refused like
 everywhere else in the package."""
 from __future__ import annotations
@@ -325,6 +328,343 @@ def lpips_video(ref: torch.Tensor, rec: torch.Tensor, model: LpipsAlex, rescale:
     return (total, layers) if return_layers else total
 
 
+# ---- FVD: Inception-I3D logits (csrc/hv_i3d.hip) and the Frechet distance -----------------------------------------------------------------
+# The fork's rebuttal/common_metrics_on_video_quality/calculate_fvd.py with method='videogpt': fvd/videogpt/pytorch_i3d.py is the network,
+# fvd/videogpt/fvd.py the preprocessing and the distance.  The number is "FVD (videogpt I3D logits)": it is NOT interchangeable with the
+# styleganv variant (a TorchScript detector, pickled code this package does not load), which is the default of the fork's run.py.
+FVD_LABEL = "FVD (videogpt I3D logits)"
+FVD_NOTE = "not interchangeable with the styleganv variant"
+I3D_CLASSES = 400
+I3D_MIN_FRAMES = 10          # calculate_fvd.py:33 asserts it
+I3D_SIZE = 224
+I3D_MIN_SIDE = 193           # the smallest side whose five halvings end at 7, what the head's 7 x 7 average pool needs
+I3D_BN_EPS = 1e-5
+
+# Inception modules (pytorch_i3d.py:229-272): name, Cin, (b0, b1a, b1b, b2a, b2b, b3b) output channels
+I3D_MIXED = (("Mixed_3b", 192, (64, 96, 128, 16, 32, 32)), ("Mixed_3c", 256, (128, 128, 192, 32, 96, 64)),
+             ("Mixed_4b", 480, (192, 96, 208, 16, 48, 64)), ("Mixed_4c", 512, (160, 112, 224, 24, 64, 64)),
+             ("Mixed_4d", 512, (128, 128, 256, 24, 64, 64)), ("Mixed_4e", 512, (112, 144, 288, 32, 64, 64)),
+             ("Mixed_4f", 528, (256, 160, 320, 32, 128, 128)), ("Mixed_5b", 832, (256, 160, 320, 32, 128, 128)),
+             ("Mixed_5c", 832, (384, 192, 384, 48, 128, 128)))
+_I3D_POOL_BEFORE = {"Mixed_4b": ("MaxPool3d_4a_3x3", (3, 3, 3), (2, 2, 2)), "Mixed_5b": ("MaxPool3d_5a_2x2", (2, 2, 2), (2, 2, 2))}
+
+
+def _i3d_layer_table():
+    """The network as one flat table, in launch order: (name, kind, Cin, Cout, kernel, stride, source, destination), kind "conv" | "pool"
+    | "head", source / destination = (buffer, first column, row pitch).  Buffers 0 and 1 alternate as the current feature map, 2 is an
+    Inception module's scratch ([b1a | b2a | pooled input] side by side), -1 the 4-channel input, -2 the logits.  A conv's name is its
+    state-dict prefix."""
+    rows = []
+    one, three = (1, 1, 1), (3, 3, 3)
+    rows.append(("Conv3d_1a_7x7", "conv", 4, 64, (7, 7, 7), (2, 2, 2), (-1, 0, 4), (0, 0, 64)))
+    rows.append(("MaxPool3d_2a_3x3", "pool", 64, 64, (1, 3, 3), (1, 2, 2), (0, 0, 64), (1, 0, 64)))
+    rows.append(("Conv3d_2b_1x1", "conv", 64, 64, one, one, (1, 0, 64), (0, 0, 64)))
+    rows.append(("Conv3d_2c_3x3", "conv", 64, 192, three, one, (0, 0, 64), (1, 0, 192)))
+    rows.append(("MaxPool3d_3a_3x3", "pool", 192, 192, (1, 3, 3), (1, 2, 2), (1, 0, 192), (0, 0, 192)))
+    cur, width = 0, 192
+    for name, cin, (o0, o1, o2, o3, o4, o5) in I3D_MIXED:
+        assert cin == width, name
+        if name in _I3D_POOL_BEFORE:
+            pname, k, s = _I3D_POOL_BEFORE[name]
+            rows.append((pname, "pool", cin, cin, k, s, (cur, 0, cin), (1 - cur, 0, cin)))
+            cur = 1 - cur
+        out, cout, sp = 1 - cur, o0 + o2 + o4 + o5, o1 + o3 + cin
+        src = (cur, 0, cin)
+        rows.append((f"{name}.b0", "conv", cin, o0, one, one, src, (out, 0, cout)))
+        rows.append((f"{name}.b1a", "conv", cin, o1, one, one, src, (2, 0, sp)))
+        rows.append((f"{name}.b1b", "conv", o1, o2, three, one, (2, 0, sp), (out, o0, cout)))
+        rows.append((f"{name}.b2a", "conv", cin, o3, one, one, src, (2, o1, sp)))
+        rows.append((f"{name}.b2b", "conv", o3, o4, three, one, (2, o1, sp), (out, o0 + o2, cout)))
+        rows.append((f"{name}.b3a", "pool", cin, cin, three, one, src, (2, o1 + o3, sp)))
+        rows.append((f"{name}.b3b", "conv", cin, o5, one, one, (2, o1 + o3, sp), (out, o0 + o2 + o4, cout)))
+        cur, width = out, cout
+    rows.append(("logits", "head", width, I3D_CLASSES, (2, 7, 7), one, (cur, 0, width), (-2, 0, I3D_CLASSES)))
+    return tuple(rows)
+
+
+I3D_LAYERS = _i3d_layer_table()
+I3D_CONVS = tuple((r[0], 3 if r[0] == "Conv3d_1a_7x7" else r[2], r[3], r[4]) for r in I3D_LAYERS if r[1] == "conv")   # state-dict shapes
+
+
+def i3d_same_pad(k: int, s: int, extent: int):
+    """The TF-"same" rule of pytorch_i3d.py:9-30,71-93 for one axis -> (cells of zero padding in front, output extent): the total is
+    max(k - s, 0) if extent % s == 0 else max(k - extent % s, 0), the front gets total // 2, the output is ceil(extent / s)."""
+    total = max(k - s, 0) if extent % s == 0 else max(k - extent % s, 0)
+    return total // 2, -(-extent // s)
+
+
+def i3d_walk(T: int, H: int, W: int):
+    """I3D_LAYERS with extents: yields (row, input extents (T, H, W), output extents, front pads) per layer"""
+    ext = {-1: (T, H, W)}
+    for row in I3D_LAYERS:
+        _, kind, _, _, k, s, src, dst = row
+        e = ext[src[0]]
+        if kind == "head":
+            yield row, e, (1, 1, 1), (0, 0, 0)
+            continue
+        pads, out = zip(*(i3d_same_pad(k[a], s[a], e[a]) for a in range(3)))
+        ext[dst[0]] = tuple(out)
+        yield row, e, tuple(out), tuple(pads)
+
+
+def i3d_buffer_plan(T: int, H: int, W: int) -> dict:
+    """Floats of the three feature buffers a [T,H,W,4] input needs (each reused across layers: the largest voxels x pitch it ever holds),
+    the frames T' of the last map, and the peak in bytes - input, buffers and the head's workspace together."""
+    floats = [0, 0, 0]
+    head_t = None
+    for (name, kind, _, _, _, _, src, dst), e, o, _ in i3d_walk(T, H, W):
+        if kind == "head":
+            head_t = e[0]
+            if e[1] != 7 or e[2] != 7 or e[0] < 2:
+                raise _lib.HVKernelError(f"I3D: a {T} x {H} x {W} input ends in a {e[0]} x {e[1]} x {e[2]} map; the head needs T' >= 2 and "
+                                         f"7 x 7 (T >= 9 frames, {I3D_MIN_SIDE} <= H, W <= {I3D_SIZE})")
+            continue
+        floats[dst[0]] = max(floats[dst[0]], o[0] * o[1] * o[2] * dst[2])
+    ws = (head_t - 1) * 1024
+    return {"floats": floats, "head_frames": head_t, "workspace_floats": ws,
+            "peak_bytes": 4 * (T * H * W * 4 + sum(floats) + ws + I3D_CLASSES)}
+
+
+def i3d_pack_conv(w: torch.Tensor) -> torch.Tensor:
+    """torch [Cout, Cin, kt, kh, kw] -> the kernel's k-major [Kpad, Cout], k = ((dt * kh + dh) * kw + dw) * Cin + ci; a 3-channel input
+    layer gets a zero fourth channel, K is rounded up to 32 with zero rows"""
+    co, ci = w.shape[:2]
+    if ci % 4:
+        w = torch.cat([w, torch.zeros(co, 4 - ci % 4, *w.shape[2:], dtype=w.dtype)], dim=1)
+    k = w.permute(2, 3, 4, 1, 0).reshape(-1, co)
+    out = torch.zeros(-(-k.shape[0] // 32) * 32, co, dtype=torch.float32)
+    out[:k.shape[0]] = k
+    return out
+
+
+def i3d_fold_bn(gamma, beta, mean, var, eps: float = I3D_BN_EPS):
+    """eval-mode BatchNorm3d as y = x * sc + sh: sc = gamma / sqrt(var + eps), sh = beta - mean * sc, in fp64, each rounded to fp32 once"""
+    g, b, m, v = (t.detach().double().cpu() for t in (gamma, beta, mean, var))
+    sc = g / torch.sqrt(v + eps)
+    return sc.float(), (b - m * sc).float()
+
+
+class I3D:
+    """Weights of the reference's InceptionI3d(400, in_channels=3) in eval mode, under its state-dict names (`Conv3d_1a_7x7.conv3d.weight`,
+    `Mixed_4b.b1b.bn.running_var`, `logits.conv3d.bias`, ...).  USER-SUPPLIED (i3d_pretrained_400.pt is a plain state dict); none ship
+    with the package.  Built on the host; the BatchNorm fold and the packed device copies are made once per device."""
+
+    def __init__(self, sd: dict, label: str = "user"):
+        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+        self.sd, self.label = {}, label
+
+        def take(key, shape):
+            if key not in sd:
+                raise ValueError(f"I3D weights: missing key {key!r}")
+            t = sd[key]
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape):
+                raise ValueError(f"I3D weights: {key!r} must be a tensor of shape {tuple(shape)}, got "
+                                 f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+            self.sd[key] = t.detach().float().cpu().contiguous()
+
+        for name, ci, co, k in I3D_CONVS:
+            take(f"{name}.conv3d.weight", (co, ci, *k))
+            for p in ("weight", "bias", "running_mean", "running_var"):
+                take(f"{name}.bn.{p}", (co,))
+        take("logits.conv3d.weight", (I3D_CLASSES, 1024, 1, 1, 1))
+        take("logits.conv3d.bias", (I3D_CLASSES,))
+        self._dev = {}
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, label: str = "user") -> "I3D":
+        return cls(sd, label)
+
+    @classmethod
+    def from_file(cls, path) -> "I3D":
+        """A tensor file read without executing anything from it (checkpoint.read_tensors: .pt / .pth with weights_only, .safetensors)."""
+        from .checkpoint import read_tensors
+        return cls(read_tensors(path))
+
+    @classmethod
+    def synthetic(cls, seed: int = 0) -> "I3D":
+        """Deterministic stand-in weights: conv hashed_uniform * sqrt(6 / fan_in) (He), BatchNorm gamma in [0.8, 1.2], beta and running
+        mean in [-0.1, 0.1], running variance in [0.5, 1.5], logits bias in [-0.1, 0.1].  About half of every layer's units stay live.
+        Distances under them are NOT comparable with published FVD."""
+        from .synthetic import hashed_uniform as hu
+        sd = {}
+        for name, ci, co, k in I3D_CONVS:
+            sd[f"{name}.conv3d.weight"] = hu((co, ci, *k), f"i3d.{name}.weight", seed) * math.sqrt(6.0 / (ci * k[0] * k[1] * k[2]))
+            sd[f"{name}.bn.weight"] = 1.0 + 0.2 * hu((co,), f"i3d.{name}.gamma", seed)
+            sd[f"{name}.bn.bias"] = 0.1 * hu((co,), f"i3d.{name}.beta", seed)
+            sd[f"{name}.bn.running_mean"] = 0.1 * hu((co,), f"i3d.{name}.mean", seed)
+            sd[f"{name}.bn.running_var"] = 1.0 + 0.5 * hu((co,), f"i3d.{name}.var", seed)
+        sd["logits.conv3d.weight"] = hu((I3D_CLASSES, 1024, 1, 1, 1), "i3d.logits.weight", seed) * math.sqrt(6.0 / 1024)
+        sd["logits.conv3d.bias"] = 0.1 * hu((I3D_CLASSES,), "i3d.logits.bias", seed)
+        return cls(sd, label="synthetic")
+
+    def state_dict(self) -> dict:
+        """the tensors under the reference's key names (fp32, host)"""
+        return dict(self.sd)
+
+    def folded(self, name: str):
+        """(sc, sh) fp32 of conv `name`: its BatchNorm folded"""
+        return i3d_fold_bn(*(self.sd[f"{name}.bn.{p}"] for p in ("weight", "bias", "running_mean", "running_var")))
+
+    def on(self, device) -> dict:
+        """{conv name: (packed w, sc, sh)} and "logits": (w [1024, 400], bias) on `device`"""
+        device = torch.device(device)
+        if device not in self._dev:
+            d = {}
+            for name, _, _, _ in I3D_CONVS:
+                sc, sh = self.folded(name)
+                d[name] = (i3d_pack_conv(self.sd[f"{name}.conv3d.weight"]).to(device), sc.to(device), sh.to(device))
+            d["logits"] = (self.sd["logits.conv3d.weight"].reshape(I3D_CLASSES, 1024).T.contiguous().to(device),
+                           self.sd["logits.conv3d.bias"].to(device))
+            self._dev[device] = d
+        return self._dev[device]
+
+
+def _i3d_buffers(plan, dev):
+    return ([torch.empty(max(n, 4), dtype=torch.float32, device=dev) for n in plan["floats"]],
+            torch.empty(plan["workspace_floats"], dtype=torch.float32, device=dev))
+
+
+def _i3d_enqueue(x_cl, wts, bufs, ws, out):
+    """the launches of one clip: x_cl [T,H,W,4] fp32 contiguous -> out [400]"""
+    T, H, W, _ = x_cl.shape
+    flat = {-1: x_cl.reshape(-1), -2: out, 0: bufs[0], 1: bufs[1], 2: bufs[2]}
+    for (name, kind, ci, co, k, s, src, dst), e, _, pads in i3d_walk(T, H, W):
+        x, y = flat[src[0]][src[1]:], flat[dst[0]][dst[1]:]
+        if kind == "conv":
+            w, sc, sh = wts[name]
+            _lib.call("i3d_conv3d_f32", x, src[2], w, sc, sh, y, dst[2], e[0], e[1], e[2], ci, co, *k, *s, *pads, 1)
+        elif kind == "pool":
+            _lib.call("i3d_maxpool3d_f32", x, src[2], y, dst[2], e[0], e[1], e[2], ci, *k, *s, *pads)
+        else:
+            w, b = wts["logits"]
+            _lib.call("i3d_head_f32", x, src[2], w, b, y, e[0], e[1], e[2], ci, ws, ws.numel())
+
+
+def _check_i3d_model(model):
+    if not isinstance(model, I3D):
+        raise TypeError(f"fvd: expected an I3D, got {type(model).__name__}")
+
+
+def i3d_logits(x_cl: torch.Tensor, model: I3D) -> torch.Tensor:
+    """The network alone: x_cl [T,H,W,4] fp32 on the GPU (channels-last voxels, channel 3 = 0; 193 <= H, W <= 224, T >= 9 so that the
+    last map is T' >= 2 frames of 7 x 7) -> float32 [400] on the device.  Nothing is synchronised."""
+    _check_i3d_model(model)
+    if not isinstance(x_cl, torch.Tensor) or not x_cl.is_cuda:
+        raise _lib.HVKernelError("i3d_logits: expected a GPU tensor (this package has no CPU path)")
+    if x_cl.dtype != torch.float32 or x_cl.dim() != 4 or x_cl.shape[-1] != 4 or not x_cl.is_contiguous():
+        raise _lib.HVKernelError(f"i3d_logits: expected a contiguous fp32 [T,H,W,4] tensor, got {x_cl.dtype} {tuple(x_cl.shape)}")
+    T, H, W, _ = x_cl.shape
+    plan = i3d_buffer_plan(T, H, W)
+    bufs, ws = _i3d_buffers(plan, x_cl.device)
+    out = torch.empty(I3D_CLASSES, dtype=torch.float32, device=x_cl.device)
+    _i3d_enqueue(x_cl, model.on(x_cl.device), bufs, ws, out)
+    return out
+
+
+def i3d_resized(H: int, W: int):
+    """(RH, RW) of fvd.py:32-36 in its own double arithmetic: the shorter side goes to 224, the other to ceil(side * (224 / min(H, W)))"""
+    scale = I3D_SIZE / min(H, W)
+    return (I3D_SIZE, math.ceil(W * scale)) if H < W else (math.ceil(H * scale), I3D_SIZE)
+
+
+def fvd_preprocess(video: torch.Tensor, rescale: bool = True) -> torch.Tensor:
+    """[3,T,H,W] fp16 / fp32 GPU video (values in [-1, 1] with rescale, [0, 1] without; W contiguous, strided views allowed) -> the
+    network input [T,224,224,4] fp32 (fvd.py:21-60 on the 8-bit frames every other score sees; channel 3 = 0)"""
+    _check_video(video, "video")
+    if video.dim() != 4 or video.shape[0] != 3:
+        raise _lib.HVKernelError(f"fvd: expected one RGB clip [3,T,H,W], got {tuple(video.shape)}")
+    _, T, H, W = video.shape
+    RH, RW = i3d_resized(H, W)
+    y = torch.empty(T, I3D_SIZE, I3D_SIZE, 4, dtype=torch.float32, device=video.device)
+    _lib.call("i3d_preprocess", video, video.stride(0), video.stride(1), video.stride(2), _DTYPES[video.dtype], T, H, W, RH, RW,
+              1 if rescale else 0, y)
+    return y
+
+
+def fvd_logits(video: torch.Tensor, model: I3D, rescale: bool = True) -> torch.Tensor:
+    """I3D logits of one clip [3,T,H,W] (or of each clip of a batch [B,3,T,H,W], one after another: clip i of a batch equals its single
+    run bit for bit) -> float32 [400] ([B,400]) on the device.  T >= 10, as the reference asserts, else ValueError.  Nothing is
+    synchronised."""
+    _check_i3d_model(model)
+    _check_video(video, "video")
+    clips = video[None] if video.dim() == 4 else video
+    if clips.shape[1] != 3:
+        raise _lib.HVKernelError(f"fvd: expected RGB clips, got C = {clips.shape[1]}")
+    T = clips.shape[2]
+    if T < I3D_MIN_FRAMES:
+        raise ValueError(f"fvd: a clip needs at least {I3D_MIN_FRAMES} frames, got {T}")
+    dev = clips.device
+    bufs, ws = _i3d_buffers(i3d_buffer_plan(T, I3D_SIZE, I3D_SIZE), dev)
+    wts = model.on(dev)
+    out = torch.empty(clips.shape[0], I3D_CLASSES, dtype=torch.float32, device=dev)
+    for b in range(clips.shape[0]):           # one stream: clip b + 1 reuses the buffers after clip b's launches
+        _i3d_enqueue(fvd_preprocess(clips[b], rescale), wts, bufs, ws, out[b])
+    return out[0] if video.dim() == 4 else out
+
+
+def _sym_sqrt(mat: np.ndarray, eps: float = 1e-10) -> np.ndarray:
+    """fvd.py:68-71: u diag(s < eps ? s : sqrt(s)) v^T of the SVD"""
+    u, s, vt = np.linalg.svd(mat)
+    return (u * np.where(s < eps, s, np.sqrt(s))) @ vt
+
+
+def frechet_distance(f1, f2) -> float:
+    """fvd.py:113-125 on the host in fp64: f1 [N1, D], f2 [N2, D] feature sets (numpy or tensors) ->
+    tr(S1 + S2) - 2 tr((S1^1/2 S2 S1^1/2)^1/2) + |m1 - m2|^2 with unbiased covariances; the mean term alone for one sample."""
+    x1, x2 = (np.asarray(f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else f, dtype=np.float64) for f in (f1, f2))
+    x1, x2 = x1.reshape(x1.shape[0], -1), x2.reshape(x2.shape[0], -1)
+    if x1.shape[1] != x2.shape[1] or x1.shape[0] < 1 or x2.shape[0] < 1:
+        raise ValueError(f"frechet_distance: feature sets {x1.shape} and {x2.shape} do not match")
+    m1, m2 = x1.mean(axis=0), x2.mean(axis=0)
+    mean = float(((m1 - m2) ** 2).sum())
+    if x1.shape[0] == 1:
+        return mean
+    if x2.shape[0] == 1:
+        raise ValueError("frechet_distance: the second set has one sample and the first several: no covariance to compare")
+    c1, c2 = ((x - m).T @ (x - m) / (x.shape[0] - 1) for x, m in ((x1, m1), (x2, m2)))
+    r1 = _sym_sqrt(c1)
+    return float(np.trace(c1 + c2) - 2.0 * np.trace(_sym_sqrt(r1 @ (c2 @ r1))) + mean)
+
+
+def fvd_caption(clips: int, synthetic: bool = False) -> str:
+    """what stands beside every printed and written FVD value: the variant, the clip count (below 400 clips the covariances are
+    singular), under stand-in weights the warning"""
+    return (f"{FVD_LABEL}, {clips} clips{' < 400: singular covariances' if clips < I3D_CLASSES else ''}; {FVD_NOTE}"
+            f"{'; SYNTHETIC I3D weights: not comparable with published FVD' if synthetic else ''}")
+
+
+def fvd_line(value: float, clips: int, synthetic: bool = False) -> str:
+    """the value of a result file's `FVD:` line"""
+    return f"{value} [{fvd_caption(clips, synthetic)}]"
+
+
+def add_fvd_arguments(parser):
+    """--fvd-i3d PATH | --fvd-synthetic"""
+    parser.add_argument("--fvd-i3d", type=str, default=None, help=f"score {FVD_LABEL} too: the I3D state dict i3d_pretrained_400.pt "
+                        f"(.pt / .pth / .safetensors; weights are not shipped); {FVD_NOTE}")
+    parser.add_argument("--fvd-synthetic", action="store_true", help="FVD under deterministic synthetic I3D weights: exercises the kernels; "
+                        "the value is NOT comparable with published FVD")
+
+
+def fvd_from_args(args, parser=None, score=True):
+    """the I3D the flags of add_fvd_arguments ask for, or None; `score`: whether the driver's --score (where it has one) is set"""
+    def fail(msg):
+        if parser is not None:
+            parser.error(msg)
+        raise ValueError(msg)
+    path, synthetic = getattr(args, "fvd_i3d", None), bool(getattr(args, "fvd_synthetic", False))
+    if (path or synthetic) and not score:
+        fail("--fvd-* flags are only valid with --score")
+    if path and synthetic:
+        fail("--fvd-synthetic and --fvd-i3d exclude each other")
+    if synthetic:
+        print(f"FVD: synthetic I3D weights - the {FVD_LABEL} value is not comparable with published FVD")
+        return I3D.synthetic(0)
+    if path:
+        return I3D.from_file(path)
+    return None
+
+
 # ---- temporal spectra (csrc/hv_spectrum.hip) --------------------------------------------------------------------------------------------
 # The fork's theory_analysis.ipynb, cells 2, 4 and 5: `np.abs(np.fft.fft(signal, axis=0)).mean(axis=1)` over every pixel time series of
 # the 8-bit gray frames of a clip (cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY)), and the same over every (channel, h, w) series of
@@ -549,9 +889,11 @@ class MetricsAccumulator:
     """Per-frame scores of many videos; the experiment's number is the mean over all FRAMES (compute_metrics.py:150-154), so a long
     video weighs more than a short one.  `lpips` (an LpipsAlex): add_video scores LPIPS too (compute_metrics.py:142-146,153-154)."""
 
-    def __init__(self, lpips: "LpipsAlex" = None):
+    def __init__(self, lpips: "LpipsAlex" = None, fvd: "I3D" = None):
         self.psnr, self.ssim, self.lpips = [], [], []
         self.lpips_model = lpips
+        self.fvd_model = fvd
+        self.fvd_ref, self.fvd_rec = [], []        # one I3D logits vector [400] per input clip and per reconstruction
 
     def add(self, psnr, ssim, lpips=None):
         """per-frame arrays of one video (or a [B,T] batch), e.g. video_metrics(...)["psnr"], ["ssim"] (and ["lpips"])"""
@@ -566,25 +908,62 @@ class MetricsAccumulator:
         self.psnr.extend(psnr.tolist())
         self.ssim.extend(ssim.tolist())
 
-    def add_video(self, ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True) -> dict:
+    def add_video(self, ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True, ref_logits=None) -> dict:
+        """`ref_logits` (with fvd=): the I3D logits of `ref` from an earlier call (m["fvd_ref_logits"]), which do not depend on how
+        `rec` was made; they are computed here otherwise.  With fvd= a pair with fewer than 10 common frames is a ValueError, raised
+        before anything of the pair is scored (the reference asserts the same): it is not skipped."""
+        if self.fvd_model is not None and min(ref.shape[-3], rec.shape[-3]) < I3D_MIN_FRAMES:
+            raise ValueError(f"fvd: a clip needs at least {I3D_MIN_FRAMES} frames, got {min(ref.shape[-3], rec.shape[-3])} common frames")
         m = video_metrics(ref, rec, rescale, lpips=self.lpips_model)
         self.add(m["psnr"], m["ssim"], m.get("lpips"))
+        if self.fvd_model is not None:
+            T = min(ref.shape[-3], rec.shape[-3])               # the frames the other scores saw
+            lr = fvd_logits(ref[..., :T, :, :], self.fvd_model, rescale) if ref_logits is None else ref_logits
+            m["fvd_ref_logits"] = lr
+            m["fvd_rec_logits"] = fvd_logits(rec[..., :T, :, :], self.fvd_model, rescale)
+            self.add_logits(lr, m["fvd_rec_logits"])
         return m
+
+    def add_logits(self, ref_logits, rec_logits):
+        """I3D logits [400] or [B,400] of input clips and of their reconstructions"""
+        for dst, v in ((self.fvd_ref, ref_logits), (self.fvd_rec, rec_logits)):
+            v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+            dst.extend(np.asarray(v, dtype=np.float32).reshape(-1, I3D_CLASSES))
+
+    @property
+    def clips(self) -> int:
+        return len(self.fvd_rec)
 
     @property
     def frames(self) -> int:
         return len(self.psnr)
 
     def result(self) -> dict:
-        """{"PSNR": ..., "SSIM": ...} and, only if LPIPS values were added, "LPIPS"; empty when nothing was added (the reference
-        writes no key then)."""
+        """{"PSNR": ..., "SSIM": ...}, only if LPIPS values were added "LPIPS", and only if the logits of at least two clip pairs were
+        added "FVD" (FVD_LABEL: the Frechet distance between the inputs' and the reconstructions' I3D logits); empty when nothing was
+        added (the reference writes no key then)."""
         out = {}
         if self.psnr:
             out["PSNR"] = sum(self.psnr) / len(self.psnr)
             out["SSIM"] = sum(self.ssim) / len(self.ssim)
         if self.lpips:
             out["LPIPS"] = sum(self.lpips) / len(self.lpips)
+        if len(self.fvd_ref) >= 2 and len(self.fvd_ref) == len(self.fvd_rec):
+            out["FVD"] = frechet_distance(np.stack(self.fvd_ref), np.stack(self.fvd_rec))
         return out
 
+    def fvd_note(self) -> str:
+        """what a driver prints after result() when it holds "FVD" (fvd_caption in brackets); the empty string otherwise"""
+        if not (len(self.fvd_ref) >= 2 and len(self.fvd_ref) == len(self.fvd_rec)):
+            return ""
+        return f" (FVD: {fvd_caption(self.clips, self._fvd_synthetic())})"
+
+    def _fvd_synthetic(self) -> bool:
+        return self.fvd_model is not None and self.fvd_model.label == "synthetic"
+
     def save(self, results_dir: str, root1: str, root2: str, timestamp: str = None) -> str:
-        return save_results(self.result(), root1, root2, results_dir, timestamp)
+        """the `FVD:` line, present only when result() has the key, carries the variant and the clip count beside the value"""
+        res = self.result()
+        if "FVD" in res:
+            res["FVD"] = fvd_line(res["FVD"], self.clips, self._fvd_synthetic())
+        return save_results(res, root1, root2, results_dir, timestamp)

@@ -32,9 +32,10 @@ typedef struct ihipStream_t* hipStream_t;
  *   7: fp8 row scales floored at 2^-126 (finite codes for rows with 0 < amax < 448 * 2^-126), hv_vae_postprocess_f16_f32 keeps a NaN
  *   8: + hv_lpips_conv1_f32, hv_lpips_conv2d_f32, hv_lpips_maxpool_f32, hv_lpips_distance_f32, hv_lpips_distance_workspace_bytes
  *   9: + hv_temporal_spectrum, hv_temporal_spectrum_workspace_bytes
+ *  10: + hv_i3d_preprocess, hv_i3d_conv3d_f32, hv_i3d_maxpool3d_f32, hv_i3d_head_f32
  * The integer `#define HV_*` constants of this header are what a caller shares with the kernels (sizes, limits, table layouts);
  * the Python side reads them from here (hunyuanvideo_efficiency_amd/_abi.py). */
-#define HV_ABI_VERSION 9
+#define HV_ABI_VERSION 10
 int hv_abi_version(void);       /* HV_ABI_VERSION of the header the library was compiled from */
 
 /* K1: nn.LayerNorm(elementwise_affine=False, eps) followed by modulate()
@@ -390,6 +391,50 @@ int hv_temporal_spectrum(const void* x, int64_t sc, int64_t st, int64_t sh, int 
                          int rescale, int wr, int wg, int wb, int round, int shift, const float* twiddle, int64_t twiddle_floats,
                          double* mag_sum, double* pow_sum, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 int64_t hv_temporal_spectrum_workspace_bytes(int mode, int C, int T, int H, int W);
+
+/* Frechet Video Distance, I3D logits (the fork's rebuttal/common_metrics_on_video_quality/calculate_fvd.py:28-48 with method='videogpt':
+ * fvd/videogpt/fvd.py:21-65 preprocessing, fvd/videogpt/pytorch_i3d.py the Inception-I3D network), one entry point per kernel, every step
+ * fp32 as in the reference.  Features are channels-last fp32 [voxel = (t * H + h) * W + w][C] with a row pitch (ldx, ldy, in elements): the
+ * pointer may address a column slice of a wider buffer, so the four branches of an Inception module (pytorch_i3d.py:127-132) write straight
+ * into their slice of the module's output and the torch.cat of :132 never happens.  Element offsets are 64-bit.
+ *
+ * Preprocessing (fvd.py:21-60 preprocess / preprocess_single): x [3,T,H,W] read as hv_video_metrics reads a video (dtype 0 = fp16, 1 =
+ * fp32, element strides, W contiguous, `rescale`, the same 8-bit quantiser: the reference's (videos * 255).astype(uint8) on [0, 1] frames
+ * is that truncation), then b / 255 in fp32, bilinear resize to RH x RW (F.interpolate(mode='bilinear', align_corners=False): source
+ * coordinate max(0, fmaf((float)in / (float)out, dst + 0.5, -0.5)), written as one fma), centre crop of 224 x 224 at ((RH - 224) / 2,
+ * (RW - 224) / 2), (v - 0.5) * 2.  y: [T][224][224][4] fp32, channel 3 = 0 (the first conv reads 4-channel voxels), 16-byte aligned.  RH, RW
+ * come from the caller (fvd.py:32-36: the shorter side 224, the other ceil(side * (224 / min(H, W))) in the host's double arithmetic);
+ * HV_ERR_ARG unless the shorter side's is 224 and the other's >= 224 (H == W: either side, since that double arithmetic gives 225 x 224 for
+ * some sizes, e.g. 200 x 200).  The 8-bit frames never reach memory. */
+int hv_i3d_preprocess(const void* x, int64_t x_sc, int64_t x_st, int64_t x_sh, int dtype, int T, int H, int W, int RH, int RW, int rescale,
+                      float* y, hipStream_t stream);
+
+/* Unit3D (pytorch_i3d.py:78-103: F.pad with zeros, Conv3d, eval-mode BatchNorm3d or bias, ReLU or none) as an implicit GEMM on the
+ * fp32-input MFMA (each output element one k-ordered fmaf chain):  y[o][n] = act(sc[n] * sum_k x[window of o][k] w[k][n] + sh[n]),
+ * act = ReLU if relu else identity; sc, sh: the BatchNorm folded by the caller (sc = gamma / sqrt(var + eps), sh = beta - mean * sc), or
+ * sc = 1, sh = bias for the logits layer.  x: [T*H*W][ldx >= Cin]; y: [OT*OH*OW][ldy >= Cout], O = ceil(extent / stride) per axis (the
+ * "same" rule of :81-83).  Kernel extents 1 | 3 | 7 and strides 1 | 2 per axis; pad_*: cells of zero padding in FRONT of each axis (< the
+ * kernel extent; the caller applies compute_pad :71-75 and :88-93), cells behind the input read as zero too.  w: k-major [Kpad][Cout],
+ * k = ((dt * kh + dh) * kw + dw) * Cin + ci, Kpad = K rounded up to 32 with zero rows, 16-byte aligned.  Cin % 4 == 0 and Cout % 4 == 0,
+ * both in [4, 4096] (the first layer reads the 4-channel output of hv_i3d_preprocess); ldx % 4 == 0, x 16-byte aligned. */
+int hv_i3d_conv3d_f32(const float* x, int64_t ldx, const float* w, const float* sc, const float* sh, float* y, int64_t ldy, int T, int H,
+                      int W, int Cin, int Cout, int kt, int kh, int kw, int stride_t, int stride_h, int stride_w, int pad_t, int pad_h,
+                      int pad_w, int relu, hipStream_t stream);
+
+/* MaxPool3dSamePadding (pytorch_i3d.py:7-34: F.pad with zeros, then MaxPool3d): kernel extents 1..3, strides 1 | 2 per axis, pad_* cells in
+ * front (< the kernel extent), output extents ceil(extent / stride).  A window cell outside the input holds 0 AND TAKES PART in the
+ * maximum: a border window over all-negative inputs gives 0.  A NaN cell makes its windows NaN, as
+ * torch's max_pool3d does.  C % 4 == 0; ldx, ldy % 4 == 0; x, y 16-byte aligned. */
+int hv_i3d_maxpool3d_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int T, int H, int W, int C, int kt, int kh, int kw,
+                         int stride_t, int stride_h, int stride_w, int pad_t, int pad_h, int pad_w, hipStream_t stream);
+
+/* The tail of InceptionI3d.forward (pytorch_i3d.py:276-285,310-315): AvgPool3d([2,7,7], stride 1) on x [T][7][7][1024] (row pitch ldx),
+ * the 1024 -> 400 logits layer with bias (w k-major [1024][400]), the mean over the T - 1 time positions: out [400].  fp32 in a fixed
+ * order: a pooled value is the sum of its 98 cells in memory order / 98, a logit one k-ordered fmaf chain, the mean summed in time order.
+ * workspace: >= (T - 1) * 1024 floats, 16-byte aligned.  HV_ERR_ARG unless H == W == 7, C == 1024 and 2 <= T <= HV_I3D_HEAD_MAX_T. */
+#define HV_I3D_HEAD_MAX_T 4096
+int hv_i3d_head_f32(const float* x, int64_t ldx, const float* w, const float* bias, float* out, int T, int H, int W, int C,
+                    float* workspace, int64_t workspace_floats, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -30,7 +30,8 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
     """Reconstructs the first `max_files` tensors, `batch_size` at a time (tensors of one batch must have equal shapes, as a
     DataLoader's default collate requires); every input still gets its own <name>.pt of shape [1, C, T, H, W].
     `scorer` (a metrics.MetricsAccumulator): each reconstruction is scored against its input while both are on the device
-    (PSNR / SSIM, and LPIPS if the accumulator holds LPIPS weights, per frame of the common frames).  save=False skips the copy to the host and the .pt files.
+    (PSNR / SSIM, and LPIPS if the accumulator holds LPIPS weights, per frame of the common frames; with I3D weights the accumulator also
+    keeps both clips' logits for the FVD of the whole run).  save=False skips the copy to the host and the .pt files.
     `spectrum_dir`: also write <name>_spectrum.json there per input - the temporal spectra (metrics.spectrum_report; the fork's
     theory_analysis.ipynb) of the input, of the posterior mean the forward already returns and of the reconstruction, with `freq` axes
     when `fps` is given."""
@@ -99,6 +100,8 @@ def parse_args(argv=None):
     p.add_argument("--lpips-linear", type=str, default=None, help="with --lpips-alexnet: the LPIPS linear layers (lin{0..4}.model.1.weight)")
     p.add_argument("--lpips-synthetic", action="store_true", help="with --score: LPIPS under deterministic synthetic weights (exercises the "
                                                                   "kernels; NOT comparable with published LPIPS)")
+    from hunyuanvideo_efficiency_amd.metrics import add_fvd_arguments
+    add_fvd_arguments(p)                 # --fvd-i3d PATH | --fvd-synthetic, with --score
     p.add_argument("--spectrum", action="store_true", help="with --score: write <name>_spectrum.json per clip into the results directory - "
                                                           "temporal spectra of input, latent and reconstruction and their high-band shares")
     p.add_argument("--fps", type=float, default=None, help="with --spectrum: frame rate of the clips, adds the frequency axes")
@@ -115,6 +118,10 @@ def parse_args(argv=None):
         p.error("--lpips-linear needs --lpips-alexnet")
     if a.lpips_synthetic and a.lpips_alexnet:
         p.error("--lpips-synthetic and --lpips-alexnet exclude each other")
+    if (a.fvd_i3d or a.fvd_synthetic) and not a.score:
+        p.error("--fvd-* flags are only valid with --score")
+    if a.fvd_i3d and a.fvd_synthetic:
+        p.error("--fvd-synthetic and --fvd-i3d exclude each other")
     if a.no_save and not a.score:
         p.error("--no-save is only valid with --score (nothing would be produced)")
     if a.results_dir and not a.score:
@@ -139,13 +146,13 @@ def main(argv=None):
             _apply_t_ops_config_to_vae(vae, load_t_ops_config(a.config_json))
     if not a.score:
         return infer_vae(vae, VideoTensorDataset(a.tensor_dir), device, a.output_dir, a.max_files, a.batch_size)
-    from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator, lpips_from_args
-    scorer = MetricsAccumulator(lpips=lpips_from_args(a))
+    from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator, fvd_from_args, lpips_from_args
+    scorer = MetricsAccumulator(lpips=lpips_from_args(a), fvd=fvd_from_args(a, score=a.score))
     done = infer_vae(vae, VideoTensorDataset(a.tensor_dir), device, a.output_dir, a.max_files, a.batch_size, scorer, not a.no_save,
                      (a.results_dir or a.output_dir) if a.spectrum else None, a.fps)
     results = scorer.result()
     print(f"Results over {scorer.frames} frames: {results}" + (" (LPIPS under synthetic weights: not comparable with published LPIPS)"
-                                                               if a.lpips_synthetic else ""))
+                                                               if a.lpips_synthetic else "") + scorer.fvd_note())
     path = scorer.save(a.results_dir or a.output_dir, a.tensor_dir, a.output_dir)
     print(f"Saved metrics to {path}")
     return done
