@@ -31,25 +31,36 @@ def psnr(img1, img2):
     return 100.0 if mse < 1.0e-10 else 20.0 * math.log10(1.0 / math.sqrt(mse))
 
 
-def ssim_map_sums(img1, img2):
-    """per channel: sum of the SSIM map over the (H-6) x (W-6) window positions, float64 [C]; data range of img1's frame"""
+def box_moments(x, y):
+    """uint8 [H, W] planes -> the exact int64 7x7 box sums (sx, sy, sxx, syy, sxy), each [H-6, W-6]"""
+    x, y = x.astype(np.int64), y.astype(np.int64)
+    return _box(x), _box(y), _box(x * x), _box(y * y), _box(x * y)
+
+
+def ssim_maps(img1, img2, R=None):
+    """uint8 [H, W, C] frames -> the float64 SSIM map of every channel, [C, H-6, W-6]; data range R of img1's frame (all channels)
+    unless given"""
     if img1.shape[0] < WIN or img1.shape[1] < WIN:
         raise ValueError("win_size exceeds image extent")
-    R = float(int(img1.max()) - int(img1.min()))
+    R = float(int(img1.max()) - int(img1.min())) if R is None else float(R)
     C1, C2 = (0.01 * R) ** 2, (0.03 * R) ** 2
     n = WIN * WIN
-    out = np.zeros(img1.shape[2], dtype=np.float64)
+    out = np.zeros((img1.shape[2], img1.shape[0] - WIN + 1, img1.shape[1] - WIN + 1), dtype=np.float64)
     for c in range(img1.shape[2]):
-        x, y = img1[..., c].astype(np.int64), img2[..., c].astype(np.int64)
-        sx, sy, sxx, syy, sxy = _box(x), _box(y), _box(x * x), _box(y * y), _box(x * y)
+        sx, sy, sxx, syy, sxy = box_moments(img1[..., c], img2[..., c])
         vx, vy, vxy = n * sxx - sx * sx, n * syy - sy * sy, n * sxy - sx * sy            # exact: the cancellation is in integers
         cov = float(n * (n - 1))
         a1 = 2.0 * (sx * sy) / float(n * n) + C1
         b1 = (sx * sx + sy * sy) / float(n * n) + C1
         a2 = 2.0 * vxy / cov + C2
         b2 = (vx + vy) / cov + C2
-        out[c] = ((a1 * a2) / (b1 * b2)).sum()
+        out[c] = (a1 * a2) / (b1 * b2)
     return out
+
+
+def ssim_map_sums(img1, img2, R=None):
+    """per channel: sum of the SSIM map over the (H-6) x (W-6) window positions, float64 [C]; data range of img1's frame"""
+    return np.array([m.sum() for m in ssim_maps(img1, img2, R)], dtype=np.float64)
 
 
 def ssim(img1, img2):
