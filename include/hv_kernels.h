@@ -33,9 +33,10 @@ typedef struct ihipStream_t* hipStream_t;
  *   8: + hv_lpips_conv1_f32, hv_lpips_conv2d_f32, hv_lpips_maxpool_f32, hv_lpips_distance_f32, hv_lpips_distance_workspace_bytes
  *   9: + hv_temporal_spectrum, hv_temporal_spectrum_workspace_bytes
  *  10: + hv_i3d_preprocess, hv_i3d_conv3d_f32, hv_i3d_maxpool3d_f32, hv_i3d_head_f32
+ *  11: + hv_yuv420_to_clip
  * The integer `#define HV_*` constants of this header are what a caller shares with the kernels (sizes, limits, table layouts);
  * the Python side reads them from here (hunyuanvideo_efficiency_amd/_abi.py). */
-#define HV_ABI_VERSION 10
+#define HV_ABI_VERSION 11
 int hv_abi_version(void);       /* HV_ABI_VERSION of the header the library was compiled from */
 
 /* K1: nn.LayerNorm(elementwise_affine=False, eps) followed by modulate()
@@ -435,6 +436,34 @@ int hv_i3d_maxpool3d_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int
 #define HV_I3D_HEAD_MAX_T 4096
 int hv_i3d_head_f32(const float* x, int64_t ldx, const float* w, const float* bias, float* out, int T, int H, int W, int C,
                     float* workspace, int64_t workspace_floats, hipStream_t stream);
+
+/* Raw planar YUV 4:2:0 frames -> clip tensor (the fork's dataset_processor/yuv_tensor.py: the frame loop :108-140 with
+ * cv2.cvtColor(COLOR_YUV2BGR_I420 / _YV12 / _NV12) :128-133, the target size :207-212 and cv2.resize :167, COLOR_BGR2RGB :237, ToTensor
+ * :238, the [3,T,H,W] stack :249 and 2x - 1 :250) in one pass; the 8-bit RGB frames never reach memory.  Integer arithmetic and table lookups
+ * only.  UNPINNED RESTATEMENT: cv2 is not part of this environment, so the bytes below are OpenCV's rule as far as it can be
+ * established without executing it (tests/test_yuv_cpu.py anchors them independently).
+ * raw: device bytes of the first frame; T frames at a pitch of W * H * 3 / 2 bytes: the Y plane [H][W], then by `layout`
+ *   HV_YUV_I420: U [H/2][W/2], V [H/2][W/2];   HV_YUV_YV12: V, U;   HV_YUV_NV12: [H/2][W/2] interleaved (U, V) pairs.
+ * Pixel (y, x) takes the chroma sample (y >> 1, x >> 1), no chroma interpolation.  Colour, BT.601 limited range, int32, `>>` arithmetic:
+ *   yy = max(0, Y - 16) * 1220542;   R = clamp((yy + 1673527 (V - 128) + 2^19) >> 20, 0, 255);
+ *   G = clamp((yy - 852492 (V - 128) - 409993 (U - 128) + 2^19) >> 20, 0, 255);   B = clamp((yy + 2116026 (U - 128) + 2^19) >> 20, 0, 255).
+ * OH == H and OW == W: no resize (ytab, xtab unused, may be NULL).  Otherwise a 2-tap bilinear filter per axis on the 8-bit R, G, B - this
+ * project's own rule, modelled on cv2.resize(INTER_LINEAR) but not claimed equal to its bytes - from the caller's tables: ytab int32
+ * [OH][2], xtab int32 [OW][2], entry d = (first source index s, weight c1 of the second index min(s + 1, extent - 1)), c1 in
+ * [0, 2^HV_YUV_COEF_BITS], c0 = 2^HV_YUV_COEF_BITS - c1 (dataset.resize_tables builds them; the kernel clamps an entry into range):
+ *   h_r = c0x P[y_r][x0] + c1x P[y_r][x1] for the two source rows,   q = (c0y h_0 + c1y h_1 + 2^21) >> 22.
+ * out: element (c, t, y, x) of channel order R, G, B at out[c * sc + t * st + y * sh + x] (element strides, W contiguous, as
+ * hv_video_metrics reads a video), dtype 0 = fp16, 1 = fp32, holding vtab[q]: the caller's 256 entries in the output dtype
+ * (dataset.yuv_value_table: the bits of (float(q) / 255) * 2 - 1, for fp16 rounded once more).  All frame and output offsets are 64-bit.
+ * HV_ERR_ARG, nothing launched: odd or non-positive W or H, a side above HV_YUV_MAX_SIDE, T < 1, OH or OW < 1, differing sizes without
+ * both tables, an unknown layout or dtype, negative strides or strides under which two cells of the output share an address. */
+#define HV_YUV_I420 0
+#define HV_YUV_YV12 1
+#define HV_YUV_NV12 2
+#define HV_YUV_COEF_BITS 11
+#define HV_YUV_MAX_SIDE 16384
+int hv_yuv420_to_clip(const void* raw, int T, int layout, int W, int H, void* out, int dtype, int64_t sc, int64_t st, int64_t sh,
+                      int OH, int OW, const int* ytab, const int* xtab, const void* vtab, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -2,8 +2,11 @@
 """VAE reconstruction driver of the fork (infer.py:1-127) on the MI355X kernels: for every `<name>.pt` video tensor [C,T,H,W] in
 --tensor-dir, run AutoencoderKLCausal3D.forward (encode -> posterior.mode() -> decode) under the temporal-op configuration of
 --config-json (t_ops_config.json) and write the reconstruction to --output-dir/<name>.pt.  Same flags as the reference; input
-tensors and checkpoints are read with torch.load(weights_only=True) only.  Without --vae-path the VAE gets deterministic
-synthetic weights (there are no checkpoints in this environment): the plumbing and the kernels are what is exercised."""
+tensors and checkpoints are read with torch.load(weights_only=True) only.  With --yuv-format {I420,NV12,YV12} --tensor-dir is a folder
+of raw planar YUV 4:2:0 files instead, converted to clips on the GPU (hunyuanvideo_efficiency_amd/dataset.py; --target-height,
+--start-frame, --end-frame as dataset_processor/yuv_tensor.py takes them); outputs keep the input file's stem.  Without --vae-path
+the VAE gets deterministic synthetic weights (there are no checkpoints in this environment): the plumbing and the kernels are what is
+exercised."""
 import argparse
 import json
 import os
@@ -38,9 +41,11 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
     if batch_size < 1:
         raise ValueError(f"--batch-size must be >= 1, got {batch_size}")
     os.makedirs(output_dir, exist_ok=True)
+    from hunyuanvideo_efficiency_amd.dataset import clip_stem
     if spectrum_dir is not None:
         from hunyuanvideo_efficiency_amd.metrics import spectrum_json, spectrum_report
         os.makedirs(spectrum_dir, exist_ok=True)
+    file_fps = getattr(dataset, "fps", {})       # a YuvClipDataset knows each file's frame rate from its name
     n = len(dataset) if max_files is None else min(len(dataset), max_files)
     done = []
     for start in range(0, n, batch_size):
@@ -48,7 +53,7 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
         shapes = {tuple(v.shape) for v, _ in items}
         if len(shapes) != 1:
             raise ValueError(f"a batch needs tensors of one shape, got {sorted(shapes)} for {[f for _, f in items]}")
-        names = [f.replace(".pt", "") for _, f in items]
+        names = [clip_stem(f) for _, f in items]
         video = torch.stack([v for v, _ in items]).to(device, dtype=torch.float16)      # the DataLoader's batch dimension
         print(f"Processing {', '.join(names)}, video shape: {tuple(video.shape)}")
         with torch.no_grad():
@@ -57,7 +62,7 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
         if spectrum_dir is not None:
             posterior = fwd[1]
             for b, name in enumerate(names):
-                rep = spectrum_report(video[b], posterior.mean[b], recon[b], fps=fps)
+                rep = spectrum_report(video[b], posterior.mean[b], recon[b], fps=fps if fps is not None else file_fps.get(items[b][1]))
                 with open(os.path.join(spectrum_dir, f"{name}_spectrum.json"), "w") as f:
                     json.dump(spectrum_json(rep), f)
                 print(f"Spectrum {name}: high-band share input {rep['input']['high_band_share']:.4f} latent "
@@ -104,8 +109,12 @@ def parse_args(argv=None):
     add_fvd_arguments(p)                 # --fvd-i3d PATH | --fvd-synthetic, with --score
     p.add_argument("--spectrum", action="store_true", help="with --score: write <name>_spectrum.json per clip into the results directory - "
                                                           "temporal spectra of input, latent and reconstruction and their high-band shares")
-    p.add_argument("--fps", type=float, default=None, help="with --spectrum: frame rate of the clips, adds the frequency axes")
+    p.add_argument("--fps", type=float, default=None, help="with --spectrum: frame rate of the clips, adds the frequency axes "
+                                                           "(default with --yuv-format: the rate in each file's name)")
+    from hunyuanvideo_efficiency_amd.dataset import add_yuv_arguments, check_yuv_arguments
+    add_yuv_arguments(p)                 # --yuv-format {I420,NV12,YV12} [--target-height N] [--start-frame A] [--end-frame B]
     a = p.parse_args(argv)
+    check_yuv_arguments(a, p)
     if a.spectrum and not a.score:
         p.error("--spectrum is only valid with --score")
     if a.fps is not None and not a.spectrum:
@@ -144,11 +153,16 @@ def main(argv=None):
         if a.config_json:
             from hunyuanvideo_efficiency_amd.vae import _apply_t_ops_config_to_vae, load_t_ops_config
             _apply_t_ops_config_to_vae(vae, load_t_ops_config(a.config_json))
+    if a.yuv_format:
+        from hunyuanvideo_efficiency_amd.dataset import dataset_from_args
+        dataset = dataset_from_args(a, device)
+    else:
+        dataset = VideoTensorDataset(a.tensor_dir)
     if not a.score:
-        return infer_vae(vae, VideoTensorDataset(a.tensor_dir), device, a.output_dir, a.max_files, a.batch_size)
+        return infer_vae(vae, dataset, device, a.output_dir, a.max_files, a.batch_size)
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator, fvd_from_args, lpips_from_args
     scorer = MetricsAccumulator(lpips=lpips_from_args(a), fvd=fvd_from_args(a, score=a.score))
-    done = infer_vae(vae, VideoTensorDataset(a.tensor_dir), device, a.output_dir, a.max_files, a.batch_size, scorer, not a.no_save,
+    done = infer_vae(vae, dataset, device, a.output_dir, a.max_files, a.batch_size, scorer, not a.no_save,
                      (a.results_dir or a.output_dir) if a.spectrum else None, a.fps)
     results = scorer.result()
     print(f"Results over {scorer.frames} frames: {results}" + (" (LPIPS under synthetic weights: not comparable with published LPIPS)"

@@ -13,7 +13,10 @@ fork's shell drivers' background batches over several cards are not reproduced.
                                                                  record then carries "lpips_weights": "synthetic")
   ... --fvd-i3d i3d_pretrained_400.pt   (user-supplied; --fvd-synthetic: stand-in weights) adds "fvd", "fvd_clips", "fvd_variant": FVD
                                         (videogpt I3D logits) of the inputs against each configuration's reconstructions - not the
-                                        styleganv variant; the inputs' logits are computed once for all configurations"""
+                                        styleganv variant; the inputs' logits are computed once for all configurations
+  ... --yuv-format I420 [--target-height 240] [--start-frame A] [--end-frame B]   --tensor-dir is a folder of raw planar YUV 4:2:0 files
+                                        (<name>_<n>fps_<w>x<h>.yuv), converted on the GPU once for all configurations and kept on the
+                                        device; with --spectrum and no --fps each file name's frame rate gives the frequency axes"""
 import argparse
 import json
 import os
@@ -56,8 +59,9 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
         reports = []
         n = len(dataset) if max_files is None else min(len(dataset), max_files)
         for idx in range(n):
-            video, _ = dataset[idx]
+            video, file_name = dataset[idx]
             video = video[None].to(device, dtype=torch.float16)
+            clip_fps = fps if fps is not None else getattr(dataset, "fps", {}).get(file_name)   # raw YUV files carry their rate
             with torch.no_grad():
                 z = vae.encode(video).latent_dist.mode()
                 recon = vae.decode(z).sample
@@ -66,7 +70,7 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
                 input_logits[(idx, min(video.shape[2], recon.shape[2]))] = m["fvd_ref_logits"]
             if spectra is not None:
                 from hunyuanvideo_efficiency_amd.metrics import spectrum_report
-                reports.append(spectrum_report(video[0], z[0], recon[0], fps=fps))
+                reports.append(spectrum_report(video[0], z[0], recon[0], fps=clip_fps))
             t_in += video.shape[2]
             t_lat += z.shape[2]
         res = acc.result()
@@ -109,6 +113,22 @@ def mean_spectra(reports):
     return out
 
 
+class ConvertedOnce:
+    """A YuvClipDataset whose clips are converted on first use and then kept on the device (fp16 [3,T,H,W] each): every configuration
+    of the study reads the same inputs, so a file is read, uploaded and converted once, not once per configuration."""
+
+    def __init__(self, dataset):
+        self.dataset, self.fps, self._items = dataset, dataset.fps, {}
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getitem__(self, idx):
+        if idx not in self._items:
+            self._items[idx] = self.dataset[idx]
+        return self._items[idx]
+
+
 def _exp_order(name):
     m = re.search(r"(\d+)", name)
     return (int(m.group(1)) if m else 0, name)
@@ -131,7 +151,10 @@ def parse_args(argv=None):
     from hunyuanvideo_efficiency_amd.metrics import add_fvd_arguments, add_lpips_arguments
     add_lpips_arguments(p, synthetic=True)
     add_fvd_arguments(p)
+    from hunyuanvideo_efficiency_amd.dataset import add_yuv_arguments, check_yuv_arguments
+    add_yuv_arguments(p)
     a = p.parse_args(argv)
+    check_yuv_arguments(a, p)
     if a.fps is not None and not (a.spectrum and a.fps > 0):
         p.error("--fps needs --spectrum and a positive rate")
     if (a.base_config is None) == (a.config_dir is None):
@@ -159,8 +182,12 @@ def main(argv=None):
     else:
         configs = [os.path.join(a.config_dir, f) for f in sorted((f for f in os.listdir(a.config_dir) if f.endswith(".json")), key=_exp_order)]
         configs = configs[:a.limit] if a.limit is not None else configs
-    dataset = VideoTensorDataset(a.tensor_dir)
-    out = os.path.join(a.output_dir, "study.jsonl")
+    if a.yuv_format:
+        from hunyuanvideo_efficiency_amd.dataset import dataset_from_args
+        dataset = ConvertedOnce(dataset_from_args(a, "cuda"))
+    else:
+        dataset = VideoTensorDataset(a.tensor_dir)
+    out =os.path.join(a.output_dir, "study.jsonl")
     records = []
     for cfg in configs:
         spectra = {} if a.spectrum else None
