@@ -232,6 +232,11 @@ def euler_ref(s, v, dt: float):
 
 
 # ---------------------------------------------------------------------------------------------------- GroupNorm apply
+def silu_e32(t64, y64):
+    """the fp32 error of silu_f on an exact argument t (derived in gn_apply_ref): |y| ((|t| + 2) 2^-24 + 2^-22)"""
+    return y64.abs() * ((t64.abs() + 2.0) * EPS32 + 2.0 ** -22)
+
+
 def gn_apply_eval(x, affine, silu: bool):
     """(y64, e32): the fp64 value of gn_apply_ref and the error of its fp32 evaluation alone (the bound without the store's ulp)"""
     sc, sh = affine[:, 0].double()[None], affine[:, 1].double()[None]
@@ -241,7 +246,7 @@ def gn_apply_eval(x, affine, silu: bool):
     if not silu:
         return t, lin
     y = silu64(t)
-    return y, 1.1 * lin + y.abs() * ((t.abs() + 2.0) * EPS32 + 2.0 ** -22)
+    return y, 1.1 * lin + silu_e32(t, y)
 
 
 def gn_apply_ref(x, affine, silu: bool):

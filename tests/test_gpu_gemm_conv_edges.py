@@ -30,7 +30,8 @@ hv_conv3d_causal_f16.  Both sides of the packing guard (PACK_CASES, STRIDED_PACK
 4097 at unit stride; sT = 254 | 255 with stride_t 2 (cT mt = 254 | 256), source H and W = 4096 | 4097 with a stride of 2 (largest packed
 coordinate 4094); the sub-pixel form at sT = 254 (accepted) and 255 (refused as a bad argument, the output untouched).
 
-Checks per case: the plain output within the fp64 bound; GELU / SiLU within 1 ulp of the oracle's formula on the kernel's own y;
+Checks per case: the plain output within the fp64 bound; GELU / SiLU within 1 ulp of the oracle's formula on the kernel's own y (random
+y of size 0.5; the whole 16-bit domain, with the tail where that sentence does not hold, is tests/test_gpu_activation_domain.py);
 gate + residual (in place and not) and res bit-equal to the oracle's formula; column splits bit-equal to the unsplit launch;
 poison (NaN rows before / after the operand, columns in [K, ld)) never reaches an output; sentinel cells around every output
 keep their bits; a dense-operand launch and a repeated launch give the same bits.  The largest error-to-bound ratio of each
