@@ -139,6 +139,13 @@ __device__ __forceinline__ int acc_row(int r, int lk) { return (r & 3) + 8 * (r 
 
 static inline bool hv_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// The output-pitch rule of the C ABI (include/hv_kernels.h): rows stored next to each other must not share an address, so a pitch
+// below the width written per row is a bad argument once more than one row is written.  A single row has no neighbour and is exempt
+// (torch reports arbitrary strides for size-1 dimensions: a [1, N] view may carry stride(0) < N).
+static inline bool hv_pitch_ok(int64_t rows, int64_t pitch, int64_t width) { return rows <= 1 || pitch >= width; }
+// A block count that dim3 would truncate: grid.x holds at most 2^31 - 1 workgroups.
+static inline bool hv_grid_x_ok(int64_t blocks) { return blocks >= 0 && blocks <= 0x7fffffff; }
+
 // Raising a kernel's dynamic-LDS limit is a per-DEVICE attribute: one process may drive several GPUs, so the "already done"
 // flag is kept per device ordinal (hipGetDevice is a thread-local read, no driver call).
 struct HvPerDeviceOnce { bool done[64] = {}; };

@@ -294,9 +294,10 @@ __device__ __forceinline__ GemmArgs epilogue_handoff(const GemmArgs& g, const f3
 template <auto KERNEL, int LDS_BYTES, int BN>
 int launch_tiles(GemmArgs& g, hipStream_t stream) {
     static HvPerDeviceOnce once;
+    if (g.tiles_m == 0) g.tiles_m = (int)(((int64_t)g.M + BM - 1) / BM);
+    g.tiles_n = (int)(((int64_t)g.N + BN - 1) / BN);
+    if (!hv_grid_x_ok((int64_t)g.tiles_m * g.tiles_n)) return HV_ERR_ARG;      // one workgroup per tile, counted in int
     if (hv_set_max_lds(once, (const void*)KERNEL, LDS_BYTES) != HV_OK) return HV_ERR_LAUNCH;
-    if (g.tiles_m == 0) g.tiles_m = (g.M + BM - 1) / BM;
-    g.tiles_n = (g.N + BN - 1) / BN;
     KERNEL<<<dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(512), LDS_BYTES, stream>>>(g);
     return hv_check_launch();
 }
@@ -1280,6 +1281,8 @@ int fill_common(GemmArgs& g, const void* A, int64_t lda, const void* W, int64_t 
     if (n_split < N && (!out1 || (n_split & 7) || (ld1 & 7))) return HV_ERR_ARG;
     if ((gate && !res) || (res && (ld_res & 7))) return HV_ERR_ARG;
     if (act0 < 0 || act0 > 2 || act1 < 0 || act1 > 2) return HV_ERR_ARG;
+    // output pitch rule: the rows of out0 hold n_split columns, those of out1 the other N - n_split
+    if (!hv_pitch_ok(M, ld0, n_split) || (n_split < N && !hv_pitch_ok(M, ld1, N - n_split))) return HV_ERR_ARG;
     g = GemmArgs{};
     g.A = (const uint16_t*)A; g.lda = lda; g.W = (const uint16_t*)W; g.ldw = ldw; g.bias = (const uint16_t*)bias;
     g.M = M; g.N = N; g.K = K;
@@ -1335,6 +1338,7 @@ extern "C" int hv_gemm_f16(const void* A, int64_t lda, const void* W, int64_t ld
     GemmArgs g;
     int rc = fill_common(g, A, lda, W, ldw, bias, M, N, K, out, ldo, 0, 0, nullptr, 0, 0, nullptr, res, ld_res);
     if (rc != HV_OK) return rc;
+    if (out_is_f32 & ~1) return HV_ERR_ARG;
     if (out_is_f32) {
         if (res) return HV_ERR_ARG;
         g.out_f32 = (float*)out;
@@ -1362,9 +1366,12 @@ extern "C" int hv_conv3d_causal_f16(const void* x, int64_t ldx, const void* w_ta
     return launch<F16T, true>(g, stream);
 }
 
-extern "C" int64_t hv_gn_partial_rows(int64_t M) { return 4 * ((M + BM - 1) / BM); }
+extern "C" int64_t hv_gn_partial_rows(int64_t M) { return M > 0 && M <= 0x7fffffff ? 4 * ((M + BM - 1) / BM) : 0; }
 
 extern "C" int64_t hv_subpixel_gn_partial_rows(int sT, int sH, int sW, int up_t) {
+    // 0 for a grid hv_conv3d_upsampled_subpixel_f16 refuses: the packed-coordinate limits and the int row count of the output
+    if (sT <= 0 || sH <= 0 || sW <= 0 || (up_t & ~1) || sT >= PACK_T_LIMIT - 1 || sH > PACK_HW_LIMIT || sW > PACK_HW_LIMIT) return 0;
+    if ((int64_t)(up_t ? 2 * sT - 1 : sT) * sH * sW * 4 > 0x7fffffff) return 0;
     int64_t tiles = 0;
     for (int c = 0; c < (up_t ? 8 : 4); ++c) tiles += ((int64_t)((up_t && (c >> 2)) ? sT - 1 : sT) * sH * sW + BM - 1) / BM;
     return tiles * 4;
@@ -1382,9 +1389,10 @@ extern "C" int hv_conv3d_upsampled_subpixel_f16(const void* x, int64_t ldx, cons
     // sum is carried as an extra "lo" tap, is its choice - this kernel only needs offsets.
     if (!x || !w_sub || !tap_table || !out || sT <= 0 || sH <= 0 || sW <= 0 || ntap < 1 || ntap > 27 || (up_t & ~1)) return HV_ERR_ARG;
     // the pipelined conv tile's shapes; the packed frame coordinate goes up to sT (k = kt + 1 for odd output frames)
-    if (Cin < 256 || !conv_fits_packing(Cin, sT + 1, sH, sW) || Cout <= 128 || (Cout & 7)) return HV_ERR_ARG;
+    if (Cin < 256 || sT >= PACK_T_LIMIT - 1 || !conv_fits_packing(Cin, sT + 1, sH, sW) || Cout <= 128 || (Cout & 7)) return HV_ERR_ARG;
     const int T2 = up_t ? 2 * sT - 1 : sT, H2 = 2 * sH, W2 = 2 * sW, ncls = up_t ? 8 : 4;
     if ((int64_t)T2 * H2 * W2 > 0x7fffffff) return HV_ERR_ARG;
+    if (ldo < Cout) return HV_ERR_ARG;      // output pitch rule (the upsampled grid always has more than one row)
     GemmArgs g;
     int rc = fill_conv(g, x, ldx, w_sub, ntap, bias, out, ldo, nullptr, 0, sT * sH * sW, {T2, H2, W2}, {sT, sH, sW}, Cin, Cout, up_t, 1,
                        {1, 1, 1});

@@ -103,6 +103,7 @@ extern "C" int hv_ln_modulate_bf16(const void* x, const void* shift_or_bias, con
                                    int64_t M, int D, int64_t ldx, int64_t ldo, float eps, int mode, hipStream_t stream) {
     if (!x || !out || M < 0 || D <= 0 || (D & 7) || D > 4096 || (ldx & 7) || (ldo & 7) || (mode != 0 && mode != 1))
         return HV_ERR_ARG;
+    if (!hv_pitch_ok(M, ldo, D) || !hv_grid_x_ok((M + 3) / 4)) return HV_ERR_ARG;
     if (M == 0) return HV_OK;
     dim3 grid((unsigned)((M + 3) / 4)), block(256);
     const bf16_t *xp = (const bf16_t*)x, *ap = (const bf16_t*)shift_or_bias, *mp = (const bf16_t*)scale_or_weight;
@@ -192,6 +193,7 @@ __global__ __launch_bounds__(256) void ln_mod_fp8_kernel(const bf16_t* __restric
 extern "C" int hv_ln_modulate_fp8(const void* x, const void* shift, const void* scale, void* out_q, float* out_row_scale, int64_t M,
                                   int D, int64_t ldx, int64_t ldq, float eps, hipStream_t stream) {
     if (!x || !out_q || !out_row_scale || M < 0 || D <= 0 || (D & 7) || D > 4096 || (ldx & 7) || (ldq & 15)) return HV_ERR_ARG;
+    if (!hv_pitch_ok(M, ldq, D) || !hv_grid_x_ok((M + 3) / 4)) return HV_ERR_ARG;
     if (M == 0) return HV_OK;
     dim3 grid((unsigned)((M + 3) / 4)), block(256);
     const bf16_t *xp = (const bf16_t*)x, *ap = (const bf16_t*)shift, *mp = (const bf16_t*)scale;
@@ -231,6 +233,7 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
 extern "C" int hv_quant_rows_fp8(const void* x, int64_t ldx, void* out_q, int64_t ldq, float* out_row_scale, int64_t M, int K,
                                  hipStream_t stream) {
     if (!x || !out_q || !out_row_scale || M < 0 || K <= 0 || (K & 7) || (ldx & 7) || (ldq & 15)) return HV_ERR_ARG;
+    if (!hv_pitch_ok(M, ldq, K) || !hv_grid_x_ok((M + 3) / 4)) return HV_ERR_ARG;
     if (M == 0) return HV_OK;
     quant_rows_fp8_kernel<<<dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream>>>((const bf16_t*)x, ldx, (uint8_t*)out_q, ldq,
                                                                                   out_row_scale, M, K);
@@ -301,6 +304,10 @@ extern "C" int hv_qknorm_rope_bf16(void* qkv, const void* q_weight, const void* 
     if (!qkv || !q_weight || !k_weight || head_dim != 128 || n_heads <= 0 || n_rows < 0 || n_rope < 0 ||
         n_rope > n_rows || (ld & 7) || (k_offset & 7) || (n_rope > 0 && (!cos_tab || !sin_tab)))
         return HV_ERR_ARG;
+    // the row is rewritten in place: the q heads [0, n_heads * 128) and the k heads behind k_offset must be different columns, and
+    // both must end inside the row's pitch once a second row follows
+    const int64_t qk_cols = (int64_t)n_heads * 128;
+    if (k_offset < qk_cols || !hv_pitch_ok(n_rows, ld, k_offset + qk_cols) || !hv_grid_x_ok(n_rows)) return HV_ERR_ARG;
     if (n_rows == 0) return HV_OK;
     qknorm_rope_kernel<<<dim3((unsigned)n_rows), dim3(256), 0, stream>>>((bf16_t*)qkv, (const bf16_t*)q_weight,
                                                                           (const bf16_t*)k_weight, cos_tab, sin_tab, n_rows,
@@ -316,6 +323,8 @@ extern "C" int hv_qknorm_rope_scatter_bf16(const void* qkv, const void* q_weight
         (ld & 7) || (k_offset & 7) || (dst_ld & 7) || (dst_block_stride & 7) || heads_per_block <= 0 ||
         (n_rope > 0 && (!cos_tab || !sin_tab)))
         return HV_ERR_ARG;
+    // the source row is only read (k_offset and ld are free); a destination row holds the heads of one block
+    if (!hv_pitch_ok(n_rows, dst_ld, (int64_t)heads_per_block * 128) || !hv_grid_x_ok(n_rows)) return HV_ERR_ARG;
     if (n_rows == 0) return HV_OK;
     qknorm_rope_kernel<<<dim3((unsigned)n_rows), dim3(256), 0, stream>>>((bf16_t*)const_cast<void*>(qkv), (const bf16_t*)q_weight,
                                                                           (const bf16_t*)k_weight, cos_tab, sin_tab, n_rows, n_rope,
@@ -368,8 +377,9 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
 
 extern "C" int hv_linear_smallm_bf16(const void* x, const void* W, const void* bias, const void* addend, void* out, int M,
                                      int N, int K, int64_t ldx, int64_t ldo, int act, hipStream_t stream) {
-    if (!x || !W || !out || M < 1 || M > 4 || N < 1 || K < 8 || (K & 7) || (ldx & 7)) return HV_ERR_ARG;
-    dim3 grid((N + 3) / 4), block(256);
+    if (!x || !W || !out || M < 1 || M > 4 || N < 1 || K < 8 || (K & 7) || (ldx & 7) || (act & ~3)) return HV_ERR_ARG;
+    if (!hv_pitch_ok(M, ldo, N)) return HV_ERR_ARG;
+    dim3 grid((unsigned)(((int64_t)N + 3) / 4)), block(256);
     const bf16_t *xp = (const bf16_t*)x, *wp = (const bf16_t*)W, *bp = (const bf16_t*)bias, *ap = (const bf16_t*)addend;
     bf16_t* op = (bf16_t*)out;
     switch (M) {
@@ -405,6 +415,7 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
 extern "C" int hv_patchify_f32_bf16(const float* x, void* A, int C, int T, int H, int W, hipStream_t stream) {
     if (!x || !A || C <= 0 || T <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return HV_ERR_ARG;
     const int64_t n = (int64_t)T * (H / 2) * (W / 2) * C;
+    if (!hv_grid_x_ok((n + 255) / 256)) return HV_ERR_ARG;
     patchify_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(x, (bf16_t*)A, C, T, H, W);
     return hv_check_launch();
 }
@@ -426,8 +437,9 @@ __global__ __launch_bounds__(256) void unpatchify_kernel(const bf16_t* __restric
 }
 
 extern "C" int hv_unpatchify_bf16(const void* y, void* out, int C, int T, int H, int W, int64_t ldy, hipStream_t stream) {
-    if (!y || !out || C <= 0 || T <= 0 || (H & 1) || (W & 1) || (ldy & 3)) return HV_ERR_ARG;
+    if (!y || !out || C <= 0 || T <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || (ldy & 3)) return HV_ERR_ARG;
     const int64_t n = (int64_t)T * (H / 2) * (W / 2) * C;
+    if (!hv_grid_x_ok((n + 255) / 256)) return HV_ERR_ARG;
     unpatchify_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>((const bf16_t*)y, (bf16_t*)out, C, T, H,
                                                                                   W, ldy);
     return hv_check_launch();
@@ -447,7 +459,7 @@ __global__ __launch_bounds__(256) void euler_kernel(float* __restrict__ s, const
 }
 
 extern "C" int hv_euler_step_f32(float* sample, const void* model_out_bf16, float dt, int64_t n, hipStream_t stream) {
-    if (!sample || !model_out_bf16 || n < 0) return HV_ERR_ARG;
+    if (!sample || !model_out_bf16 || n < 0 || !hv_grid_x_ok((n / 4 + 256) / 256)) return HV_ERR_ARG;
     if (n == 0) return HV_OK;
     euler_kernel<<<dim3((unsigned)((n / 4 + 256) / 256)), dim3(256), 0, stream>>>(sample, (const bf16_t*)model_out_bf16, dt, n);
     return hv_check_launch();
@@ -467,7 +479,7 @@ __global__ __launch_bounds__(256) void euler_f32_kernel(float* __restrict__ s, c
 }
 
 extern "C" int hv_euler_step_f32_f32(float* sample, const float* model_out_f32, float dt, int64_t n, hipStream_t stream) {
-    if (!sample || !model_out_f32 || n < 0) return HV_ERR_ARG;
+    if (!sample || !model_out_f32 || n < 0 || !hv_grid_x_ok((n / 4 + 256) / 256)) return HV_ERR_ARG;
     if (n == 0) return HV_OK;
     euler_f32_kernel<<<dim3((unsigned)((n / 4 + 256) / 256)), dim3(256), 0, stream>>>(sample, model_out_f32, dt, n);
     return hv_check_launch();
@@ -502,7 +514,8 @@ __global__ __launch_bounds__(256) void bcast_row_kernel(const bf16_t* __restrict
 }
 
 extern "C" int hv_broadcast_row_bf16(const void* src, void* dst, int64_t n_rows, int D, int64_t ld, hipStream_t stream) {
-    if (!src || !dst || n_rows < 0 || D <= 0) return HV_ERR_ARG;
+    if (!src || !dst || n_rows < 0 || D <= 0 || !hv_pitch_ok(n_rows, ld, D)) return HV_ERR_ARG;
+    if (n_rows > ((int64_t)0x7fffffff * 256) / D) return HV_ERR_ARG;      // one thread per element: the block count must fit grid.x
     if (n_rows == 0) return HV_OK;
     bcast_row_kernel<<<dim3((unsigned)((n_rows * D + 255) / 256)), dim3(256), 0, stream>>>((const bf16_t*)src, (bf16_t*)dst,
                                                                                           n_rows, D, ld);
@@ -524,6 +537,7 @@ __global__ void timestep_embedding_kernel(const float* __restrict__ t, bf16_t* _
 
 extern "C" int hv_timestep_embedding_bf16(const float* t, void* out, int n_t, int dim, float max_period, hipStream_t stream) {
     if (!t || !out || n_t <= 0 || dim <= 0 || (dim & 1)) return HV_ERR_ARG;
+    if ((int64_t)n_t * dim > 0x7fffffff) return HV_ERR_ARG;      // the kernel indexes the [n_t, dim] output with int
     const int n = n_t * (dim / 2);
     timestep_embedding_kernel<<<dim3((n + 127) / 128), dim3(128), 0, stream>>>(t, (bf16_t*)out, n_t, dim, max_period);
     return hv_check_launch();
@@ -549,6 +563,7 @@ extern "C" int hv_copy3d_bf16(const void* src, void* dst, int n_batch, int64_t r
     if (!src || !dst || n_batch < 0 || rows < 0 || cols <= 0 || (cols & 7) || (src_ld & 7) || (dst_ld & 7) ||
         (src_batch_stride & 7) || (dst_batch_stride & 7) || rows > 0x7fffffff)
         return HV_ERR_ARG;
+    if (n_batch > 65535 || !hv_pitch_ok(rows, dst_ld, cols)) return HV_ERR_ARG;      // the batch is grid.z (at most 65535)
     if (n_batch == 0 || rows == 0) return HV_OK;
     const int64_t total = rows * (cols / 8);
     const unsigned gx = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);

@@ -504,7 +504,7 @@ inline unsigned grid_for(int64_t n) { return (unsigned)((n + 255) / 256 > 8192 ?
 inline bool views4(const int64_t* s0, const int64_t* s1, const int* dims, View4& v0, View4& v1, Dims4& d, int64_t& n) {
     n = 1;
     for (int i = 0; i < 4; ++i) {
-        if (dims[i] <= 0) return false;
+        if (dims[i] <= 0 || n > INT64_MAX / dims[i]) return false;
         v0.s[i] = s0[i], v1.s[i] = s1[i], d.d[i] = dims[i];
         n *= dims[i];
     }
@@ -606,7 +606,8 @@ extern "C" int hv_groupnorm_finalize_f16(const float* partial, int64_t partial_f
 
 extern "C" int hv_groupnorm_apply_f16(const void* x, int64_t ldx, void* y, int64_t ldy, int64_t M, int C, const float* affine,
                                       int silu, hipStream_t stream) {
-    if (!x || !y || !affine || M <= 0 || C < 8 || (C & 7) || C > 2048 || (ldx & 7) || (ldy & 7)) return HV_ERR_ARG;
+    if (!x || !y || !affine || M <= 0 || C < 8 || (C & 7) || C > 2048 || (ldx & 7) || (ldy & 7) || (silu & ~1) || !hv_pitch_ok(M, ldy, C))
+        return HV_ERR_ARG;
     const int nrl = 256 / (C >> 3);                                  // rows per block step
     const int64_t nblk = (M + 4 * nrl - 1) / (4 * nrl);             // four steps per block
     if (nblk > 0x7fffffff) return HV_ERR_ARG;
@@ -615,30 +616,31 @@ extern "C" int hv_groupnorm_apply_f16(const void* x, int64_t ldx, void* y, int64
     return hv_check_launch();
 }
 
-extern "C" int64_t hv_conv3d_cout4_planes_floats(int64_t M) { return M > 0 ? 27 * M * 3 : 0; }
+// (0 for a voxel count hv_conv3d_cout4_f16 refuses: T, H, W are ints and the gather pass runs one thread per voxel)
+extern "C" int64_t hv_conv3d_cout4_planes_floats(int64_t M) { return M > 0 && M <= (int64_t)0x7fffffff * 256 ? 27 * M * 3 : 0; }
 
 extern "C" int hv_conv3d_cout4_f16(const void* x, int64_t ldx, const float* affine, int silu, const void* w_frag, const void* bias, void* out,
                                    int64_t ldo, int T, int H, int W, int Cin, int Cout, float* planes, int64_t planes_floats, hipStream_t stream) {
     if (!x || !w_frag || !bias || !out || !planes || T <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin > 128 || (Cin & 31) || Cout <= 0 || Cout > 3 ||
         ldx < Cin || (ldx & 7) || ldo < Cout || (ldo >= 8 && (ldo & 7)) || ((uintptr_t)x & 15) || ((uintptr_t)out & 15) || ((uintptr_t)w_frag & 15))
         return HV_ERR_ARG;
+    if (silu & ~1) return HV_ERR_ARG;
     const int64_t M = (int64_t)T * H * W;
-    if (planes_floats < hv_conv3d_cout4_planes_floats(M)) return HV_ERR_ARG;
+    const int64_t gblk = (M + 255) / 256;
+    if (!hv_grid_x_ok(gblk) || planes_floats < hv_conv3d_cout4_planes_floats(M)) return HV_ERR_ARG;
     const int64_t ngrp = (M + 15) >> 4;
     const int64_t want = (ngrp + 3) / 4;
     const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);      // 4 waves per block, each walks 16-voxel groups grid-stride
     launch_silu(silu, conv_cout4_planes_kernel<true>, conv_cout4_planes_kernel<false>, dim3(blocks), stream, (const uint16_t*)x, ldx, affine,
                 (const u32x4*)w_frag, planes, M, Cin / 32);
     if (int rc = hv_check_launch(); rc != HV_OK) return rc;
-    const int64_t gblk = (M + 255) / 256;
-    if (gblk > 0x7fffffff) return HV_ERR_ARG;
     conv_cout4_gather_kernel<<<dim3((unsigned)gblk), dim3(256), 0, stream>>>(planes, (const uint16_t*)bias, (uint16_t*)out, ldo, T, H, W, Cout);
     return hv_check_launch();
 }
 
 extern "C" int hv_softmax_rows_f32_f16(const float* S, int64_t ld_s, void* P, int64_t ld_p, int rows, int cols, int cols_pad,
                                        float scale, int causal_block, hipStream_t stream) {
-    if (!S || !P || rows <= 0 || cols <= 0 || cols_pad < cols || causal_block < 0) return HV_ERR_ARG;
+    if (!S || !P || rows <= 0 || cols <= 0 || cols_pad < cols || causal_block < 0 || !hv_pitch_ok(rows, ld_p, cols_pad)) return HV_ERR_ARG;
     const bool vec = !(ld_s & 3) && !(ld_p & 3) && !(cols & 3) && !(cols_pad & 3) && !(causal_block & 3) &&
                      !((uintptr_t)S & 15) && !((uintptr_t)P & 7);
     if (vec)
@@ -649,14 +651,16 @@ extern "C" int hv_softmax_rows_f32_f16(const float* S, int64_t ld_s, void* P, in
 }
 
 extern "C" int hv_transpose_16b(const void* src, int64_t ld_src, void* dst, int64_t ld_dst, int R, int C, hipStream_t stream) {
-    if (!src || !dst || R <= 0 || C <= 0) return HV_ERR_ARG;
-    transpose16_kernel<<<dim3((C + 31) / 32, (R + 31) / 32), dim3(256), 0, stream>>>((const uint16_t*)src, ld_src, (uint16_t*)dst, ld_dst, R, C);
+    // the C output rows hold R elements each; R / 32 tile rows are grid.y (at most 65535)
+    if (!src || !dst || R <= 0 || C <= 0 || !hv_pitch_ok(C, ld_dst, R) || ((int64_t)R + 31) / 32 > 65535) return HV_ERR_ARG;
+    transpose16_kernel<<<dim3((unsigned)(((int64_t)C + 31) / 32), (unsigned)((R + 31) / 32)), dim3(256), 0, stream>>>((const uint16_t*)src, ld_src, (uint16_t*)dst, ld_dst, R, C);
     return hv_check_launch();
 }
 
 extern "C" int hv_vae_latent_tile_f16(const float* z, int64_t sc, int64_t st, int64_t sh, int64_t sw, int C, int T, int H, int W,
                                       int Cpad, void* out, hipStream_t stream) {
     if (!z || !out || C <= 0 || T <= 0 || H <= 0 || W <= 0 || Cpad < C) return HV_ERR_ARG;
+    if ((int64_t)T * H > INT64_MAX / ((int64_t)W * Cpad)) return HV_ERR_ARG;      // the element count is an int64
     latent_tile_kernel<<<dim3(grid_for((int64_t)T * H * W * Cpad)), dim3(256), 0, stream>>>(z, sc, st, sh, sw, C, T, H, W, Cpad, (uint16_t*)out);
     return hv_check_launch();
 }
@@ -694,7 +698,9 @@ extern "C" int hv_temporal_resample_f16(const void* x, int64_t ldx, void* out, i
     if (!x || !out || T_in <= 0 || HW <= 0 || C <= 0 || (C & 7) || (ldx & 7) || (ldo & 7) || s < 1 || (mode != 0 && mode != 1) ||
         (mode == 0 && k < 1))
         return HV_ERR_ARG;
+    if (mode == 1 && (int64_t)T_in * s > 0x7fffffff) return HV_ERR_ARG;
     const int t_out = mode == 1 ? T_in * s : (T_in - 1) / s + 1;
+    if (HW > INT64_MAX / ((int64_t)t_out * (C / 8)) || !hv_pitch_ok((int64_t)t_out * HW, ldo, C)) return HV_ERR_ARG;
     const int64_t total = (int64_t)t_out * HW * (C / 8);
     temporal_resample_kernel<<<dim3(grid_for(total)), dim3(256), 0, stream>>>((const uint16_t*)x, ldx, (uint16_t*)out, ldo, t_out, HW, C / 8,
                                                                              mode, k, s);

@@ -8,6 +8,19 @@
  * (paths relative to /root/reference/hyvideo/).  The Python host side that mirrors the reference
  * interface (the modules/ directory of the hunyuanvideo_efficiency_amd package) binds these symbols with ctypes;
  * INTEGRATION.md shows the binding a maintainer of the reference would add.
+ *
+ * Argument contract (tests/abi_contract.py lists it row by row, tests/test_capi_refusals_cpu.py checks it without a GPU):
+ *   - a bad argument is -1 (HV_ERR_ARG) BEFORE anything is enqueued; every condition an entry point enforces is stated in its comment.
+ *     Common to all: a pointer not marked nullable must not be NULL; extents are positive unless an early-out is named; flags and
+ *     enumerations take the listed values only; a shape whose launch grid or int index arithmetic would overflow (block counts
+ *     above 2^31 - 1, grid.y / grid.z above 65535, element counts that do not fit the index type) is refused, never truncated.
+ *   - early-outs return 0 (HV_OK) and touch no memory: M == 0, n == 0, n_rows == 0, n_q == 0, n_batch == 0, rows == 0 where named.
+ *   - OUTPUT PITCH RULE, every entry point that stores rows: a row pitch of an OUTPUT below the width stored per row is HV_ERR_ARG when
+ *     more than one row is stored (rows would overlap and two workgroups store to one address).  A single row is exempt: it has no
+ *     neighbour, and hosts report arbitrary strides for extents of 1 (a [1, N] torch view may carry stride(0) < N).  INPUT pitches
+ *     are not constrained beyond their alignment unless the comment says so (overlapping reads are well defined, pitch 0 broadcasts a
+ *     row).  Documented aliasing stays legal: res may alias out0, hv_qknorm_rope_bf16 works in place.
+ *   - the host queries (no stream argument) return 0 for every shape their kernel refuses and never a negative number.
  */
 #ifndef HV_KERNELS_H
 #define HV_KERNELS_H
@@ -43,7 +56,8 @@ int hv_abi_version(void);       /* HV_ABI_VERSION of the header the library was 
  *     (modules/models.py:161-164,182-185,235,246,338; modules/modulate_layers.py:31-49; mlp_layers.py:115-117)
  * mode 0: out = LN(x) * bf16(1 + scale[d]) + shift[d]      (shift/scale may be NULL = absent)
  * mode 1: out = LN(x) * weight[d] + bias[d]                (token_refiner.py:33-35,56-58 affine LayerNorm)
- * x/out: [M, D] bf16 with row strides ldx/ldo (elements); D % 8 == 0, D <= 4096. */
+ * x/out: [M, D] bf16 with row strides ldx/ldo (elements, % 8); D % 8 == 0, 0 < D <= 4096; M >= 0 (M == 0: HV_OK, nothing done), at most
+ * 4 * (2^31 - 1) rows; ldo >= D when M > 1 (output pitch rule). */
 int hv_ln_modulate_bf16(const void* x, const void* shift_or_bias, const void* scale_or_weight, void* out,
                         int64_t M, int D, int64_t ldx, int64_t ldo, float eps, int mode, hipStream_t stream);
 
@@ -52,7 +66,10 @@ int hv_ln_modulate_bf16(const void* x, const void* shift_or_bias, const void* sc
  *   row r: q head h at qkv[r*ld + h*128], k head h at qkv[r*ld + k_offset + h*128]  (v untouched).
  * Rows [0, n_rope) are rotated with cos/sin[r][128] (fp32); rows [n_rope, n_rows) are only normalised
  * (text tokens).  Writing in place into the joint [img|txt] QKV buffer removes the torch.cat of
- * models.py:195-197,358-359. head_dim must be 128. */
+ * models.py:195-197,358-359. head_dim must be 128; n_heads > 0; 0 <= n_rope <= n_rows <= 2^31 - 1 (n_rows == 0: HV_OK, nothing done);
+ * cos_tab / sin_tab may be NULL when n_rope == 0; ld % 8 == 0, k_offset % 8 == 0.  The q and k heads must be different columns of the
+ * row, k_offset >= n_heads * 128 (the row is rewritten in place: overlapping heads would be normalised twice), and the row must hold
+ * them, ld >= k_offset + n_heads * 128, when n_rows > 1 (output pitch rule). */
 int hv_qknorm_rope_bf16(void* qkv, const void* q_weight, const void* k_weight, const float* cos_tab,
                         const float* sin_tab, int64_t n_rows, int64_t n_rope, int n_heads, int head_dim,
                         int64_t ld, int64_t k_offset, float eps, hipStream_t stream);
@@ -60,7 +77,10 @@ int hv_qknorm_rope_bf16(void* qkv, const void* q_weight, const void* k_weight, c
 /* The same, OUT OF PLACE with a scatter by head block (sequence parallelism, hyvideo/modules/attenion.py:169-180: the q / k chunk
  * that is normalised here is exchanged by an all-to-all over head groups next): head hv of row r (hv = 0 .. 2*n_heads-1 in the
  * q-then-k order of the source row) is stored at dst[(hv / heads_per_block) * dst_block_stride + r * dst_ld + (hv % heads_per_block)
- * * 128] - the [peer][row][heads of that peer] send layout - so no pack copy follows.  The source row is not modified. */
+ * * 128] - the [peer][row][heads of that peer] send layout - so no pack copy follows.  The source row is not modified: ld and k_offset
+ * are only % 8 (q and k may be read from overlapping columns).  dst_ld % 8 == 0, dst_block_stride % 8 == 0, heads_per_block > 0;
+ * dst_ld >= heads_per_block * 128 when n_rows > 1 (output pitch rule); the block stride is free (the layout [row][block][heads] has it
+ * below a row). */
 int hv_qknorm_rope_scatter_bf16(const void* qkv, const void* q_weight, const void* k_weight, const float* cos_tab,
                                 const float* sin_tab, int64_t n_rows, int64_t n_rope, int n_heads, int head_dim, int64_t ld,
                                 int64_t k_offset, float eps, void* dst, int64_t dst_ld, int heads_per_block,
@@ -72,7 +92,10 @@ int hv_qknorm_rope_scatter_bf16(const void* qkv, const void* q_weight, const voi
  * out1[., n - n_split] (row stride ld1) with act1 (act: 0 none, 1 GELU-tanh, 2 SiLU) - the single-stream
  * block's linear1 split + mlp_act (models.py:339-341,392).  n_split <= 0 or >= N: no split.
  * If gate != NULL: out = res + bf16(bf16(y) * gate[n])  (x + apply_gate(y, gate), models.py:231-250,393);
- * res may alias out0.  K % 64 == 0, N % 8 == 0, all strides % 8 == 0. */
+ * res may alias out0.  K % 64 == 0 (K >= 64), N % 8 == 0, all strides % 8 == 0 (ld1 and ld_res only where out1 / res are used); a split
+ * needs out1 and n_split % 8 == 0; gate needs res; act0, act1 in 0..2; M >= 0 (M == 0: HV_OK, nothing done).  Output pitch rule, M > 1:
+ * ld0 >= the columns of out0 (n_split, or N without a split), ld1 >= N - n_split.  ceil(M / 256) * ceil(N / 256) (N <= 128: / 128)
+ * workgroups must fit 2^31 - 1. */
 int hv_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, int M, int N, int K,
                  void* out0, int64_t ld0, int act0, int n_split, void* out1, int64_t ld1, int act1,
                  const void* gate, const void* res, int64_t ld_res, hipStream_t stream);
@@ -81,12 +104,13 @@ int hv_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, const v
  * (ModulateDiT / adaLN: Linear(SiLU(vec)), modulate_layers.py:27-28), bit1: SiLU on output
  * (MLPEmbedder / TimestepEmbedder hidden layer, mlp_layers.py:72-73, embed_layers.py:140-150).
  * addend (nullable, same layout as out): out = bf16(y) + addend, the bf16 `vec = vec + embedder(...)` adds of
- * models.py:621,631 and token_refiner.py:229. */
+ * models.py:621,631 and token_refiner.py:229.  1 <= M <= 4, N >= 1, K >= 8 and % 8, ldx % 8 == 0; act has no bits besides 0 and 1;
+ * ldo >= N when M > 1 (output pitch rule; the [1, N] rows of the modulation vectors are exempt). */
 int hv_linear_smallm_bf16(const void* x, const void* W, const void* bias, const void* addend, void* out, int M,
                           int N, int K, int64_t ldx, int64_t ldo, int act, hipStream_t stream);
 
 /* timestep_embedding (modules/embed_layers.py:93-117,152-155): [cos(t f_i) | sin(t f_i)] in fp32 -> bf16;
- * t: n_t device floats. */
+ * t: n_t device floats, out [n_t, dim]; n_t > 0, dim > 0 and even, n_t * dim <= 2^31 - 1 (the kernel indexes with int). */
 int hv_timestep_embedding_bf16(const float* t, void* out, int n_t, int dim, float max_period, hipStream_t stream);
 
 /* K6/K6': softmax(scale * q k^T) v, bf16, head_dim 128, non-causal, over ONE contiguous key segment
@@ -102,14 +126,18 @@ int hv_timestep_embedding_bf16(const float* t, void* out, int n_t, int dim, floa
  *      Ulysses-8): the key range is split in two halves processed by separate workgroups and merged (log-sum-exp) by a second
  *      tiny kernel: shorter makespan, same result up to fp32 rounding.
  * Without a workspace the single-pass kernel with the online maximum always runs.  A workspace must not be shared by launches
- * that can run concurrently (different streams). */
+ * that can run concurrently (different streams).
+ * head_dim must be 128; n_heads > 0; n_q >= 0 (n_q == 0: HV_OK, nothing done); 0 < n_kv <= 2^31 - 2049 when there are queries;
+ * stride_q, stride_k, stride_v % 8 == 0, stride_o % 4 == 0; stride_o >= n_heads * 128 when n_q > 1 (output pitch rule);
+ * ceil(n_q / 256) * n_heads workgroups must fit 2^31 - 1.  A workspace too small for a step only switches that step off. */
 #define HV_ATTN_MIN_WORKSPACE_BYTES 256
 #define HV_ATTN_BOUND_MIN_KV 4096
 int hv_attn_fwd_bf16(const void* q, const void* k, const void* v, void* o, int64_t stride_q, int64_t stride_k,
                      int64_t stride_v, int64_t stride_o, int n_q, int n_kv, int n_heads, int head_dim,
                      float scale, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
-/* bytes of scratch hv_attn_fwd_bf16 can use: the 256-byte bound area + the partials of a 2-way KV split (returned as int64). */
+/* bytes of scratch hv_attn_fwd_bf16 can use: the 256-byte bound area + the partials of a 2-way KV split (returned as int64);
+ * 0 for extents hv_attn_fwd_bf16 refuses (n_q == 0 is its early-out: the bound area alone). */
 int64_t hv_attn_workspace_bytes(int n_q, int n_kv, int n_heads);
 /* crc32 of the generated steady-state iteration (csrc/hv_attention_w4_loop.inc, `#define HV_W4_LOOP_SIGNATURE`) the library's attention
  * kernel was compiled from: lets a host check that the library in front of it is the product build and not a timing experiment. */
@@ -119,46 +147,54 @@ int hv_attn_w4_loop_signature(void);        /* the 32 bits of the crc, as int */
  * modules/attenion.py:169-180): the queries of one rank against ONE K/V chunk.  Leaves the unnormalised partial in slot(s)
  * [slot, slot+splits) of caller-owned buffers part_o = float[n_slots][n_q][n_heads][128], part_ml = float[n_slots][n_q][n_heads][2]
  * (running max in the log2 domain, denominator).  splits = 1 | 2: 2 halves the key range over two workgroup sets (load balance,
- * see hv_attn_suggest_splits) and fills two slots. */
+ * see hv_attn_suggest_splits) and fills two slots; it needs two key tiles (n_kv > 64).  Extents and input strides as hv_attn_fwd_bf16
+ * (n_kv > 0 always); 0 <= slot, slot + splits <= n_slots.  n_q == 0: HV_OK, nothing done. */
 int hv_attn_partial_bf16(const void* q, const void* k, const void* v, int64_t stride_q, int64_t stride_k, int64_t stride_v,
                          int n_q, int n_kv, int n_heads, int head_dim, float scale, void* part_o, void* part_ml,
                          int n_slots, int slot, int splits, hipStream_t stream);
 
-/* Online-softmax merge of all n_slots partials: o = sum_s O_s 2^(m_s-m) / sum_s l_s 2^(m_s-m), written as bf16 rows. */
+/* Online-softmax merge of all n_slots partials: o = sum_s O_s 2^(m_s-m) / sum_s l_s 2^(m_s-m), written as bf16 rows.
+ * n_heads > 0, n_slots > 0, n_q >= 0 (n_q == 0: HV_OK, nothing done), n_q * n_heads / 8 workgroups must fit 2^31 - 1; stride_o % 4 == 0
+ * and >= n_heads * 128 when n_q > 1 (output pitch rule). */
 int hv_attn_merge_bf16(const void* part_o, const void* part_ml, void* o, int64_t stride_o, int n_q, int n_heads, int n_slots,
                        hipStream_t stream);
 
-/* 1 or 2: whether splitting the key range shortens the makespan of this launch shape on 256 CUs. */
+/* 1 or 2: whether splitting the key range shortens the makespan of this launch shape on 256 CUs; 0 for extents hv_attn_fwd_bf16 refuses. */
 int hv_attn_suggest_splits(int n_q, int n_kv, int n_heads);
 
-/* K10 gather: fp32 latent [C,T,H,W] -> bf16 patch rows [T*(H/2)*(W/2), C*4] (embed_layers.py:40-59). */
+/* K10 gather: fp32 latent [C,T,H,W] -> bf16 patch rows [T*(H/2)*(W/2), C*4] (embed_layers.py:40-59).  C, T > 0; H, W > 0 and even;
+ * at most 256 * (2^31 - 1) (token, channel) pairs. */
 int hv_patchify_f32_bf16(const float* x, void* A, int C, int T, int H, int W, hipStream_t stream);
 
-/* unpatchify (models.py:697-710): y[tok][c*4+ph*2+pw] (row stride ldy) -> out[C,T,H,W] bf16. */
+/* unpatchify (models.py:697-710): y[tok][c*4+ph*2+pw] (row stride ldy, % 4) -> out[C,T,H,W] bf16.  C, T > 0; H, W > 0 and even;
+ * at most 256 * (2^31 - 1) (token, channel) pairs. */
 int hv_unpatchify_bf16(const void* y, void* out, int C, int T, int H, int W, int64_t ldy, hipStream_t stream);
 
 /* K13: FlowMatchDiscreteScheduler.step (scheduling_flow_match_discrete.py:236-242):
- * sample_f32[i] += f32(model_out_bf16[i]) * dt. */
+ * sample_f32[i] += f32(model_out_bf16[i]) * dt.  0 <= n < 2^41 - 1024 (n == 0: HV_OK, nothing done). */
 int hv_euler_step_f32(float* sample, const void* model_out_bf16, float dt, int64_t n, hipStream_t stream);
 
-/* K13 with an fp32 velocity (the reference upcasts model_output, :239): sample_f32[i] += model_out_f32[i] * dt. */
+/* K13 with an fp32 velocity (the reference upcasts model_output, :239): sample_f32[i] += model_out_f32[i] * dt.  n as above. */
 int hv_euler_step_f32_f32(float* sample, const float* model_out_f32, float dt, int64_t n, hipStream_t stream);
 
-/* token_refiner.py:222-228: out[d] = sum_l x[l][d]*mask[l] / sum_l mask[l]  (mask NULL = plain mean). */
+/* token_refiner.py:222-228: out[d] = sum_l x[l][d]*mask[l] / sum_l mask[l]  (mask NULL = plain mean).  L > 0, D > 0. */
 int hv_masked_mean_bf16(const void* x, const int* mask, void* out, int L, int D, hipStream_t stream);
 
-/* token_refiner.py:155-157: fully masked query rows see only key 0 -> their attention output is v[0]. */
+/* token_refiner.py:155-157: fully masked query rows see only key 0 -> their attention output is v[0].  D > 0, n_rows >= 0 (n_rows == 0:
+ * HV_OK, nothing done), n_rows * D <= 256 * (2^31 - 1); ld >= D when n_rows > 1 (output pitch rule). */
 int hv_broadcast_row_bf16(const void* src, void* dst, int64_t n_rows, int D, int64_t ld, hipStream_t stream);
 
 /* C1 pack/unpack: batched strided 2-D copy dst[b][r][c] = src[b][r][c] with independent batch/row strides
  * (elements).  Re-lays tokens x heads for the Ulysses all-to-all (xfuser SeqAllToAll4D reached from
- * modules/attenion.py:169-180); the exchange itself is RCCL (torch.distributed "nccl"). cols % 8 == 0. */
+ * modules/attenion.py:169-180); the exchange itself is RCCL (torch.distributed "nccl"). cols % 8 == 0 (cols > 0), all four strides % 8;
+ * 0 <= n_batch <= 65535 and 0 <= rows <= 2^31 - 1 (n_batch == 0 or rows == 0: HV_OK, nothing done); dst_ld >= cols when rows > 1 (output
+ * pitch rule).  The batch strides are free: the unpack out[r][p * w + c] = recv[p][r][c] has dst_batch_stride = w below dst_ld. */
 int hv_copy3d_bf16(const void* src, void* dst, int n_batch, int64_t rows, int cols, int64_t src_batch_stride,
                    int64_t src_ld, int64_t dst_batch_stride, int64_t dst_ld, hipStream_t stream);
 
 /* K14: FP8 weight-only Linear (modules/fp8_optimization.py:50-53,55-80): out = bf16(bf16(w_e4m3fn[i]) * scale_bf16),
  * the per-forward dequantisation the reference performs before F.linear; the GEMM then runs on hv_gemm_bf16.
- * OCP e4m3fn (gfx950-native).  n % 8 == 0. */
+ * OCP e4m3fn (gfx950-native).  n > 0, n % 8 == 0. */
 int hv_fp8_dequant_bf16(const void* w_e4m3fn, const void* scale_bf16, void* out_bf16, int64_t n, hipStream_t stream);
 
 /* ---- FP8-MFMA path (opt-in; BASELINE.json configs[3] "fp8 weight path (CDNA4 fp8 MFMA)").  The reference's FP8 is weight-only
@@ -174,18 +210,20 @@ int hv_fp8_dequant_bf16(const void* w_e4m3fn, const void* scale_bf16, void* out_
  * NaN codes); |x| / s_row <= 448 holds with the floor as without it.  Such a row quantises coarsely (it is < 2^-117 everywhere). */
 
 /* K1 with an fp8 output: y = bf16(LN(x) * bf16(1 + scale) + shift) (hv_ln_modulate_bf16 mode 0), then per-row quantisation:
- * out_q [M, D] e4m3 bytes (row stride ldq bytes, % 16), out_row_scale [M] fp32. */
+ * out_q [M, D] e4m3 bytes (row stride ldq bytes, % 16), out_row_scale [M] fp32.  D, M, ldx as hv_ln_modulate_bf16; ldq >= D when M > 1
+ * (output pitch rule). */
 int hv_ln_modulate_fp8(const void* x, const void* shift, const void* scale, void* out_q, float* out_row_scale, int64_t M,
                        int D, int64_t ldx, int64_t ldq, float eps, hipStream_t stream);
 
 /* per-row quantisation of bf16 rows x[M, K] (row stride ldx elements) -> e4m3 rows + fp32 row scales (A operands that are not
- * LayerNorm outputs: attention output, GELU(MLP) hidden, the single block's [attn | mlp] concat). */
+ * LayerNorm outputs: attention output, GELU(MLP) hidden, the single block's [attn | mlp] concat).  K > 0 and % 8, ldx % 8 == 0,
+ * ldq % 16 == 0; M >= 0 (M == 0: HV_OK, nothing done), at most 4 * (2^31 - 1) rows; ldq >= K when M > 1 (output pitch rule). */
 int hv_quant_rows_fp8(const void* x, int64_t ldx, void* out_q, int64_t ldq, float* out_row_scale, int64_t M, int K,
                       hipStream_t stream);
 
 /* C = (A_q . W_q^T) * a_row_scale[m] * w_scale + bias with hv_gemm_bf16's epilogue arguments.  A_q [M, K], W_q [N, K]: e4m3fn
  * bytes (row strides lda / ldw in bytes, % 16); w_scale_bf16: ONE bf16 on the device (the layer's `fp8_scale`).
- * K % 128 == 0, K >= 384. */
+ * K % 128 == 0, K >= 384; everything else as hv_gemm_bf16 (M == 0: HV_OK, nothing done). */
 int hv_gemm_fp8(const void* A_q, int64_t lda, const float* a_row_scale, const void* W_q, int64_t ldw, const void* w_scale_bf16,
                 const void* bias, int M, int N, int K, void* out0, int64_t ld0, int act0, int n_split, void* out1, int64_t ld1,
                 int act1, const void* gate, const void* res, int64_t ld_res, hipStream_t stream);
@@ -196,7 +234,8 @@ int hv_gemm_fp8(const void* A_q, int64_t lda, const float* a_row_scale, const vo
 
 /* fp16 Linear on MFMA (diffusers Attention to_q/to_k/to_v/to_out of the VAE mid block, unet_causal_3d_blocks.py:579-593;
  * 1x1x1 convs: post_quant_conv autoencoder_kl_causal_3d.py:115 and conv_shortcut unet_causal_3d_blocks.py:339-347).
- * out = A.W^T + bias; out_is_f32: fp32 result (attention scores); res (nullable): out = res + f16(y). */
+ * out = A.W^T + bias; out_is_f32 (0 | 1): fp32 result (attention scores; no res then); res (nullable): out = res + f16(y).
+ * K, N, strides, M == 0 and the workgroup limit as hv_gemm_bf16; ldo (in elements of the result type) >= N when M > 1 (output pitch rule). */
 int hv_gemm_f16(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, int M, int N, int K,
                 void* out, int64_t ldo, int out_is_f32, const void* res, int64_t ld_res, hipStream_t stream);
 
@@ -206,6 +245,8 @@ int hv_gemm_f16(const void* A, int64_t lda, const void* W, int64_t ldw, const vo
  * w_taps: [Cout][27][Cin] fp16 (tap = (dt*3 + dh)*3 + dw); out: [T*H*W, Cout]; res (nullable): out = res + f16(y)
  * (ResnetBlockCausal3D residual :413-415).  Cin % 64 == 0, Cout % 8 == 0 (callers zero-pad 16->64 and 3->8).
  * The source is addressed with 32-bit byte offsets: sT*sH*sW*ldx*2 must be < 4 GiB (HV_ERR_ARG otherwise).
+ * T, H, W > 0 with T*H*W <= 2^31 - 1; up_t, up_hw 0 | 1 (up_t: T odd; up_hw: H, W even); ldx, ldo, ld_res % 8 == 0; ldo >= Cout when
+ * T*H*W > 1 (output pitch rule).
  * gn_partial (nullable, device fp32 [hv_gn_partial_rows(T*H*W)][Cout][2], gn_partial_floats = its size): the epilogue also
  * leaves the GroupNorm statistics of the tensor it stores - per 64-row block b and pair of adjacent columns (c, c+1), c even, over the
  * k valid values: gn_partial[b][c] = (S = sum, C2 = sum of (x - S/k)^2), gn_partial[b][c+1] = (0, k); every entry written once, in a
@@ -215,9 +256,10 @@ int hv_conv3d_causal_f16(const void* x, int64_t ldx, const void* w_taps, const v
                          int T, int H, int W, int Cin, int Cout, int up_t, int up_hw, const void* res,
                          int64_t ld_res, float* gn_partial, int64_t gn_partial_floats, hipStream_t stream);
 
-/* rows of the gn_partial buffer for an output of M rows: one per 64 output rows, whole 256-row tiles. */
+/* rows of the gn_partial buffer for an output of M rows: one per 64 output rows, whole 256-row tiles; 0 unless 0 < M <= 2^31 - 1. */
 int64_t hv_gn_partial_rows(int64_t M);
-/* ... and for hv_conv3d_upsampled_subpixel_f16, whose M tiles are formed per parity class (some blocks cover no row: zeros). */
+/* ... and for hv_conv3d_upsampled_subpixel_f16, whose M tiles are formed per parity class (some blocks cover no row: zeros); 0 for a
+ * source grid that kernel refuses. */
 int64_t hv_subpixel_gn_partial_rows(int sT, int sH, int sW, int up_t);
 
 /* UpsampleCausal3D (unet_causal_3d_blocks.py:154-172: nearest x2 in H, W - and in T with the first frame kept single - then the
@@ -231,7 +273,9 @@ int64_t hv_subpixel_gn_partial_rows(int sT, int sH, int sW, int up_t);
  * [classes][ntap], source offset of each tap as (ot+8) | (oh+8)<<4 | (ow+8)<<8.  Weights and table come from the caller
  * (vae_ops.subpixel_weights): a summed weight is rounded to fp16 once ("fast": <= 2 fp16 ulp from the 27-tap form), or its rounding
  * residue rides along as an extra tap with the same offset ("exact": products exact, as in the 27-tap form).
- * Cin a power of two >= 256, Cout > 128 and % 8 == 0 (the decoder's 256- and 512-channel upsamplers).
+ * Cin a power of two >= 256, Cout > 128 and % 8 == 0 (the decoder's 256- and 512-channel upsamplers).  1 <= ntap <= 27, up_t 0 | 1,
+ * 0 < sT <= 254, 0 < sH, sW <= 4096 (packed gather coordinates), output voxels <= 2^31 - 1, source below 4 GiB as above; ldx, ldo % 8 == 0,
+ * ldo >= Cout (output pitch rule).
  * gn_partial: as for hv_conv3d_causal_f16, [hv_subpixel_gn_partial_rows(sT, sH, sW, up_t)][Cout][2]. */
 int hv_conv3d_upsampled_subpixel_f16(const void* x, int64_t ldx, const void* w_sub, const void* tap_table, int ntap,
                                      const void* bias, void* out, int64_t ldo, int sT, int sH, int sW, int Cin, int Cout,
@@ -246,7 +290,9 @@ int hv_conv3d_upsampled_subpixel_f16(const void* x, int64_t ldx, const void* w_s
  * hv_groupnorm_apply_f16; silu: 0 | 1.  w_frag: the weights in MFMA fragment order, fp16 [7][4][64][8]: row block nb, k step ks, lane l,
  * element j = w[c][ks*32 + 8*(l>>4) + j][tap] with 4*tap + c = 16*nb + (l & 15), zero for c == 3, tap >= 27 and channels >= Cin
  * (vae_ops.cout4_weight_fragments builds it).  out: [T*H*W][ldo]: ldo >= 8: columns Cout..7 are written as zeros (one 16-byte store).
- * planes: workspace of hv_conv3d_cout4_planes_floats(T*H*W) floats.  Cin % 32 == 0, Cin <= 128, Cout <= 3.  The sum over the taps is
+ * planes: workspace of hv_conv3d_cout4_planes_floats(T*H*W) floats (HV_ERR_ARG if planes_floats is below it; the query returns 0 unless
+ * 0 < M <= 256 * (2^31 - 1), the most voxels the kernel takes).  Cin % 32 == 0, 0 < Cin <= 128, 0 < Cout <= 3; ldx % 8 == 0; ldo >= Cout
+ * and % 8 from 8 on; x, out, w_frag 16-byte aligned; bias is required.  The sum over the taps is
  * taken in a fixed order: results are run-to-run identical (not bit-identical to hv_conv3d_causal_f16: another summation order). */
 int hv_conv3d_cout4_f16(const void* x, int64_t ldx, const float* affine, int silu, const void* w_frag, const void* bias, void* out,
                         int64_t ldo, int T, int H, int W, int Cin, int Cout, float* planes, int64_t planes_floats, hipStream_t stream);
@@ -254,21 +300,24 @@ int64_t hv_conv3d_cout4_planes_floats(int64_t M);
 
 /* DownsampleCausal3D (VAE encoder, unet_causal_3d_blocks.py:185-247): the same padding as hv_conv3d_causal_f16, then the 3x3x3
  * conv with stride 1|2 per axis (the fork's t_ops `downsample_stride` override, :737-742, changes these strides).
- * x: source [sT,sH,sW,Cin]; out: [T*H*W, Cout] with T = (sT-1)/stride_t + 1, H = (sH-1)/stride_h + 1, W likewise. */
+ * x: source [sT,sH,sW,Cin]; out: [T*H*W, Cout] with T = (sT-1)/stride_t + 1, H = (sH-1)/stride_h + 1, W likewise.  Cin, Cout, ldx, ldo,
+ * the 4 GiB source rule and the output pitch rule as hv_conv3d_causal_f16; sT*sH*sW <= 2^31 - 1. */
 int hv_conv3d_causal_strided_f16(const void* x, int64_t ldx, const void* w_taps, const void* bias, void* out, int64_t ldo,
                                  int sT, int sH, int sW, int Cin, int Cout, int stride_t, int stride_h, int stride_w,
                                  hipStream_t stream);
 
 /* The fork's temporal ops on a channels-last activation x[T_in][HW][C] (unet_causal_3d_blocks.py:657-672,764-783,884-907).
  * mode 0: F.pad(replicate, k-1 frames in front) + F.avg_pool3d((k,1,1), stride (s,1,1)) -> T_out = (T_in-1)/s + 1;
- * mode 1: F.interpolate(scale_factor=(s,1,1), mode="nearest") -> T_out = T_in*s.  C % 8 == 0. */
+ * mode 1: F.interpolate(scale_factor=(s,1,1), mode="nearest") -> T_out = T_in*s (must fit an int).  C % 8 == 0, ldx, ldo % 8 == 0,
+ * T_in, HW > 0, s >= 1, k >= 1 in mode 0, mode 0 | 1; T_out * HW * C / 8 must fit an int64; ldo >= C when T_out * HW > 1 (output pitch rule). */
 int hv_temporal_resample_f16(const void* x, int64_t ldx, void* out, int64_t ldo, int T_in, int64_t HW, int C, int mode,
                              int k, int s, hipStream_t stream);
 
 /* K16 pass 1+2: GroupNorm statistics (nn.GroupNorm(32, C, eps 1e-6, affine), unet_causal_3d_blocks.py:302,323) folded
  * into a per-channel affine: affine_out[2c] = rstd_g*w[c], affine_out[2c+1] = b[c] - mean_g*rstd_g*w[c].  The moments are summed
  * about a pivot per group (its first channel in row 0), so an offset group mean does not cancel the variance.
- * partial_ws: caller workspace of partial_ws_floats floats (>= 2*C; 2*C*1024 for full parallelism). */
+ * partial_ws: caller workspace of partial_ws_floats floats (>= 2*C; 2*C*1024 for full parallelism).  M > 0; C % 8 == 0, 8 <= C <= 2048,
+ * C / 8 a divisor of 256; groups a power of two <= 64 dividing C; ldx % 8 == 0. */
 int hv_groupnorm_affine_f16(const void* x, int64_t ldx, int64_t M, int C, int groups, float eps, const void* weight,
                             const void* bias, float* partial_ws, int64_t partial_ws_floats, float* affine_out,
                             hipStream_t stream);
@@ -279,41 +328,45 @@ int hv_groupnorm_affine_f16(const void* x, int64_t ldx, int64_t M, int C, int gr
  * buffer in floats: HV_ERR_ARG unless it is >= align2(nrow*C*2) + HV_GN_FOLD_WS_FLOATS (a buffer sized for the conv alone is too
  * small and is refused, never overrun).  Folded in fp64 in a fixed order: sum x^2 of an entry = C2 + S^2 / k, so the variance
  * var = Q/n - mean^2 cancels only in fp64.  The epilogue credits each pair of adjacent channels to the even one, so C / groups must
- * be even (HV_ERR_ARG otherwise). */
+ * be even (HV_ERR_ARG otherwise).  nrow, M > 0; C and groups as hv_groupnorm_affine_f16 (any C % 8 == 0). */
 #define HV_GN_FOLD_WS_FLOATS 16384
 int hv_groupnorm_finalize_f16(const float* partial, int64_t partial_floats, int64_t nrow, int64_t M, int C, int groups, float eps,
                               const void* weight, const void* bias, float* affine_out, hipStream_t stream);
 
-/* K16 pass 3: y = [SiLU](x*affine[2c] + affine[2c+1]) -> fp16 (norm + nonlinearity, unet_causal_3d_blocks.py:361-363,399-405). */
+/* K16 pass 3: y = [SiLU](x*affine[2c] + affine[2c+1]) -> fp16 (norm + nonlinearity, unet_causal_3d_blocks.py:361-363,399-405).
+ * silu 0 | 1; M > 0; C % 8 == 0, 8 <= C <= 2048; ldx, ldy % 8 == 0; ldy >= C when M > 1 (output pitch rule). */
 int hv_groupnorm_apply_f16(const void* x, int64_t ldx, void* y, int64_t ldy, int64_t M, int C, const float* affine,
                            int silu, hipStream_t stream);
 
 /* K18: P = softmax(scale * S) row-wise, fp32 -> fp16, columns [valid, cols_pad) zero-filled (K padding of the P.V GEMM).
  * causal_block = 0: valid = cols for every row.  causal_block = HW > 0: the frame-causal mask of prepare_causal_attention_mask
  * (unet_causal_3d_blocks.py:38-46) - row r belongs to frame r / HW and sees the keys of frames <= its own: valid =
- * min(cols, (r / HW + 1) * HW) - so one launch covers all frames of a tile. */
+ * min(cols, (r / HW + 1) * HW) - so one launch covers all frames of a tile.  rows, cols > 0, cols_pad >= cols, causal_block >= 0;
+ * ld_p >= cols_pad when rows > 1 (output pitch rule). */
 int hv_softmax_rows_f32_f16(const float* S, int64_t ld_s, void* P, int64_t ld_p, int rows, int cols, int cols_pad,
                             float scale, int causal_block, hipStream_t stream);
 
-/* [R][C] -> [C][R] for 16-bit elements (V^T for the P.V GEMM). */
+/* [R][C] -> [C][R] for 16-bit elements (V^T for the P.V GEMM).  R, C > 0, R <= 65535 * 32; ld_dst >= R when C > 1 (output pitch rule). */
 int hv_transpose_16b(const void* src, int64_t ld_src, void* dst, int64_t ld_dst, int R, int C, hipStream_t stream);
 
 /* latent crop: fp32 z[C,T,H,W] region (element strides) -> channels-last fp16 [T,H,W,Cpad] (zero-padded channels):
- * the tile slicing of autoencoder_kl_causal_3d.py:443,520 + the fp16 cast of autocast. */
+ * the tile slicing of autoencoder_kl_causal_3d.py:443,520 + the fp16 cast of autocast.  C, T, H, W > 0, Cpad >= C, T*H*W*Cpad must fit
+ * an int64; the source strides are free. */
 int hv_vae_latent_tile_f16(const float* z, int64_t sc, int64_t st, int64_t sh, int64_t sw, int C, int T, int H, int W,
                            int Cpad, void* out, hipStream_t stream);
 
 /* K19: blend_v / blend_h / blend_t (autoencoder_kl_causal_3d.py:344-360) on strided [C,T,H,W] fp16 views:
- * b[i] = f16(f16(a[i]*(1 - y/extent)) + f16(b[i]*(y/extent))), y = index along `axis`; dims[axis] <= extent. */
+ * b[i] = f16(f16(a[i]*(1 - y/extent)) + f16(b[i]*(y/extent))), y = index along `axis` (0..3); dims[axis] <= extent, extent > 0.
+ * a_strides, b_strides (int64 [4]) and dims (int [4], all > 0, product within an int64) are HOST arrays, read before the call returns. */
 int hv_vae_blend_f16(const void* a, const int64_t* a_strides, void* b, const int64_t* b_strides, const int* dims,
                      int axis, int extent, hipStream_t stream);
 
-/* crop + concat of tiles (autoencoder_kl_causal_3d.py:463-465,531-537): strided 4-D copy of 16-bit elements. */
+/* crop + concat of tiles (autoencoder_kl_causal_3d.py:463-465,531-537): strided 4-D copy of 16-bit elements; host arrays as above. */
 int hv_copy4d_16b(const void* src, const int64_t* src_strides, void* dst, const int64_t* dst_strides, const int* dims,
                   hipStream_t stream);
 
 /* K20 tail: (image / 2 + 0.5).clamp(0, 1) in fp16 then .float() (pipeline_hunyuan_video.py:1090-1092).  A NaN input gives a NaN, as
- * torch's clamp keeps it (it is not clamped to 0). */
+ * torch's clamp keeps it (it is not clamped to 0).  n > 0. */
 int hv_vae_postprocess_f16_f32(const void* x, float* out, int64_t n, hipStream_t stream);
 
 /* Reconstruction scoring (evaluation/compute_metrics.py:31-41 compute_psnr / compute_ssim of the fork, without the mp4 round trip):
@@ -326,7 +379,8 @@ int hv_vae_postprocess_f16_f32(const void* x, float* out, int64_t n, hipStream_t
  * such a frame SSIM 1).  Box moments are exact integers; the map value is fp32, summed in fp64 in a fixed order (no atomics: run-to-run
  * identical).  passes: 3 = both; 1 = the statistics pass alone (sse, minmax); 2 = the SSIM pass alone, reading the data range from a
  * `minmax` an earlier statistics pass filled (how tools/bench_metrics.py times the two separately).  workspace: >= hv_video_metrics_workspace_bytes(C, T, H, W) bytes, 16-byte aligned.  H < 7 or W < 7, T > 65535 and
- * negative or overlapping strides are HV_ERR_ARG (the workspace query returns 0 for them). */
+ * negative or overlapping strides (*_sh < W) are HV_ERR_ARG (the workspace query returns 0 for the shapes among them), as are H or W above
+ * 65536, C other than 1 | 3, T < 1, dtype or rescale other than 0 | 1, passes outside 1..3 and a workspace that is too small. */
 int hv_video_metrics(const void* a, int64_t a_sc, int64_t a_st, int64_t a_sh, const void* b, int64_t b_sc, int64_t b_st,
                      int64_t b_sh, int dtype, int C, int T, int H, int W, int rescale, int passes, void* sse, void* minmax,
                      void* ssim_sum, void* workspace, int64_t workspace_bytes, hipStream_t stream);
@@ -343,26 +397,31 @@ int64_t hv_video_metrics_workspace_bytes(int C, int T, int H, int W);
  * 147-154, and the input scaling of compute_metrics.py:44-60): reads the two videos a, b [3,T,H,W] as hv_video_metrics does (dtype,
  * element strides, rescale, the same 8-bit quantiser) and feeds the conv lut[c][q], a host-built float [3][256] holding
  * ((float32(q / 255.0) * 2 - 1) - shift[c]) / scale[c]; padding is zero in that scaled domain.  k = (c * 11 + ky) * 11 + kx, K = 363
- * (w is [384][64]).  y: [2T][(H - 7) / 4 + 1][(W - 7) / 4 + 1][64].  H or W < 31 (the smallest input with a tap-5 pixel) is HV_ERR_ARG. */
+ * (w is [384][64]).  y: [2T][(H - 7) / 4 + 1][(W - 7) / 4 + 1][64].  H or W < 31 (the smallest input with a tap-5 pixel) is HV_ERR_ARG, as
+ * are H or W above 65536, T outside [1, 32767], dtype or rescale other than 0 | 1, negative strides and *_sh < W. */
 int hv_lpips_conv1_f32(const void* a, int64_t a_sc, int64_t a_st, int64_t a_sh, const void* b, int64_t b_sc, int64_t b_st,
                        int64_t b_sh, int dtype, int T, int H, int W, int rescale, const float* lut, const float* w,
                        const float* bias, float* y, hipStream_t stream);
 
 /* Layers 2-5 (pretrained_networks.py:68-77,82-90: Conv2d(64, 192, 5, padding=2), Conv2d(192, 384, 3, padding=1), Conv2d(384, 256, 3,
  * padding=1), Conv2d(256, 256, 3, padding=1), each + ReLU): y[N][OH][OW][Cout] = relu(conv(x[N][H][W][Cin], stride 1, zero padding
- * `pad`) + bias), OH = H + 2 pad - ksize + 1.  k = (ky * ksize + kx) * Cin + ci.  Cin % 32 == 0, Cout % 64 == 0, pad < ksize <= 11. */
+ * `pad`) + bias), OH = H + 2 pad - ksize + 1.  k = (ky * ksize + kx) * Cin + ci.  Cin % 32 == 0, Cout % 64 == 0, 0 <= pad < ksize <= 11
+ * (ksize >= 1); Cin in [32, 4096], Cout in [64, 4096]; N >= 1, H, W in [1, 65536], OH, OW >= 1, N*H*W and N*OH*OW <= 2^31 - 1; x (and w)
+ * 16-byte aligned. */
 int hv_lpips_conv2d_f32(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
                         int ksize, int pad, hipStream_t stream);
 
 /* MaxPool2d(kernel_size=3, stride=2) between taps 1-2 and 2-3 (torchvision alexnet features[2], [5]; pretrained_networks.py:66-71):
- * x [N][H][W][C] -> y [N][(H - 3) / 2 + 1][(W - 3) / 2 + 1][C], C % 4 == 0, H, W >= 3. */
+ * x [N][H][W][C] -> y [N][(H - 3) / 2 + 1][(W - 3) / 2 + 1][C], C % 4 == 0, 4 <= C <= 4096, H, W in [3, 65536], N >= 1, x and y 16-byte
+ * aligned, output elements / 4 <= 256 * (2^31 - 1). */
 int hv_lpips_maxpool_f32(const float* x, float* y, int N, int H, int W, int C, hipStream_t stream);
 
 /* One tap's distance (lpips.py:122-130 with lpips/__init__.py:13-15 normalize_tensor and the NetLinLayer 1x1 conv of lpips.py:157-167):
  * f [2T][P][C] (P pixels), lin [C]; out[t * 5 + layer] = sum over pixels of sum_c lin[c] (f0 / (sqrt(sum f0^2) + 1e-10) - f1 / (...))^2
  * in fp64, frame t comparing image t with image T + t (the caller divides by P: spatial_average, and adds the five taps).  C <= 384.
  * Workgroup partials go to `workspace` (>= hv_lpips_distance_workspace_bytes(T, P) bytes, 8-byte aligned) and are folded in a fixed
- * order: no atomics, run-to-run identical, and a frame's bits do not depend on T. */
+ * order: no atomics, run-to-run identical, and a frame's bits do not depend on T.  T in [1, 65535], P >= 1, C >= 1, layer in 0..4
+ * (the query returns 0 for T, P outside these). */
 int hv_lpips_distance_f32(const float* f, const float* lin, int T, int64_t P, int C, int layer, double* out, void* workspace,
                           int64_t workspace_bytes, hipStream_t stream);
 int64_t hv_lpips_distance_workspace_bytes(int T, int64_t P);
@@ -383,8 +442,9 @@ int64_t hv_lpips_distance_workspace_bytes(int T, int64_t P);
  * 16-byte aligned, twiddle_floats >= Tpad * 64 * ncol: column 64 j + c holds cos (c < 32) or sin (c >= 32) of 2 pi ((k t) mod T) / T for
  * bin k = 1 + 32 j + (c & 31) (HV_SPECTRUM_BINS = 32 bins per column tile), zero for k > T/2 and in rows t >= T.
  * workspace: >= hv_temporal_spectrum_workspace_bytes(mode, C, T, H, W) bytes, 8-byte aligned.  T < 1, T > HV_SPECTRUM_MAX_T, C != 3 in
- * mode 0, H or W outside [1, 65536], negative or overlapping strides are HV_ERR_ARG (the workspace query returns 0 for the shapes among
- * them). */
+ * mode 0, H or W outside [1, 65536], negative or overlapping strides (sh < W) are HV_ERR_ARG (the workspace query returns 0 for the
+ * shapes among them), as are C outside [1, 65536], H * W above 2^31 - 1, mode, dtype or rescale other than 0 | 1, a weight above 2^22 and
+ * buffers that are too small. */
 #define HV_SPECTRUM_MAX_T 1024
 #define HV_SPECTRUM_BK 32
 #define HV_SPECTRUM_BINS 32
@@ -406,7 +466,8 @@ int64_t hv_temporal_spectrum_workspace_bytes(int mode, int C, int T, int H, int 
  * (RW - 224) / 2), (v - 0.5) * 2.  y: [T][224][224][4] fp32, channel 3 = 0 (the first conv reads 4-channel voxels), 16-byte aligned.  RH, RW
  * come from the caller (fvd.py:32-36: the shorter side 224, the other ceil(side * (224 / min(H, W))) in the host's double arithmetic);
  * HV_ERR_ARG unless the shorter side's is 224 and the other's >= 224 (H == W: either side, since that double arithmetic gives 225 x 224 for
- * some sizes, e.g. 200 x 200).  The 8-bit frames never reach memory. */
+ * some sizes, e.g. 200 x 200).  The 8-bit frames never reach memory.  T, H, W in [1, 65536], RH, RW <= 2^20, dtype and rescale 0 | 1,
+ * x_sh >= W, no negative stride. */
 int hv_i3d_preprocess(const void* x, int64_t x_sc, int64_t x_st, int64_t x_sh, int dtype, int T, int H, int W, int RH, int RW, int rescale,
                       float* y, hipStream_t stream);
 
@@ -417,7 +478,8 @@ int hv_i3d_preprocess(const void* x, int64_t x_sc, int64_t x_st, int64_t x_sh, i
  * "same" rule of :81-83).  Kernel extents 1 | 3 | 7 and strides 1 | 2 per axis; pad_*: cells of zero padding in FRONT of each axis (< the
  * kernel extent; the caller applies compute_pad :71-75 and :88-93), cells behind the input read as zero too.  w: k-major [Kpad][Cout],
  * k = ((dt * kh + dh) * kw + dw) * Cin + ci, Kpad = K rounded up to 32 with zero rows, 16-byte aligned.  Cin % 4 == 0 and Cout % 4 == 0,
- * both in [4, 4096] (the first layer reads the 4-channel output of hv_i3d_preprocess); ldx % 4 == 0, x 16-byte aligned. */
+ * both in [4, 4096] (the first layer reads the 4-channel output of hv_i3d_preprocess); ldx % 4 == 0, x 16-byte aligned.  T, H, W in
+ * [1, 65536] with T*H*W <= 2^31 - 1; relu 0 | 1; ldy >= Cout also for a single output voxel. */
 int hv_i3d_conv3d_f32(const float* x, int64_t ldx, const float* w, const float* sc, const float* sh, float* y, int64_t ldy, int T, int H,
                       int W, int Cin, int Cout, int kt, int kh, int kw, int stride_t, int stride_h, int stride_w, int pad_t, int pad_h,
                       int pad_w, int relu, hipStream_t stream);
@@ -425,14 +487,15 @@ int hv_i3d_conv3d_f32(const float* x, int64_t ldx, const float* w, const float* 
 /* MaxPool3dSamePadding (pytorch_i3d.py:7-34: F.pad with zeros, then MaxPool3d): kernel extents 1..3, strides 1 | 2 per axis, pad_* cells in
  * front (< the kernel extent), output extents ceil(extent / stride).  A window cell outside the input holds 0 AND TAKES PART in the
  * maximum: a border window over all-negative inputs gives 0.  A NaN cell makes its windows NaN, as
- * torch's max_pool3d does.  C % 4 == 0; ldx, ldy % 4 == 0; x, y 16-byte aligned. */
+ * torch's max_pool3d does.  C % 4 == 0, 4 <= C <= 4096; ldx, ldy % 4 == 0 and >= C; x, y 16-byte aligned; T, H, W as hv_i3d_conv3d_f32. */
 int hv_i3d_maxpool3d_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int T, int H, int W, int C, int kt, int kh, int kw,
                          int stride_t, int stride_h, int stride_w, int pad_t, int pad_h, int pad_w, hipStream_t stream);
 
 /* The tail of InceptionI3d.forward (pytorch_i3d.py:276-285,310-315): AvgPool3d([2,7,7], stride 1) on x [T][7][7][1024] (row pitch ldx),
  * the 1024 -> 400 logits layer with bias (w k-major [1024][400]), the mean over the T - 1 time positions: out [400].  fp32 in a fixed
  * order: a pooled value is the sum of its 98 cells in memory order / 98, a logit one k-ordered fmaf chain, the mean summed in time order.
- * workspace: >= (T - 1) * 1024 floats, 16-byte aligned.  HV_ERR_ARG unless H == W == 7, C == 1024 and 2 <= T <= HV_I3D_HEAD_MAX_T. */
+ * workspace: >= (T - 1) * 1024 floats, 16-byte aligned.  HV_ERR_ARG unless H == W == 7, C == 1024 and 2 <= T <= HV_I3D_HEAD_MAX_T;
+ * ldx >= C and % 4, x 16-byte aligned. */
 #define HV_I3D_HEAD_MAX_T 4096
 int hv_i3d_head_f32(const float* x, int64_t ldx, const float* w, const float* bias, float* out, int T, int H, int W, int C,
                     float* workspace, int64_t workspace_floats, hipStream_t stream);
@@ -455,7 +518,8 @@ int hv_i3d_head_f32(const float* x, int64_t ldx, const float* w, const float* bi
  * out: element (c, t, y, x) of channel order R, G, B at out[c * sc + t * st + y * sh + x] (element strides, W contiguous, as
  * hv_video_metrics reads a video), dtype 0 = fp16, 1 = fp32, holding vtab[q]: the caller's 256 entries in the output dtype
  * (dataset.yuv_value_table: the bits of (float(q) / 255) * 2 - 1, for fp16 rounded once more).  All frame and output offsets are 64-bit.
- * HV_ERR_ARG, nothing launched: odd or non-positive W or H, a side above HV_YUV_MAX_SIDE, T < 1, OH or OW < 1, differing sizes without
+ * HV_ERR_ARG, nothing launched: odd or non-positive W or H, a side (W, H, OH, OW) above HV_YUV_MAX_SIDE, T < 1, OH or OW < 1, out or vtab
+ * not aligned to the output dtype, differing sizes without
  * both tables, an unknown layout or dtype, negative strides or strides under which two cells of the output share an address. */
 #define HV_YUV_I420 0
 #define HV_YUV_YV12 1
