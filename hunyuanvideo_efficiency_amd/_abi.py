@@ -33,3 +33,10 @@ if not os.path.exists(HEADER):
                         "description of the C ABI its bindings are derived from)")
 with open(HEADER) as _f:
     DECLS, MACROS = parse(_f.read())
+
+# include/hv_content.h: the content-statistics entry points (csrc/hv_content.hip), declared beside the main header, parsed the same way
+CONTENT_HEADER = os.path.join(os.path.dirname(HEADER), "hv_content.h")
+if not os.path.exists(CONTENT_HEADER):
+    raise HVKernelError(f"{CONTENT_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
+with open(CONTENT_HEADER) as _f:
+    CONTENT_DECLS, CONTENT_MACROS = parse(_f.read())

@@ -1,5 +1,5 @@
-"""PSNR / SSIM / LPIPS of a reconstruction against its input, temporal spectra and FVD, on the device (csrc/hv_metrics.hip, hv_lpips.hip,
-hv_spectrum.hip, hv_i3d.hip).
+"""PSNR / SSIM / LPIPS of a reconstruction against its input, temporal spectra, FVD and content statistics, on the device
+(csrc/hv_metrics.hip, hv_lpips.hip, hv_spectrum.hip, hv_i3d.hip, hv_content.hip).
 
 The fork's study scores reconstructions with evaluation/compute_metrics.py: per frame `compute_psnr` / `compute_ssim` (skimage) on
 the 8-bit frames of an mp4 that `save_videos_grid(..., rescale=True)` wrote, averaged over all frames of an experiment.  Here the
@@ -16,6 +16,8 @@ Temporal spectra (`temporal_spectrum`, `spectrum_report`; csrc/hv_spectrum.hip) 
 FVD (`I3D`, `fvd_logits`, `frechet_distance`; csrc/hv_i3d.hip) is the `method='videogpt'` path of the fork's calculate_fvd: Inception-I3D
 logits of every input clip and every reconstruction as fp32-MFMA 3-D convolutions, then the Frechet distance on the host.  Its weights are
 user-supplied too.  The value is "FVD (videogpt I3D logits)", not interchangeable with the styleganv variant (a TorchScript archive).
+Content statistics (`content_histograms`, `content_entropy`, `content_bucket`; csrc/hv_content.hip) give the measure behind the fork's
+InterEntropy bucket lists - the entropy of the gray frame-difference histogram, a definition of this project's own.
 What it is not: there is no video codec in between (the reference's frames went through libx264).  CPU tensors are refused like
 everywhere else in the package."""
 from __future__ import annotations
@@ -838,6 +840,183 @@ def add_high_band_shares(spectra: dict) -> dict:
 def spectrum_json(report: dict) -> dict:
     """a `spectrum_report` of ONE video as plain lists and floats (the <name>_spectrum.json of infer.py --spectrum)"""
     return {name: {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in d.items()} for name, d in report.items()}
+
+
+# ---- content statistics and buckets (csrc/hv_content.hip) -------------------------------------------------------------------------------
+# The last stage of the fork's study, run_experiments_buckets.sh, runs every configuration once per content bucket; the buckets are lists
+# named after a measure and its edges (metric_buckets/InterEntropy_buckets/Very_Low_InterEntropy_lt2.txt, Low_InterEntropy_2-4.txt,
+# Medium_InterEntropy_4-6.txt).  The fork does not contain the program that computed the measure, so the definition below is this
+# project's own and every record that carries a value says so.
+CONTENT_DEFINITION = ("entropy of the 8-bit gray frame difference histogram, bits; this project's definition, the fork publishes only "
+                      "the bucket names")
+CONTENT_INTER_BINS, CONTENT_CHUNK = _abi.CONTENT_MACROS["HV_CONTENT_INTER_BINS"], _abi.CONTENT_MACROS["HV_CONTENT_CHUNK"]
+CONTENT_EDGES = (2.0, 4.0, 6.0)
+# (label = the fork's file stem, lower edge, upper edge): half-open [lo, hi); the fork's three, then everything above its last edge
+CONTENT_BUCKETS = (("Very_Low_InterEntropy_lt2", None, 2.0), ("Low_InterEntropy_2-4", 2.0, 4.0), ("Medium_InterEntropy_4-6", 4.0, 6.0),
+                   ("High_InterEntropy_gt6", 6.0, None))
+
+
+def _edge_text(v) -> str:
+    return f"{float(v):g}"
+
+
+def content_bucket_labels(edges=CONTENT_EDGES, metric: str = "inter"):
+    """the bucket labels for `edges` (ascending), lowest first: the fork's names for its own edges (2, 4, 6), the same pattern for others:
+    Very_Low / Low / Medium / High for four buckets, B<i> otherwise; `metric` "inter" | "intra" names the measure"""
+    edges = [float(e) for e in edges]
+    if not edges or any(b <= a for a, b in zip(edges, edges[1:])):
+        raise ValueError(f"bucket edges must be ascending and not empty, got {edges}")
+    if metric not in ("inter", "intra"):
+        raise ValueError(f"metric is 'inter' or 'intra', got {metric!r}")
+    word = "InterEntropy" if metric == "inter" else "IntraEntropy"
+    n = len(edges) + 1
+    ranks = ("Very_Low", "Low", "Medium", "High") if n == 4 else tuple(f"B{i}" for i in range(n))
+    out = []
+    for i in range(n):
+        span = f"lt{_edge_text(edges[0])}" if i == 0 else f"gt{_edge_text(edges[-1])}" if i == n - 1 else \
+            f"{_edge_text(edges[i - 1])}-{_edge_text(edges[i])}"
+        out.append(f"{ranks[i]}_{word}_{span}")
+    return out
+
+
+def content_bucket(value, edges=CONTENT_EDGES, metric: str = "inter"):
+    """The label of the bucket `value` falls in, half-open intervals [lo, hi): the fork's `lt2` is strictly below 2, exactly 2.0 is
+    `Low_InterEntropy_2-4`.  None (a single-frame clip has no inter-frame entropy) and NaN belong to no bucket: None."""
+    labels = content_bucket_labels(edges, metric)
+    if value is None or value != value:
+        return None
+    i = 0
+    for e in edges:
+        if float(value) >= float(e):
+            i += 1
+    return labels[i]
+
+
+def _content_check(x, luma):
+    _check_video(x, "x")
+    if x.shape[-4] != 3:
+        raise _lib.HVKernelError(f"content histograms read RGB videos, got C = {x.shape[-4]}")
+    if len(tuple(luma)) != 5:
+        raise _lib.HVKernelError(f"luma is (wr, wg, wb, round, shift), got {luma!r}")
+
+
+def content_histograms(x: torch.Tensor, rescale: bool = True, luma=GRAY_LUMA):
+    """Histograms of the 8-bit gray frames of `x` ([3,T,H,W] or [B,3,T,H,W]; GPU tensors only, fp16 or fp32, W contiguous, strided views
+    allowed; gray as in `temporal_spectrum`'s gray mode) and of the differences of consecutive gray frames, left on the device:
+    `intra` int32 [T, 256] - pixels of frame t with gray value g - and `inter` int32 [T - 1, 511] - pixels with gray[t + 1] - gray[t] ==
+    d in column d + 255 ([B, ...] for a batch).  Counts are exact (at most H W <= 2^31 - 1).  Nothing is synchronised."""
+    _content_check(x, luma)
+    batched = x.dim() == 5
+    if not batched:
+        x = x[None]
+    B, _, T, H, W = x.shape
+    ws_bytes = _lib.host("content_histograms_workspace_bytes", T, H, W)
+    if ws_bytes <= 0:
+        raise _lib.HVKernelError(f"content histograms: unsupported shape {tuple(x.shape)}")
+    dev = x.device
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    intra = torch.empty(B, T, 256, dtype=torch.int32, device=dev)
+    inter = torch.empty(B, T - 1, CONTENT_INTER_BINS, dtype=torch.int32, device=dev)
+    wr, wg, wb, rnd, shift = (int(v) for v in luma)
+    for b in range(B):                        # one stream: video b + 1 reuses the workspace after video b's fold
+        v = x[b]
+        _lib.call("content_histograms", v, v.stride(0), v.stride(1), v.stride(2), _DTYPES[x.dtype], T, H, W, 1 if rescale else 0,
+                  wr, wg, wb, rnd, shift, intra[b], inter[b] if T > 1 else None, ws, ws.numel())
+    return (intra, inter) if batched else (intra[0], inter[0])
+
+
+def histogram_entropy(counts: torch.Tensor, origin: int = 0) -> torch.Tensor:
+    """float64 [rows, 3] on the device: (entropy in bits, sum c v, sum c v^2) of every row of `counts` (int32 [rows, bins <= 1024], GPU,
+    contiguous), bin b standing for the value b - origin.  Nothing is synchronised."""
+    if not isinstance(counts, torch.Tensor) or not counts.is_cuda:
+        raise _lib.HVKernelError("histogram_entropy: expected a GPU tensor (this package has no CPU path)")
+    if counts.dtype != torch.int32 or counts.dim() != 2 or not counts.is_contiguous():
+        raise _lib.HVKernelError(f"histogram_entropy: counts are contiguous int32 [rows, bins], got {counts.dtype} {tuple(counts.shape)}")
+    rows, bins = counts.shape
+    out = torch.empty(rows, 3, dtype=torch.float64, device=counts.device)
+    if rows:
+        _lib.call("histogram_entropy", counts, rows, bins, int(origin), out)
+    return out
+
+
+def _content_enqueue(x: torch.Tensor, rescale: bool = True, luma=GRAY_LUMA):
+    """histograms and their entropies of ONE clip ([3,T,H,W] or [1,3,T,H,W]), everything enqueued, nothing synchronised: a job for
+    `_content_to_host`"""
+    _content_check(x, luma)
+    if x.dim() == 5:
+        if x.shape[0] != 1:
+            raise _lib.HVKernelError(f"content entropy takes one clip at a time, got a batch of {x.shape[0]}")
+        x = x[0]
+    intra, inter = content_histograms(x, rescale, luma)
+    return (histogram_entropy(intra, 0), histogram_entropy(inter, 255), inter, x.shape[-3], x.shape[-2] * x.shape[-1])
+
+
+def content_from_host(intra_stats, inter_stats, inter_counts, frames: int, pixels: int) -> dict:
+    """The host rules on the finaliser's rows (numpy float64; pure, also used on CPU by the tests): intra_stats [T, 3], inter_stats
+    [T - 1, 3] = (entropy, sum c v, sum c v^2) per row, inter_counts [T - 1, 511]."""
+    intra_stats = np.asarray(intra_stats, dtype=np.float64).reshape(-1, 3)
+    inter_stats = np.asarray(inter_stats, dtype=np.float64).reshape(-1, 3)
+    inter_counts = np.asarray(inter_counts, dtype=np.int64).reshape(-1, CONTENT_INTER_BINS)
+    n = float(pixels)
+    d = {"inter_entropy": None, "intra_entropy": float(intra_stats[:, 0].mean()), "intra_entropy_frames": intra_stats[:, 0].tolist(),
+         "inter_entropy_pairs": inter_stats[:, 0].tolist(), "mean_abs_diff": None, "ti": None, "frames": int(frames),
+         "definition": CONTENT_DEFINITION}
+    if inter_stats.shape[0]:
+        d["inter_entropy"] = float(inter_stats[:, 0].mean())
+        absv = np.abs(np.arange(CONTENT_INTER_BINS, dtype=np.int64) - 255)
+        d["mean_abs_diff"] = float(((inter_counts * absv[None, :]).sum(axis=1) / n).mean())
+        # ITU-T P.910 temporal information: max over time of the spatial standard deviation of the difference; the moments are exact
+        # integers (below 2^53 as doubles), so the variance (N S2 - S1^2) / N^2 is formed in python integers and rounded once
+        var = [(int(pixels) * int(s2) - int(s1) * int(s1)) / float(int(pixels) ** 2) for _, s1, s2 in inter_stats]
+        d["ti"] = math.sqrt(max(var))
+    return d
+
+
+def _content_to_host(jobs):
+    """jobs of `_content_enqueue` on one device -> one synchronisation, then `content_from_host` per job"""
+    host = []
+    for job in jobs:
+        trio = []
+        for t in job[:3]:
+            h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+            h.copy_(t, non_blocking=True)
+            trio.append(h)
+        host.append(trio)
+    torch.cuda.current_stream(jobs[0][0].device).synchronize()
+    return [content_from_host(hi.numpy(), hp.numpy(), hc.numpy(), job[3], job[4]) for job, (hi, hp, hc) in zip(jobs, host)]
+
+
+def content_entropy(x: torch.Tensor, rescale: bool = True, luma=GRAY_LUMA) -> dict:
+    """Content statistics of one clip ([3,T,H,W] or [1,3,T,H,W], as `content_histograms`): `inter_entropy` - the mean over the T - 1 frame
+    pairs of the Shannon entropy, in bits, of the histogram of gray[t + 1] - gray[t] (None for T = 1: such a clip is not bucketed) -,
+    `intra_entropy` - the mean over frames of the entropy of the gray histogram -, the per-pair and per-frame lists
+    (`inter_entropy_pairs`, `intra_entropy_frames`), `mean_abs_diff` (mean |difference| in gray levels, mean over pairs), `ti` (ITU-T
+    P.910 temporal information: the maximum over pairs of the standard deviation of the difference, from exact integer moments),
+    `frames`, and `definition` (CONTENT_DEFINITION: the measure is this project's own).  One host synchronisation."""
+    return _content_to_host([_content_enqueue(x, rescale, luma)])[0]
+
+
+def content_entropy_many(clips, rescale: bool = True, luma=GRAY_LUMA) -> list:
+    """`content_entropy` of every clip of an iterable (a generator may load and drop one clip at a time: only the histograms of a clip
+    outlive its launches), everything enqueued first: one host synchronisation for all of them"""
+    jobs = [_content_enqueue(x, rescale, luma) for x in clips]
+    return _content_to_host(jobs) if jobs else []
+
+
+_CONTENT_MEANS = ("inter_entropy", "intra_entropy", "mean_abs_diff", "ti")
+
+
+def content_summary(inputs: list, recons: list) -> dict:
+    """The `content` entry of a driver's record: the fields of `content_entropy` averaged over the clips that have them, for the inputs
+    and for their reconstructions, and `inter_entropy_drop` = input - reconstruction: the frame-to-frame detail a pool or stride removed"""
+    def mean(ds, k):
+        v = [d[k] for d in ds if d[k] is not None]
+        return sum(v) / len(v) if v else None
+    out = {"input": {k: mean(inputs, k) for k in _CONTENT_MEANS}, "reconstruction": {k: mean(recons, k) for k in _CONTENT_MEANS},
+           "clips": len(inputs), "definition": CONTENT_DEFINITION}
+    a, b = out["input"]["inter_entropy"], out["reconstruction"]["inter_entropy"]
+    out["inter_entropy_drop"] = None if a is None or b is None else a - b
+    return out
 
 
 def add_lpips_arguments(parser, synthetic: bool = False):

@@ -29,7 +29,8 @@ class VideoTensorDataset:
         return torch.load(path, map_location="cpu", weights_only=True), self.tensor_files[idx]
 
 
-def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, scorer=None, save=True, spectrum_dir=None, fps=None):
+def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, scorer=None, save=True, spectrum_dir=None, fps=None,
+              content_dir=None):
     """Reconstructs the first `max_files` tensors, `batch_size` at a time (tensors of one batch must have equal shapes, as a
     DataLoader's default collate requires); every input still gets its own <name>.pt of shape [1, C, T, H, W].
     `scorer` (a metrics.MetricsAccumulator): each reconstruction is scored against its input while both are on the device
@@ -37,7 +38,9 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
     keeps both clips' logits for the FVD of the whole run).  save=False skips the copy to the host and the .pt files.
     `spectrum_dir`: also write <name>_spectrum.json there per input - the temporal spectra (metrics.spectrum_report; the fork's
     theory_analysis.ipynb) of the input, of the posterior mean the forward already returns and of the reconstruction, with `freq` axes
-    when `fps` is given."""
+    when `fps` is given.  `content_dir`: also write <name>_content.json there per input - {"input", "reconstruction"}, each the dict
+    of metrics.content_entropy (inter- / intra-frame entropy of the 8-bit gray frames, this project's definition): comparing the two
+    `inter_entropy` values shows how much frame-to-frame detail the configuration removed."""
     if batch_size < 1:
         raise ValueError(f"--batch-size must be >= 1, got {batch_size}")
     os.makedirs(output_dir, exist_ok=True)
@@ -45,6 +48,9 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
     if spectrum_dir is not None:
         from hunyuanvideo_efficiency_amd.metrics import spectrum_json, spectrum_report
         os.makedirs(spectrum_dir, exist_ok=True)
+    if content_dir is not None:
+        from hunyuanvideo_efficiency_amd.metrics import content_entropy_many
+        os.makedirs(content_dir, exist_ok=True)
     file_fps = getattr(dataset, "fps", {})       # a YuvClipDataset knows each file's frame rate from its name
     n = len(dataset) if max_files is None else min(len(dataset), max_files)
     done = []
@@ -68,6 +74,16 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
                 print(f"Spectrum {name}: high-band share input {rep['input']['high_band_share']:.4f} latent "
                       f"{rep['latent']['high_band_share']:.4f} reconstruction {rep['reconstruction']['high_band_share']:.4f} "
                       f"(cutoff bin {rep['input']['cutoff_bin']} of {video.shape[2]} frames)")
+        if content_dir is not None:
+            stats = content_entropy_many([video[b] for b in range(len(names))] + [recon[b] for b in range(len(names))])
+            for b, name in enumerate(names):
+                c = {"input": stats[b], "reconstruction": stats[len(names) + b]}
+                with open(os.path.join(content_dir, f"{name}_content.json"), "w") as f:
+                    json.dump(c, f)
+                fmt = lambda v: "n/a" if v is None else f"{v:.4f}"      # noqa: E731  (a single frame has no inter-frame entropy)
+                print(f"Content {name}: inter-frame entropy input {fmt(c['input']['inter_entropy'])} reconstruction "
+                      f"{fmt(c['reconstruction']['inter_entropy'])} bits, intra-frame {fmt(c['input']['intra_entropy'])} / "
+                      f"{fmt(c['reconstruction']['intra_entropy'])} (this project's definition)")
         if scorer is not None:
             m = scorer.add_video(video, recon, rescale=True)
             for b, name in enumerate(names):
@@ -111,12 +127,16 @@ def parse_args(argv=None):
                                                           "temporal spectra of input, latent and reconstruction and their high-band shares")
     p.add_argument("--fps", type=float, default=None, help="with --spectrum: frame rate of the clips, adds the frequency axes "
                                                            "(default with --yuv-format: the rate in each file's name)")
+    p.add_argument("--content", action="store_true", help="with --score: write <name>_content.json per clip into the results directory - "
+                                                         "inter- / intra-frame entropy of input and reconstruction (this project's definition)")
     from hunyuanvideo_efficiency_amd.dataset import add_yuv_arguments, check_yuv_arguments
     add_yuv_arguments(p)                 # --yuv-format {I420,NV12,YV12} [--target-height N] [--start-frame A] [--end-frame B]
     a = p.parse_args(argv)
     check_yuv_arguments(a, p)
     if a.spectrum and not a.score:
         p.error("--spectrum is only valid with --score")
+    if a.content and not a.score:
+        p.error("--content is only valid with --score")
     if a.fps is not None and not a.spectrum:
         p.error("--fps is only valid with --spectrum")
     if a.fps is not None and not a.fps > 0:
@@ -163,7 +183,7 @@ def main(argv=None):
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator, fvd_from_args, lpips_from_args
     scorer = MetricsAccumulator(lpips=lpips_from_args(a), fvd=fvd_from_args(a, score=a.score))
     done = infer_vae(vae, dataset, device, a.output_dir, a.max_files, a.batch_size, scorer, not a.no_save,
-                     (a.results_dir or a.output_dir) if a.spectrum else None, a.fps)
+                     (a.results_dir or a.output_dir) if a.spectrum else None, a.fps, (a.results_dir or a.output_dir) if a.content else None)
     results = scorer.result()
     print(f"Results over {scorer.frames} frames: {results}" + (" (LPIPS under synthetic weights: not comparable with published LPIPS)"
                                                                if a.lpips_synthetic else "") + scorer.fvd_note())

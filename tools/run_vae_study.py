@@ -16,7 +16,15 @@ fork's shell drivers' background batches over several cards are not reproduced.
                                         styleganv variant; the inputs' logits are computed once for all configurations
   ... --yuv-format I420 [--target-height 240] [--start-frame A] [--end-frame B]   --tensor-dir is a folder of raw planar YUV 4:2:0 files
                                         (<name>_<n>fps_<w>x<h>.yuv), converted on the GPU once for all configurations and kept on the
-                                        device; with --spectrum and no --fps each file name's frame rate gives the frequency axes"""
+                                        device; with --spectrum and no --fps each file name's frame rate gives the frequency axes
+  ... --content                         each record gains "content": inter- / intra-frame entropy, mean |difference| and TI of the inputs
+                                        and of the reconstructions (metrics.content_entropy, this project's definition) and
+                                        "inter_entropy_drop", the frame-to-frame detail the configuration removed; the inputs' values
+                                        are computed once for all configurations
+  ... --bucket-dir B                    the fork's run_experiments_buckets.sh: the sweep runs once per <bucket>.txt list of folder B
+                                        (tools/bucket_clips.py writes them), on the clips of --tensor-dir whose file stems the list
+                                        names; records go to <output-dir>/<bucket>/study.jsonl and carry "bucket".  A list that names a
+                                        clip absent from --tensor-dir is an error"""
 import argparse
 import json
 import os
@@ -43,12 +51,14 @@ def build_vae(config_json, vae_path, reduced, device):
 
 
 def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, lpips=None, spectra=None, fps=None, fvd=None,
-               input_logits=None):
+               input_logits=None, input_content=None):
     """-> the study.jsonl record of one configuration.  `fvd` (an I3D, --fvd-i3d / --fvd-synthetic): the record gains "fvd" - FVD
     (videogpt I3D logits) between the inputs and this configuration's reconstructions, None below two clips - and "fvd_clips";
     `input_logits` (a dict the caller keeps across configurations) holds every input clip's logits, which do not depend on the
     configuration: they are computed once.  `spectra` (a dict, --spectrum): temporal spectra are taken too - the record gains
-    "spectrum" and the dict is filled with the configuration's mean spectra (`mean_spectra`)"""
+    "spectrum" and the dict is filled with the configuration's mean spectra (`mean_spectra`).  `input_content` (a dict the caller keeps
+    across configurations, --content): the record gains "content" (metrics.content_summary); the dict holds every input clip's
+    statistics, computed once"""
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator
     rec = {"config": os.path.basename(config_json)}
     try:
@@ -57,6 +67,7 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
         input_logits = {} if input_logits is None else input_logits
         t_in = t_lat = 0
         reports = []
+        content_jobs = []                               # (clip index or None for a reconstruction, enqueued job): one synchronisation below
         n = len(dataset) if max_files is None else min(len(dataset), max_files)
         for idx in range(n):
             video, file_name = dataset[idx]
@@ -71,6 +82,11 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
             if spectra is not None:
                 from hunyuanvideo_efficiency_amd.metrics import spectrum_report
                 reports.append(spectrum_report(video[0], z[0], recon[0], fps=clip_fps))
+            if input_content is not None:
+                from hunyuanvideo_efficiency_amd import metrics
+                if idx not in input_content:
+                    content_jobs.append((idx, metrics._content_enqueue(video[0])))
+                content_jobs.append((None, metrics._content_enqueue(recon[0])))
             t_in += video.shape[2]
             t_lat += z.shape[2]
         res = acc.result()
@@ -83,6 +99,11 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
             rec["lpips_weights"] = "synthetic"          # not comparable with published LPIPS
         rec["frames"] = acc.frames
         rec["compression"] = t_lat / t_in if t_in else None
+        if input_content is not None:
+            from hunyuanvideo_efficiency_amd import metrics
+            stats = metrics._content_to_host([j for _, j in content_jobs]) if content_jobs else []
+            input_content.update({i: d for (i, _), d in zip(content_jobs, stats) if i is not None})
+            rec["content"] = metrics.content_summary([input_content[i] for i in range(n)], [d for (i, _), d in zip(content_jobs, stats) if i is None])
         if spectra is not None:
             rec["spectrum"] = {f"{name}_high_band_share": (sum(r[name]["high_band_share"] for r in reports) / len(reports) if reports else None)
                                for name in ("input", "latent", "reconstruction")}
@@ -119,6 +140,7 @@ class ConvertedOnce:
 
     def __init__(self, dataset):
         self.dataset, self.fps, self._items = dataset, dataset.fps, {}
+        self.tensor_files = dataset.tensor_files
 
     def __len__(self):
         return len(self.dataset)
@@ -127,6 +149,48 @@ class ConvertedOnce:
         if idx not in self._items:
             self._items[idx] = self.dataset[idx]
         return self._items[idx]
+
+
+class ClipSubset:
+    """the clips `indices` of a dataset, under the dataset's surface (len, [i] -> (clip, file name), tensor_files, fps)"""
+
+    def __init__(self, dataset, indices):
+        self.dataset, self.indices = dataset, list(indices)
+        self.tensor_files = [dataset.tensor_files[i] for i in self.indices]
+        if hasattr(dataset, "fps"):
+            self.fps = dataset.fps
+
+    def __len__(self):
+        return len(self.indices)
+
+    def __getitem__(self, idx):
+        return self.dataset[self.indices[idx]]
+
+
+def read_bucket_lists(bucket_dir, tensor_files):
+    """The <bucket>.txt lists of `bucket_dir`, sorted by name -> [(bucket, [index into tensor_files, ...])].  A line names a clip by path
+    or file name; it is matched by file stem (the fork's script maps x.mp4 to x.pt).  ValueError for a folder without lists, an empty
+    list, and a list that names a clip `tensor_files` does not hold: such a clip is not skipped."""
+    from hunyuanvideo_efficiency_amd.dataset import clip_stem
+    by_stem = {clip_stem(f): i for i, f in enumerate(tensor_files)}
+    names = sorted(f for f in os.listdir(bucket_dir) if f.endswith(".txt"))
+    if not names:
+        raise ValueError(f"--bucket-dir {bucket_dir} holds no <bucket>.txt list")
+    out = []
+    for name in names:
+        with open(os.path.join(bucket_dir, name)) as f:
+            lines = [ln.strip() for ln in f if ln.strip()]
+        if not lines:
+            raise ValueError(f"bucket list {name} is empty")
+        idx = []
+        for ln in lines:
+            stem = os.path.splitext(os.path.basename(ln))[0]
+            if stem not in by_stem:
+                raise ValueError(f"bucket list {name} names {ln!r}, but the tensor folder has no clip with the stem {stem!r}")
+            if by_stem[stem] not in idx:
+                idx.append(by_stem[stem])
+        out.append((name[:-len(".txt")], idx))
+    return out
 
 
 def _exp_order(name):
@@ -148,6 +212,11 @@ def parse_args(argv=None):
     p.add_argument("--spectrum", action="store_true", help="temporal spectra of input, latent and reconstruction: each record gains "
                    "\"spectrum\" (three high-band shares, averaged over clips), each configuration a spectra_<config>.json")
     p.add_argument("--fps", type=float, default=None, help="with --spectrum: frame rate of the clips, adds the frequency axes")
+    p.add_argument("--content", action="store_true", help="content statistics of inputs and reconstructions: each record gains \"content\" "
+                   "(inter- / intra-frame entropy, this project's definition, mean |difference|, TI, and the inter-frame entropy the "
+                   "configuration removed)")
+    p.add_argument("--bucket-dir", default=None, help="run the sweep once per <bucket>.txt list of this folder (tools/bucket_clips.py), "
+                   "under <output-dir>/<bucket>/; records carry \"bucket\"")
     from hunyuanvideo_efficiency_amd.metrics import add_fvd_arguments, add_lpips_arguments
     add_lpips_arguments(p, synthetic=True)
     add_fvd_arguments(p)
@@ -165,6 +234,8 @@ def parse_args(argv=None):
         p.error("--lpips-synthetic and --lpips-alexnet exclude each other")
     if a.fvd_i3d and a.fvd_synthetic:
         p.error("--fvd-synthetic and --fvd-i3d exclude each other")
+    if a.bucket_dir is not None and not os.path.isdir(a.bucket_dir):
+        p.error(f"--bucket-dir {a.bucket_dir} is not a folder")
     return a
 
 
@@ -187,13 +258,29 @@ def main(argv=None):
         dataset = ConvertedOnce(dataset_from_args(a, "cuda"))
     else:
         dataset = VideoTensorDataset(a.tensor_dir)
-    out =os.path.join(a.output_dir, "study.jsonl")
+    if a.bucket_dir is None:
+        return run_sweep(a, configs, dataset, a.output_dir, lpips, fvd, input_logits, {} if a.content else None)
+    records = []
+    for bucket, indices in read_bucket_lists(a.bucket_dir, dataset.tensor_files):
+        print(f"bucket {bucket}: {len(indices)} clips")
+        sub_dir = os.path.join(a.output_dir, bucket)
+        os.makedirs(sub_dir, exist_ok=True)
+        # the caches are keyed by the position in the subset: one pair per bucket
+        records += run_sweep(a, configs, ClipSubset(dataset, indices), sub_dir, lpips, fvd, {}, {} if a.content else None, bucket)
+    return records
+
+
+def run_sweep(a, configs, dataset, output_dir, lpips, fvd, input_logits, input_content, bucket=None):
+    """every configuration on `dataset` -> <output_dir>/study.jsonl; `bucket`: the label every record carries"""
+    out =os.path.join(output_dir, "study.jsonl")
     records = []
     for cfg in configs:
         spectra = {} if a.spectrum else None
-        rec = run_config(cfg, dataset, a.vae_path, a.reduced, "cuda", a.max_files, lpips, spectra, a.fps, fvd, input_logits)
+        rec = run_config(cfg, dataset, a.vae_path, a.reduced, "cuda", a.max_files, lpips, spectra, a.fps, fvd, input_logits, input_content)
+        if bucket is not None:
+            rec["bucket"] = bucket
         if spectra:
-            with open(os.path.join(a.output_dir, f"spectra_{os.path.splitext(os.path.basename(cfg))[0]}.json"), "w") as f:
+            with open(os.path.join(output_dir, f"spectra_{os.path.splitext(os.path.basename(cfg))[0]}.json"), "w") as f:
                 json.dump(spectra, f)
         records.append(rec)
         with open(out, "a") as f:
