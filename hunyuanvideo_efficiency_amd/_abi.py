@@ -40,3 +40,10 @@ if not os.path.exists(CONTENT_HEADER):
     raise HVKernelError(f"{CONTENT_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
 with open(CONTENT_HEADER) as _f:
     CONTENT_DECLS, CONTENT_MACROS = parse(_f.read())
+
+# include/hv_temporal.h: the linear temporal interpolation (csrc/hv_temporal.hip), declared and parsed the same way
+TEMPORAL_HEADER = os.path.join(os.path.dirname(HEADER), "hv_temporal.h")
+if not os.path.exists(TEMPORAL_HEADER):
+    raise HVKernelError(f"{TEMPORAL_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
+with open(TEMPORAL_HEADER) as _f:
+    TEMPORAL_DECLS, TEMPORAL_MACROS = parse(_f.read())

@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from .. import synthetic as syn
 from .. import vae_ops as V
-from .tiling import AxisPlan, TilePlan
+from .tiling import AxisPlan, TilePlan, decoded_frames, spatial_stride_overrides
 
 F16 = torch.float16
 
@@ -347,11 +347,10 @@ class AutoencoderKLCausal3D(nn.Module):
             if len(eib) != n_res or len(eia) != n_res:
                 raise ValueError(f"[UpDecoderBlockCausal3D] config mismatch: expecting {n_res} bools in each list.")
             sc = int(bc.get("interp_t_scale_factor", 2))
-            if (any(eib) or any(eia)) and bc.get("interp_mode", "nearest") != "nearest":
-                raise NotImplementedError("t_ops interp_mode: only 'nearest' has a kernel (the fork's config default)")
+            t_up = self._interp_op(bc.get("interp_mode", "nearest")) if (any(eib) or any(eia)) else None
             for j in range(n_res):
                 if eib[j]:
-                    h, T = V.temporal_nearest_up(h, T, H * W, sc)      # unet_causal_3d_blocks.py:884-895
+                    h, T = t_up(h, T, H * W, sc)      # unet_causal_3d_blocks.py:884-895
                     st = None
                 # the tensor this resnet returns is normalised next (the following resnet's norm1, or conv_norm_out after the last
                 # block) unless an upsampler or a t_ops interpolation comes in between: then its conv2 takes the statistics
@@ -359,7 +358,7 @@ class AutoencoderKLCausal3D(nn.Module):
                 h = self._resnet(P, f"{pre}up_blocks.{i}.resnets.{j}.", h, T, H, W, x_stats=st, out_stats=feeds_gn)
                 h, st = h if feeds_gn else (h, None)
                 if eia[j]:
-                    h, T = V.temporal_nearest_up(h, T, H * W, sc)
+                    h, T = t_up(h, T, H * W, sc)
             if sp or tm:
                 T2, H2, W2 = (1 + 2 * (T - 1) if tm else T), (2 * H if sp else H), (2 * W if sp else W)
                 name = f"{pre}up_blocks.{i}.upsamplers.0.conv.conv"
@@ -388,6 +387,18 @@ class AutoencoderKLCausal3D(nn.Module):
         log2(8) = 3 spatial layers from the front, log2(4) = 2 temporal ones before the last block."""
         nb = len(self.config.block_out_channels)
         return [(i < 3, (i >= nb - 1 - 2) and (i != nb - 1)) for i in range(nb)]
+
+    @staticmethod
+    def _interp_op(mode):
+        """The kernel behind F.interpolate(h, scale_factor=(sc,1,1), mode=mode) on a 5-D h, for every mode that call accepts: with
+        integer sc "nearest-exact" and "area" give the bits of "nearest" (the same source frame / a mean over one frame), "trilinear" is
+        linear along T alone; "linear", "bilinear" and "bicubic" raise inside F.interpolate for 5-D input."""
+        if mode in ("nearest", "nearest-exact", "area"):
+            return V.temporal_nearest_up
+        if mode == "trilinear":
+            return V.temporal_linear_up
+        raise NotImplementedError(f"t_ops interp_mode {mode!r}: 'nearest', 'nearest-exact', 'area' and 'trilinear' have kernels "
+                                  "(what F.interpolate accepts for a 5-D input)")
 
     @staticmethod
     def _block_cfg(cfgs, i):
@@ -490,9 +501,20 @@ class AutoencoderKLCausal3D(nn.Module):
             return (posterior,)
         return SimpleNamespace(latent_dist=posterior, tiles_ci=None)
 
-    def _encode_moments(self, x):
-        if self._t_ops is not None and (self.use_temporal_tiling or self.use_spatial_tiling):
+    def _check_tiling_under_t_ops(self):
+        """Temporal tiling under t_ops stays refused (the blend extents assume the 4x ratio); spatial tiling never looks at T and is
+        allowed while no `downsample_stride` moves a spatial stride (the tile and blend geometry assumes the 8x ratio)."""
+        if self._t_ops is None:
+            return
+        if self.use_temporal_tiling:
             raise NotImplementedError("t_ops change the compression ratios the tile/blend geometry assumes; the fork runs them untiled")
+        if self.use_spatial_tiling:
+            for i, st in spatial_stride_overrides(self._t_ops, self._resample_schedule()):
+                raise NotImplementedError(f"t_ops encoder.down_blocks[{i}]: downsample_stride {list(st)} changes a spatial stride; spatial "
+                                          "tiling assumes the 8x spatial ratio of the schedule's own strides")
+
+    def _encode_moments(self, x):
+        self._check_tiling_under_t_ops()
         return self._assemble_temporal(self._tile_plan(decode=False), x[0], self._encode_tile, 2 * self.config.latent_channels)[None]
 
     @torch.no_grad()
@@ -577,7 +599,8 @@ class AutoencoderKLCausal3D(nn.Module):
     def _decoded_size(self, z_view) -> Tuple[int, int, int]:
         """(T', H', W') of the video a latent view [C,T,H,W] decodes to."""
         s = self.config.spatial_compression_ratio
-        return (z_view.shape[1] - 1) * self.time_compression_ratio + 1, z_view.shape[2] * s, z_view.shape[3] * s
+        frames = decoded_frames(z_view.shape[1], self._t_ops, self._resample_schedule(), self.config.layers_per_block)
+        return frames, z_view.shape[2] * s, z_view.shape[3] * s
 
     # ------------------------------------------------------------------ tile parallelism (SURVEY.md 8e; new vs the reference,
     # which decodes every tile on every rank).  Tiles are independent until the blend: each rank decodes its share, the decoded
@@ -691,8 +714,7 @@ class AutoencoderKLCausal3D(nn.Module):
         assert len(z.shape) == 5, "The input tensor should have 5 dimensions."
         assert z.shape[0] == 1, "one video per _decode call: decode() steps through a batch"
         z4 = z[0].to(torch.float32)
-        if self._t_ops is not None and (self.use_temporal_tiling or self.use_spatial_tiling):
-            raise NotImplementedError("t_ops change the compression ratios the tile/blend geometry assumes; the fork runs them untiled")
+        self._check_tiling_under_t_ops()
         tiles = None          # tiles decoded ahead of the blends (sharded over ranks, else on decode_streams streams), if any
         if self._tp_enabled:
             import torch.distributed as dist

@@ -223,6 +223,15 @@ def temporal_nearest_up(x, T: int, HW: int, s: int):
     return out, T * s
 
 
+def temporal_linear_up(x, T: int, HW: int, s: int):
+    """t_ops interp, interp_mode "trilinear": linear interpolation along T with half-pixel centres and clamped ends
+    (F.interpolate(scale_factor=(s,1,1), mode="trilinear", align_corners=False)).  x [T*HW, C] -> ([T*s*HW, C], T*s)."""
+    _chk(x, F16, "x")
+    out = torch.empty(T * s * HW, x.shape[1], dtype=F16, device=x.device)
+    _lib.call("temporal_interp_f16", x, x.stride(0), out, out.stride(0), T, HW, x.shape[1], s)
+    return out, T * s
+
+
 _gn_ws = {}
 
 

@@ -24,7 +24,10 @@ fork's shell drivers' background batches over several cards are not reproduced.
   ... --bucket-dir B                    the fork's run_experiments_buckets.sh: the sweep runs once per <bucket>.txt list of folder B
                                         (tools/bucket_clips.py writes them), on the clips of --tensor-dir whose file stems the list
                                         names; records go to <output-dir>/<bucket>/study.jsonl and carry "bucket".  A list that names a
-                                        clip absent from --tensor-dir is an error"""
+                                        clip absent from --tensor-dir is an error
+  ... --interp-mode trilinear           with --base-config: every decoder block of each enumerated configuration gets this
+                                        "interp_mode" (nearest | nearest-exact | area | trilinear) before it is written; without the
+                                        flag the configurations are written as enumerated"""
 import argparse
 import json
 import os
@@ -193,6 +196,20 @@ def read_bucket_lists(bucket_dir, tensor_files):
     return out
 
 
+INTERP_MODES = ("nearest", "nearest-exact", "area", "trilinear")       # the modes AutoencoderKLCausal3D has kernels for
+
+
+def override_interp_mode(paths, mode):
+    """--interp-mode: rewrite the configuration files `paths` with `interp_mode` = mode in every decoder block"""
+    for path in paths:
+        with open(path) as f:
+            cfg = json.load(f)
+        for bc in cfg.get("decoder", {}).get("up_blocks", []):
+            bc["interp_mode"] = mode
+        with open(path, "w") as f:
+            json.dump(cfg, f, indent=2)
+
+
 def _exp_order(name):
     m = re.search(r"(\d+)", name)
     return (int(m.group(1)) if m else 0, name)
@@ -217,6 +234,8 @@ def parse_args(argv=None):
                    "configuration removed)")
     p.add_argument("--bucket-dir", default=None, help="run the sweep once per <bucket>.txt list of this folder (tools/bucket_clips.py), "
                    "under <output-dir>/<bucket>/; records carry \"bucket\"")
+    p.add_argument("--interp-mode", default=None, choices=INTERP_MODES, help="with --base-config: the interp_mode of every decoder block "
+                   "of each enumerated configuration (default: what the base configuration says)")
     from hunyuanvideo_efficiency_amd.metrics import add_fvd_arguments, add_lpips_arguments
     add_lpips_arguments(p, synthetic=True)
     add_fvd_arguments(p)
@@ -228,6 +247,8 @@ def parse_args(argv=None):
         p.error("--fps needs --spectrum and a positive rate")
     if (a.base_config is None) == (a.config_dir is None):
         p.error("give exactly one of --base-config (enumerate) or --config-dir (ready-made configurations)")
+    if a.interp_mode is not None and a.base_config is None:
+        p.error("--interp-mode rewrites enumerated configurations: it needs --base-config")
     if a.lpips_linear and not a.lpips_alexnet:
         p.error("--lpips-linear needs --lpips-alexnet")
     if a.lpips_synthetic and a.lpips_alexnet:
@@ -250,6 +271,8 @@ def main(argv=None):
     os.makedirs(a.output_dir, exist_ok=True)
     if a.base_config:
         configs = dynamic_enumeration.write_configs(a.base_config, os.path.join(a.output_dir, f"config_{a.mode}_json"), a.mode, a.limit)
+        if a.interp_mode is not None:
+            override_interp_mode(configs, a.interp_mode)
     else:
         configs = [os.path.join(a.config_dir, f) for f in sorted((f for f in os.listdir(a.config_dir) if f.endswith(".json")), key=_exp_order)]
         configs = configs[:a.limit] if a.limit is not None else configs
