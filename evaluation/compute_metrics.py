@@ -34,8 +34,9 @@ def parse_args(argv=None):
     p.add_argument("--lpips-alexnet", type=str, default=None, help="score LPIPS too: a torchvision AlexNet state dict (needs --lpips-linear), "
                                                                    "or one full LPIPS state dict (.pt / .pth / .safetensors; weights are not shipped)")
     p.add_argument("--lpips-linear", type=str, default=None, help="the LPIPS linear layers (lin{0..4}.model.1.weight)")
-    from hunyuanvideo_efficiency_amd.metrics import add_fvd_arguments
+    from hunyuanvideo_efficiency_amd.metrics import add_fvd_arguments, add_gssim_arguments
     add_fvd_arguments(p)
+    add_gssim_arguments(p)               # --gssim, --metrics-csv PATH
     a = p.parse_args(argv)
     if a.lpips_linear and not a.lpips_alexnet:
         p.error("--lpips-linear needs --lpips-alexnet")
@@ -83,26 +84,29 @@ def read_video(path):
     return x, True
 
 
-def score_folders(root1, root2, results_dir, device="cuda", lpips=None, fvd=None):
+def score_folders(root1, root2, results_dir, device="cuda", lpips=None, fvd=None, gssim=False, metrics_csv=None):
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator
     names = pair_files(root1, root2)
     if not names:
         print(f"No matching video files between {root1} and {root2}.")
         return None
     print(f"Found {len(names)} matching pairs.")
-    acc = MetricsAccumulator(lpips=lpips, fvd=fvd)
+    acc = MetricsAccumulator(lpips=lpips, fvd=fvd, gssim=gssim, csv=metrics_csv is not None)
     for name in names:
         v1, r1 = read_video(os.path.join(root1, name))
         v2, r2 = read_video(os.path.join(root2, name))
         if r1 != r2:
             raise ValueError(f"{name}: one side holds uint8 frames and the other float video")
         dt = torch.float16 if v1.dtype == torch.float16 and v2.dtype == torch.float16 else torch.float32
-        m = acc.add_video(v1.to(device, dtype=dt), v2.to(device, dtype=dt), rescale=r1)
+        m = acc.add_video(v1.to(device, dtype=dt), v2.to(device, dtype=dt), rescale=r1,
+                          names=[os.path.abspath(os.path.join(root2, name))] if acc.csv else None)
         print(f"{name}: PSNR {m['psnr_mean']:.4f} SSIM {m['ssim_mean']:.6f}" + (f" LPIPS {m['lpips_mean']:.6f}" if lpips is not None else "")
-              + f" ({len(m['psnr'])} frames)")
+              + (f" SSIM3D {m['ssim3d']:.6f} SSIM2D {m['ssim2d']:.6f}" if gssim else "") + f" ({len(m['psnr'])} frames)")
     results = acc.result()
     path = acc.save(results_dir, root1, root2)
     print(f"Results: {results}{acc.fvd_note()}\nSaved to {path}")
+    if metrics_csv is not None:
+        print(f"Saved per-clip rows to {acc.save_csv(metrics_csv)}")
     return path
 
 
@@ -116,8 +120,10 @@ def main(argv=None):
     fvd = fvd_from_args(a)
     subdirs = sorted(d for d in os.listdir(a.root2) if os.path.isdir(os.path.join(a.root2, d)))
     if subdirs and not list_videos(a.root2):            # one folder per experiment: one result file each
-        return [score_folders(a.root1, os.path.join(a.root2, d), os.path.join(a.results_dir, d), lpips=lpips, fvd=fvd) for d in subdirs]
-    return [score_folders(a.root1, a.root2, a.results_dir, lpips=lpips, fvd=fvd)]
+        csv_of = lambda d: None if a.metrics_csv is None else "{0}_{2}{1}".format(*os.path.splitext(a.metrics_csv), d)   # noqa: E731
+        return [score_folders(a.root1, os.path.join(a.root2, d), os.path.join(a.results_dir, d), lpips=lpips, fvd=fvd, gssim=a.gssim,
+                              metrics_csv=csv_of(d)) for d in subdirs]
+    return [score_folders(a.root1, a.root2, a.results_dir, lpips=lpips, fvd=fvd, gssim=a.gssim, metrics_csv=a.metrics_csv)]
 
 
 if __name__ == "__main__":

@@ -47,3 +47,10 @@ if not os.path.exists(TEMPORAL_HEADER):
     raise HVKernelError(f"{TEMPORAL_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
 with open(TEMPORAL_HEADER) as _f:
     TEMPORAL_DECLS, TEMPORAL_MACROS = parse(_f.read())
+
+# include/hv_gssim.h: the Gaussian-window SSIM (csrc/hv_gssim.hip), declared and parsed the same way
+GSSIM_HEADER = os.path.join(os.path.dirname(HEADER), "hv_gssim.h")
+if not os.path.exists(GSSIM_HEADER):
+    raise HVKernelError(f"{GSSIM_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
+with open(GSSIM_HEADER) as _f:
+    GSSIM_DECLS, GSSIM_MACROS = parse(_f.read())

@@ -16,6 +16,8 @@ Temporal spectra (`temporal_spectrum`, `spectrum_report`; csrc/hv_spectrum.hip) 
 FVD (`I3D`, `fvd_logits`, `frechet_distance`; csrc/hv_i3d.hip) is the `method='videogpt'` path of the fork's calculate_fvd: Inception-I3D
 logits of every input clip and every reconstruction as fp32-MFMA 3-D convolutions, then the Frechet distance on the host.  Its weights are
 user-supplied too.  The value is "FVD (videogpt I3D logits)", not interchangeable with the styleganv variant (a TorchScript archive).
+Gaussian-window SSIM (`gaussian_ssim`, `gaussian_ssim_sums`; csrc/hv_gssim.hip) is the SSIM of the fork's rebuttal tables: an 11-tap
+Gaussian over T, H and W (run.py, pytorch_msssim) and per frame (calculate_ssim.py, cv2), in fp64 on the same 8-bit frames.
 Content statistics (`content_histograms`, `content_entropy`, `content_bucket`; csrc/hv_content.hip) give the measure behind the fork's
 InterEntropy bucket lists - the entropy of the gray frame-difference histogram, a definition of this project's own.
 What it is not: there is no video codec in between (the reference's frames went through libx264).  CPU tensors are refused like
@@ -98,18 +100,21 @@ def video_stats(ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True) -> d
     return {"sse": sse, "minmax": minmax, "ssim_sum": ssim_sum, "shape": (B, C, T, H, W)}
 
 
-def video_metrics(ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True, lpips: "LpipsAlex" = None) -> dict:
+def video_metrics(ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True, lpips: "LpipsAlex" = None, gssim: bool = False) -> dict:
     """PSNR / SSIM per frame of `rec` against `ref` ([C,T,H,W] or [B,C,T,H,W] GPU tensors, fp16 or fp32, values in [-1, 1] with
     rescale=True, [0, 1] without).  One host synchronisation.  Returns float64 numpy arrays `psnr`, `ssim` ([T], or [B,T] for a batch),
     their means `psnr_mean`, `ssim_mean`, and the raw integers `sse`, `minmax` the scores were formed from.  With `lpips` (an
-    LpipsAlex) also `lpips` (per frame) and `lpips_mean`."""
+    LpipsAlex) also `lpips` (per frame) and `lpips_mean`; with `gssim` also the keys of gaussian_ssim (`ssim3d`, `ssim2d`, `ssim2d_frames`,
+    `temporal`)."""
     batched = ref.dim() == 5
     st = video_stats(ref, rec, rescale)
     B, C, T, H, W = st["shape"]
     if lpips is not None:
         st["lpips_sums"], lp_pixels = _lpips_enqueue(ref, rec, lpips, rescale, None)
+    if gssim:
+        st["gssim3"], g_temporal, st["gssim2"] = _gssim_enqueue(ref, rec, rescale)
     host = {}
-    for k in ("sse", "minmax", "ssim_sum") + (("lpips_sums",) if lpips is not None else ()):
+    for k in ("sse", "minmax", "ssim_sum") + (("lpips_sums",) if lpips is not None else ()) + (("gssim3", "gssim2") if gssim else ()):
         host[k] = torch.empty(st[k].shape, dtype=st[k].dtype, pin_memory=True)
         host[k].copy_(st[k], non_blocking=True)
     torch.cuda.current_stream(ref.device).synchronize()
@@ -126,6 +131,119 @@ def video_metrics(ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True, lp
         lp = lpips_from_sums(host["lpips_sums"].numpy(), lp_pixels)[0]
         out["lpips"] = lp if batched else lp[0]
         out["lpips_mean"] = float(lp.mean())
+    if gssim:
+        g = gssim_from_sums(host["gssim3"].numpy(), host["gssim2"].numpy(), H, W)
+        if not batched:
+            g = {"ssim3d": float(g["ssim3d"][0]), "ssim2d": float(g["ssim2d"][0]), "ssim2d_frames": g["ssim2d_frames"][0]}
+        out.update(g, temporal=g_temporal)
+    return out
+
+
+# ---- Gaussian-window SSIM (csrc/hv_gssim.hip, include/hv_gssim.h) -----------------------------------------------------------------------
+# The fork's second scoring programme, rebuttal/common_metrics_on_video_quality: run.py:61-68 calls pytorch_msssim.ssim on the 5-D tensor
+# [B,C,T,H,W] (data_range 1: an 11-tap Gaussian, sigma 1.5, over T, H and W, valid positions, C1 = 0.01^2, C2 = 0.03^2) - `ssim3d`;
+# calculate_ssim.py beside it applies cv2.getGaussianKernel(11, 1.5) per frame and channel in float64 - `ssim2d`.  Neither package is part
+# of this environment: the definition is pinned to this project's restatement (tests/gssim_ref.py).
+GSSIM_WIN = _abi.GSSIM_MACROS["HV_GSSIM_WIN"]
+GSSIM_SIGMA = 1.5
+
+
+def gaussian_window(dtype=torch.float32) -> np.ndarray:
+    """The 11 weights exp(-(i - 5)^2 / (2 * 1.5^2)) / sum as float64 numpy.  torch.float32: computed and normalised in fp32, then widened
+    (pytorch_msssim._fspecial_gauss_1d); torch.float64: the same formula in double (cv2.getGaussianKernel(11, 1.5))."""
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"gaussian_window: torch.float32 or torch.float64, got {dtype}")
+    c = torch.arange(GSSIM_WIN, dtype=dtype) - GSSIM_WIN // 2
+    g = torch.exp(-(c ** 2) / (2 * GSSIM_SIGMA ** 2))
+    return (g / g.sum()).double().numpy()
+
+
+_gssim_windows = {}
+
+
+def _gssim_window_on(device, dtype) -> torch.Tensor:
+    key = (str(device), dtype)
+    if key not in _gssim_windows:
+        _gssim_windows[key] = torch.from_numpy(gaussian_window(dtype)).to(device)
+    return _gssim_windows[key]
+
+
+def gaussian_ssim_sums(ref: torch.Tensor, rec: torch.Tensor, temporal: bool = True, rescale: bool = True, win: torch.Tensor = None):
+    """Sums of the Gaussian-window SSIM map, left on the device: float64 [B,To,C], To = T - 10 with `temporal` (the window runs along T, H
+    and W) and T without (H and W only); each entry is the sum over the (H - 10) * (W - 10) positions of that output frame and channel.
+    [C,T,H,W] inputs count as B = 1; the first min(T_ref, T_rec) frames are scored, as by video_stats.  `win`: 11 float64 weights on the
+    device (default: the fp32-form window with `temporal`, the fp64-form one without).  Nothing is synchronised."""
+    _check_video(ref, "ref"), _check_video(rec, "rec")
+    if ref.dim() == 4:
+        ref = ref[None]
+    if rec.dim() == 4:
+        rec = rec[None]
+    if ref.dtype != rec.dtype:
+        raise _lib.HVKernelError(f"ref and rec must have one dtype, got {ref.dtype} and {rec.dtype}")
+    if ref.device != rec.device:
+        raise _lib.HVKernelError(f"ref and rec are on different devices: {ref.device}, {rec.device}")
+    B, C, _, H, W = ref.shape
+    if (rec.shape[0], rec.shape[1], rec.shape[3], rec.shape[4]) != (B, C, H, W):
+        raise _lib.HVKernelError(f"ref {tuple(ref.shape)} and rec {tuple(rec.shape)} differ in more than the frame count")
+    T = min(ref.shape[2], rec.shape[2])
+    dev = ref.device
+    temporal = 1 if temporal else 0
+    if win is None:
+        win = _gssim_window_on(dev, torch.float32 if temporal else torch.float64)
+    if not isinstance(win, torch.Tensor) or win.device != dev or win.dtype != torch.float64 or win.shape != (GSSIM_WIN,) or \
+            not win.is_contiguous():
+        raise _lib.HVKernelError(f"win: expected {GSSIM_WIN} contiguous float64 weights on {dev}")
+    ws_bytes = _lib.host("gaussian_ssim_workspace_bytes", C, T, H, W, temporal)
+    if ws_bytes <= 0:
+        raise _lib.HVKernelError(f"gaussian_ssim: shape C={C} T={T} H={H} W={W} temporal={temporal} is refused (C 1 | 3, H and W >= "
+                                 f"{GSSIM_WIN}, T >= {GSSIM_WIN} with the temporal window)")
+    To = T - (GSSIM_WIN - 1) * temporal
+    sums = torch.empty(B, To, C, dtype=torch.float64, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    for b in range(B):
+        a, r = ref[b], rec[b]
+        _lib.call("gaussian_ssim", a, a.stride(0), a.stride(1), a.stride(2), r, r.stride(0), r.stride(1), r.stride(2),
+                  _DTYPES[ref.dtype], C, T, H, W, 1 if rescale else 0, temporal, win, sums[b], ws, ws.numel())
+    return sums
+
+
+def _gssim_enqueue(ref, rec, rescale):
+    """-> (sums of the run.py score, whether its window spans T, sums of the calculate_ssim.py score), on the device"""
+    T = min(ref.shape[-3], rec.shape[-3])
+    temporal = T >= GSSIM_WIN
+    if not temporal:
+        import warnings
+        warnings.warn(f"gaussian_ssim: {T} frames are fewer than the window's {GSSIM_WIN}: ssim3d skips the T axis (pytorch_msssim "
+                      "does the same), so it is a 2-D score under the fp32-form window", stacklevel=3)
+    dev = ref.device
+    s3 = gaussian_ssim_sums(ref, rec, temporal, rescale, _gssim_window_on(dev, torch.float32))
+    s2 = gaussian_ssim_sums(ref, rec, False, rescale, _gssim_window_on(dev, torch.float64))
+    return s3, temporal, s2
+
+
+def gssim_from_sums(sums3d, sums2d, H: int, W: int) -> dict:
+    """host rules on the sums [B,To,C] and [B,T,C] (numpy float64): ssim3d [B] = mean over channels, output frames and positions (run.py);
+    ssim2d_frames [B,T] = per frame the mean over channels, ssim2d [B] = their mean over frames (calculate_ssim.py)"""
+    npos = float((H - GSSIM_WIN + 1) * (W - GSSIM_WIN + 1))
+    s3, s2 = np.asarray(sums3d, dtype=np.float64), np.asarray(sums2d, dtype=np.float64)
+    frames = (s2 / npos).mean(axis=2)
+    return {"ssim3d": (s3 / npos).mean(axis=(1, 2)), "ssim2d": frames.mean(axis=1), "ssim2d_frames": frames}
+
+
+def gaussian_ssim(ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True) -> dict:
+    """Both Gaussian-window scores of `rec` against `ref` ([C,T,H,W] or [B,C,T,H,W] GPU tensors as video_metrics takes them); one host
+    synchronisation.  `ssim3d`: the run.py score (fp32-form window over T, H, W; with fewer than 11 frames over H, W only, with a
+    warning); `ssim2d`: the calculate_ssim.py score (fp64-form window per frame); `ssim2d_frames`: its per-frame values; `temporal`:
+    whether ssim3d's window spanned T.  Floats and [T] for one video, [B] and [B,T] for a batch."""
+    batched = ref.dim() == 5
+    s3, temporal, s2 = _gssim_enqueue(ref, rec, rescale)
+    h3 = torch.empty(s3.shape, dtype=s3.dtype, pin_memory=True).copy_(s3, non_blocking=True)
+    h2 = torch.empty(s2.shape, dtype=s2.dtype, pin_memory=True).copy_(s2, non_blocking=True)
+    torch.cuda.current_stream(ref.device).synchronize()
+    out = gssim_from_sums(h3.numpy(), h2.numpy(), ref.shape[-2], ref.shape[-1])
+    if not batched:
+        out = {"ssim3d": float(out["ssim3d"][0]), "ssim2d": float(out["ssim2d"][0]), "ssim2d_frames": out["ssim2d_frames"][0]}
+    out["temporal"] = temporal
     return out
 
 
@@ -1064,12 +1182,30 @@ def save_results(results: dict, root1: str, root2: str, results_dir: str, timest
     return path
 
 
+METRICS_CSV_HEADER = ["video_path", "ssim", "psnr", "lpips", "fvd", "fvdm"]
+
+
+def add_gssim_arguments(parser, csv: bool = True):
+    parser.add_argument("--gssim", action="store_true", help="score the Gaussian-window SSIMs of the fork's rebuttal tables too: SSIM3D "
+                        "(run.py: pytorch_msssim on [B,C,T,H,W], the window spans T) and SSIM2D (calculate_ssim.py: per frame)")
+    if csv:
+        parser.add_argument("--metrics-csv", type=str, default=None, help="write one row per clip under run.py's header (video_path, ssim, "
+                            "psnr, lpips, fvd, fvdm); ssim is SSIM3D; fvd and fvdm stay empty (styleganv detector / keypoint tracker: "
+                            "out of scope)")
+
+
 class MetricsAccumulator:
     """Per-frame scores of many videos; the experiment's number is the mean over all FRAMES (compute_metrics.py:150-154), so a long
     video weighs more than a short one.  `lpips` (an LpipsAlex): add_video scores LPIPS too (compute_metrics.py:142-146,153-154)."""
 
-    def __init__(self, lpips: "LpipsAlex" = None, fvd: "I3D" = None):
+    def __init__(self, lpips: "LpipsAlex" = None, fvd: "I3D" = None, gssim: bool = False, csv: bool = False):
+        """`gssim`: add_video scores the two Gaussian-window SSIMs too and result() gains "SSIM3D", "SSIM2D".  `csv`: add_video(names=)
+        also keeps one row per clip for save_csv (the Gaussian-window scores are computed for it, result() is unchanged by it)."""
         self.psnr, self.ssim, self.lpips = [], [], []
+        self.gssim = gssim
+        self.csv = csv
+        self.csv_rows = []
+        self.ssim3d, self.ssim2d = [], []          # with gssim: one value of each Gaussian-window score per clip
         self.lpips_model = lpips
         self.fvd_model = fvd
         self.fvd_ref, self.fvd_rec = [], []        # one I3D logits vector [400] per input clip and per reconstruction
@@ -1087,14 +1223,24 @@ class MetricsAccumulator:
         self.psnr.extend(psnr.tolist())
         self.ssim.extend(ssim.tolist())
 
-    def add_video(self, ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True, ref_logits=None) -> dict:
+    def add_video(self, ref: torch.Tensor, rec: torch.Tensor, rescale: bool = True, ref_logits=None, names=None) -> dict:
         """`ref_logits` (with fvd=): the I3D logits of `ref` from an earlier call (m["fvd_ref_logits"]), which do not depend on how
         `rec` was made; they are computed here otherwise.  With fvd= a pair with fewer than 10 common frames is a ValueError, raised
         before anything of the pair is scored (the reference asserts the same): it is not skipped."""
         if self.fvd_model is not None and min(ref.shape[-3], rec.shape[-3]) < I3D_MIN_FRAMES:
             raise ValueError(f"fvd: a clip needs at least {I3D_MIN_FRAMES} frames, got {min(ref.shape[-3], rec.shape[-3])} common frames")
-        m = video_metrics(ref, rec, rescale, lpips=self.lpips_model)
+        m = video_metrics(ref, rec, rescale, lpips=self.lpips_model, gssim=self.gssim or self.csv)
         self.add(m["psnr"], m["ssim"], m.get("lpips"))
+        if self.csv:
+            if names is None:
+                raise ValueError("an accumulator with csv=True needs add_video(names=[one path per clip])")
+            rows = lambda v: np.asarray(v, dtype=np.float64).reshape(len(names), -1)      # noqa: E731
+            lp = rows(m["lpips"]).mean(axis=1) if "lpips" in m else [""] * len(names)
+            for name, s3, ps, l in zip(names, np.atleast_1d(m["ssim3d"]), rows(m["psnr"]).mean(axis=1), lp):
+                self.csv_rows.append([name, float(s3), float(ps), l if l == "" else float(l), "", ""])
+        if self.gssim:
+            self.ssim3d.extend(np.atleast_1d(m["ssim3d"]).tolist())
+            self.ssim2d.extend(np.atleast_1d(m["ssim2d"]).tolist())
         if self.fvd_model is not None:
             T = min(ref.shape[-3], rec.shape[-3])               # the frames the other scores saw
             lr = fvd_logits(ref[..., :T, :, :], self.fvd_model, rescale) if ref_logits is None else ref_logits
@@ -1118,7 +1264,7 @@ class MetricsAccumulator:
         return len(self.psnr)
 
     def result(self) -> dict:
-        """{"PSNR": ..., "SSIM": ...}, only if LPIPS values were added "LPIPS", and only if the logits of at least two clip pairs were
+        """{"PSNR": ..., "SSIM": ...}, only if LPIPS values were added "LPIPS", only with gssim "SSIM3D" and "SSIM2D", and only if the logits of at least two clip pairs were
         added "FVD" (FVD_LABEL: the Frechet distance between the inputs' and the reconstructions' I3D logits); empty when nothing was
         added (the reference writes no key then)."""
         out = {}
@@ -1127,6 +1273,9 @@ class MetricsAccumulator:
             out["SSIM"] = sum(self.ssim) / len(self.ssim)
         if self.lpips:
             out["LPIPS"] = sum(self.lpips) / len(self.lpips)
+        if self.ssim3d:                                     # the mean over CLIPS, as run.py averages its per-video rows
+            out["SSIM3D"] = sum(self.ssim3d) / len(self.ssim3d)
+            out["SSIM2D"] = sum(self.ssim2d) / len(self.ssim2d)
         if len(self.fvd_ref) >= 2 and len(self.fvd_ref) == len(self.fvd_rec):
             out["FVD"] = frechet_distance(np.stack(self.fvd_ref), np.stack(self.fvd_rec))
         return out
@@ -1139,6 +1288,19 @@ class MetricsAccumulator:
 
     def _fvd_synthetic(self) -> bool:
         return self.fvd_model is not None and self.fvd_model.label == "synthetic"
+
+    def save_csv(self, path: str) -> str:
+        """one row per clip under the header of the fork's rebuttal/common_metrics_on_video_quality/run.py: `ssim` is ssim3d (its
+        pytorch_msssim call), `psnr` the mean of the per-frame values (calculate_psnr.py's rule is scores_from_stats'), `lpips` the
+        per-frame mean when the accumulator holds LPIPS weights and empty otherwise; `fvd` (run.py: the styleganv detector per video) and
+        `fvdm` (a keypoint tracker) are out of scope and always empty"""
+        import csv
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, mode="w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(METRICS_CSV_HEADER)
+            w.writerows(self.csv_rows)
+        return path
 
     def save(self, results_dir: str, root1: str, root2: str, timestamp: str = None) -> str:
         """the `FVD:` line, present only when result() has the key, carries the variant and the clip count beside the value"""

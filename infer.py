@@ -85,9 +85,12 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
                       f"{fmt(c['reconstruction']['inter_entropy'])} bits, intra-frame {fmt(c['input']['intra_entropy'])} / "
                       f"{fmt(c['reconstruction']['intra_entropy'])} (this project's definition)")
         if scorer is not None:
-            m = scorer.add_video(video, recon, rescale=True)
+            m = scorer.add_video(video, recon, rescale=True,
+                                 names=[os.path.abspath(os.path.join(output_dir, f"{name}.pt")) for name in names] if scorer.csv else None)
             for b, name in enumerate(names):
                 lp = f" LPIPS {m['lpips'][b].mean():.6f}" if "lpips" in m else ""
+                if scorer.gssim:
+                    lp += f" SSIM3D {m['ssim3d'][b]:.6f} SSIM2D {m['ssim2d'][b]:.6f}"
                 print(f"Scored {name}: PSNR {m['psnr'][b].mean():.4f} SSIM {m['ssim'][b].mean():.6f}{lp} ({m['psnr'].shape[1]} frames)")
         if not save:
             continue
@@ -129,6 +132,8 @@ def parse_args(argv=None):
                                                            "(default with --yuv-format: the rate in each file's name)")
     p.add_argument("--content", action="store_true", help="with --score: write <name>_content.json per clip into the results directory - "
                                                          "inter- / intra-frame entropy of input and reconstruction (this project's definition)")
+    from hunyuanvideo_efficiency_amd.metrics import add_gssim_arguments
+    add_gssim_arguments(p)               # --gssim, --metrics-csv PATH, with --score
     from hunyuanvideo_efficiency_amd.dataset import add_yuv_arguments, check_yuv_arguments
     add_yuv_arguments(p)                 # --yuv-format {I420,NV12,YV12} [--target-height N] [--start-frame A] [--end-frame B]
     a = p.parse_args(argv)
@@ -137,6 +142,8 @@ def parse_args(argv=None):
         p.error("--spectrum is only valid with --score")
     if a.content and not a.score:
         p.error("--content is only valid with --score")
+    if (a.gssim or a.metrics_csv) and not a.score:
+        p.error("--gssim and --metrics-csv are only valid with --score")
     if a.fps is not None and not a.spectrum:
         p.error("--fps is only valid with --spectrum")
     if a.fps is not None and not a.fps > 0:
@@ -181,7 +188,7 @@ def main(argv=None):
     if not a.score:
         return infer_vae(vae, dataset, device, a.output_dir, a.max_files, a.batch_size)
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator, fvd_from_args, lpips_from_args
-    scorer = MetricsAccumulator(lpips=lpips_from_args(a), fvd=fvd_from_args(a, score=a.score))
+    scorer = MetricsAccumulator(lpips=lpips_from_args(a), fvd=fvd_from_args(a, score=a.score), gssim=a.gssim, csv=bool(a.metrics_csv))
     done = infer_vae(vae, dataset, device, a.output_dir, a.max_files, a.batch_size, scorer, not a.no_save,
                      (a.results_dir or a.output_dir) if a.spectrum else None, a.fps, (a.results_dir or a.output_dir) if a.content else None)
     results = scorer.result()
@@ -189,6 +196,8 @@ def main(argv=None):
                                                                if a.lpips_synthetic else "") + scorer.fvd_note())
     path = scorer.save(a.results_dir or a.output_dir, a.tensor_dir, a.output_dir)
     print(f"Saved metrics to {path}")
+    if a.metrics_csv:
+        print(f"Saved per-clip rows to {scorer.save_csv(a.metrics_csv)}")
     return done
 
 

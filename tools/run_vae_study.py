@@ -17,6 +17,8 @@ fork's shell drivers' background batches over several cards are not reproduced.
   ... --yuv-format I420 [--target-height 240] [--start-frame A] [--end-frame B]   --tensor-dir is a folder of raw planar YUV 4:2:0 files
                                         (<name>_<n>fps_<w>x<h>.yuv), converted on the GPU once for all configurations and kept on the
                                         device; with --spectrum and no --fps each file name's frame rate gives the frequency axes
+  ... --gssim                           each record gains "ssim3d" and "ssim2d": the Gaussian-window SSIMs of the fork's rebuttal tables
+                                        (run.py's pytorch_msssim call, whose window spans frames, and calculate_ssim.py's per-frame one)
   ... --content                         each record gains "content": inter- / intra-frame entropy, mean |difference| and TI of the inputs
                                         and of the reconstructions (metrics.content_entropy, this project's definition) and
                                         "inter_entropy_drop", the frame-to-frame detail the configuration removed; the inputs' values
@@ -54,19 +56,20 @@ def build_vae(config_json, vae_path, reduced, device):
 
 
 def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, lpips=None, spectra=None, fps=None, fvd=None,
-               input_logits=None, input_content=None):
+               input_logits=None, input_content=None, gssim=False):
     """-> the study.jsonl record of one configuration.  `fvd` (an I3D, --fvd-i3d / --fvd-synthetic): the record gains "fvd" - FVD
     (videogpt I3D logits) between the inputs and this configuration's reconstructions, None below two clips - and "fvd_clips";
     `input_logits` (a dict the caller keeps across configurations) holds every input clip's logits, which do not depend on the
     configuration: they are computed once.  `spectra` (a dict, --spectrum): temporal spectra are taken too - the record gains
     "spectrum" and the dict is filled with the configuration's mean spectra (`mean_spectra`).  `input_content` (a dict the caller keeps
     across configurations, --content): the record gains "content" (metrics.content_summary); the dict holds every input clip's
-    statistics, computed once"""
+    statistics, computed once.  `gssim` (--gssim): the record gains "ssim3d" and "ssim2d", the Gaussian-window SSIMs of the fork's rebuttal
+    tables (metrics.gaussian_ssim), each the mean over the clips"""
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator
     rec = {"config": os.path.basename(config_json)}
     try:
         vae = build_vae(config_json, vae_path, reduced, device)
-        acc = MetricsAccumulator(lpips=lpips, fvd=fvd)
+        acc = MetricsAccumulator(lpips=lpips, fvd=fvd, gssim=gssim)
         input_logits = {} if input_logits is None else input_logits
         t_in = t_lat = 0
         reports = []
@@ -97,7 +100,11 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
             rec["fvd"] = res.pop("FVD", None)
             rec["fvd_clips"] = acc.clips
             rec["fvd_variant"] = "videogpt I3D logits" + (", synthetic weights" if fvd.label == "synthetic" else "")
+        if gssim:
+            rec_gssim = {"ssim3d": res.pop("SSIM3D", None), "ssim2d": res.pop("SSIM2D", None)}
         rec.update(res)
+        if gssim:
+            rec.update(rec_gssim)
         if lpips is not None and lpips.label == "synthetic":
             rec["lpips_weights"] = "synthetic"          # not comparable with published LPIPS
         rec["frames"] = acc.frames
@@ -236,7 +243,8 @@ def parse_args(argv=None):
                    "under <output-dir>/<bucket>/; records carry \"bucket\"")
     p.add_argument("--interp-mode", default=None, choices=INTERP_MODES, help="with --base-config: the interp_mode of every decoder block "
                    "of each enumerated configuration (default: what the base configuration says)")
-    from hunyuanvideo_efficiency_amd.metrics import add_fvd_arguments, add_lpips_arguments
+    from hunyuanvideo_efficiency_amd.metrics import add_fvd_arguments, add_gssim_arguments, add_lpips_arguments
+    add_gssim_arguments(p, csv=False)    # --gssim: each record gains "ssim3d", "ssim2d"
     add_lpips_arguments(p, synthetic=True)
     add_fvd_arguments(p)
     from hunyuanvideo_efficiency_amd.dataset import add_yuv_arguments, check_yuv_arguments
@@ -299,7 +307,7 @@ def run_sweep(a, configs, dataset, output_dir, lpips, fvd, input_logits, input_c
     records = []
     for cfg in configs:
         spectra = {} if a.spectrum else None
-        rec = run_config(cfg, dataset, a.vae_path, a.reduced, "cuda", a.max_files, lpips, spectra, a.fps, fvd, input_logits, input_content)
+        rec = run_config(cfg, dataset, a.vae_path, a.reduced, "cuda", a.max_files, lpips, spectra, a.fps, fvd, input_logits, input_content, a.gssim)
         if bucket is not None:
             rec["bucket"] = bucket
         if spectra:
