@@ -384,7 +384,7 @@ class HYVideoDiffusionTransformer(nn.Module):
         else:
             t = t.reshape(-1)
             if t.numel() == 1:
-                t = t.expand(B)
+                t = t.repeat(B)     # (not expand: its stride-0 rows are refused by the kernel wrappers' contiguity check)
             outs = []
             for b in range(B):
                 g_b = None if guidance is None else guidance.reshape(-1)[b:b + 1] if guidance.numel() > 1 else guidance

@@ -59,20 +59,58 @@ def _act(y, act):
     return y
 
 
-def gemm(a, w, bias=None, out=None, act=0, n_split=0, out1=None, act1=0, gate=None, res=None):
-    y = E.r(a.float() @ w.float().T + (0 if bias is None else bias.float()))
-    n = w.shape[0]
+def _gemm_store(y, a_rows, out, act, n_split, out1, act1, gate, res):
+    """the epilogues shared by gemm and gemm_fp8, on the rounded product y [M, N]"""
+    n = y.shape[1]
     n0 = n_split if 0 < n_split < n else n
     if gate is not None:
         r = _bf(res.float() + E.r(_act(y, act) * gate.float()))
     else:
         r = _bf(_act(y[:, :n0], act))
     if out is None:
-        out = torch.empty(a.shape[0], n0, dtype=BF16)
+        out = torch.empty(a_rows, n0, dtype=BF16)
     out[:, :n0] = r[:, :n0]
     if n0 < n:
         out1[:, :n - n0] = _bf(_act(y[:, n0:], act1))
     return out
+
+
+def gemm(a, w, bias=None, out=None, act=0, n_split=0, out1=None, act1=0, gate=None, res=None):
+    y = E.r(a.float() @ w.float().T + (0 if bias is None else bias.float()))
+    return _gemm_store(y, a.shape[0], out, act, n_split, out1, act1, gate, res)
+
+
+# ---- the opt-in FP8-MFMA path (ops.fp8_dequant, quant_rows_fp8, ln_modulate_fp8, gemm_fp8): the contract of oracle/dit_ref.py
+# (fp8_quant_rows, Fp8MfmaPrec) on CPU float8_e4m3fn tensors
+FP8 = torch.float8_e4m3fn
+
+
+def fp8_dequant(w8, scale_bf16, out_bf16):
+    out_bf16.copy_(_bf(w8.to(BF16).float() * scale_bf16.float()).reshape(out_bf16.shape))
+    return out_bf16
+
+
+def quant_rows_fp8(x, out_q=None, out_scale=None):
+    q, s = R.fp8_quant_rows(x.float())
+    m = x.shape[0]
+    if out_q is None:
+        out_q = torch.empty(m, x.shape[1], dtype=FP8)
+    if out_scale is None:
+        out_scale = torch.empty(m, dtype=torch.float32)
+    out_q.copy_(q.to(FP8))
+    out_scale[:m] = s[:, 0]
+    return out_q, out_scale
+
+
+def ln_modulate_fp8(x, shift=None, scale=None, out_q=None, out_scale=None, eps=1e-6):
+    return quant_rows_fp8(ln_modulate(x, shift, scale, eps=eps), out_q, out_scale)
+
+
+def gemm_fp8(a_q, a_scale, w_q, w_scale, bias=None, out=None, act=0, n_split=0, out1=None, act1=0, gate=None, res=None):
+    m = a_q.shape[0]
+    y = (a_q.float() @ (w_q.float() * w_scale.float()).T) * a_scale[:m, None]
+    y = E.r(y + (0 if bias is None else bias.float()))
+    return _gemm_store(y, m, out, act, n_split, out1, act1, gate, res)
 
 
 def linear_smallm(x, w, bias=None, silu_in=False, silu_out=False, out=None, addend=None):
@@ -129,6 +167,8 @@ def broadcast_row_(src, dst):
 
 
 def timestep_embedding(t_f32, dim=256, max_period=10000.0):
+    if t_f32.dtype != torch.float32 or (t_f32.dim() > 0 and t_f32.stride(-1) != 1):     # what ops._chk refuses
+        raise ValueError("t: expected fp32 with a contiguous innermost dimension")
     return _bf(R.timestep_embedding(t_f32.reshape(-1), dim, max_period))
 
 
@@ -310,7 +350,8 @@ def install_vae_mid_attention(monkeypatch, softmax_mutant=None):
 
 
 NAMES = ["ln_modulate", "qknorm_rope_", "gemm", "linear_smallm", "attn_fwd", "patchify", "unpatchify", "euler_step_",
-         "masked_mean", "broadcast_row_", "timestep_embedding", "copy3d"]
+         "masked_mean", "broadcast_row_", "timestep_embedding", "copy3d",
+         "fp8_dequant", "quant_rows_fp8", "ln_modulate_fp8", "gemm_fp8"]
 
 
 def install():
