@@ -54,3 +54,10 @@ if not os.path.exists(GSSIM_HEADER):
     raise HVKernelError(f"{GSSIM_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
 with open(GSSIM_HEADER) as _f:
     GSSIM_DECLS, GSSIM_MACROS = parse(_f.read())
+
+# include/hv_yuv_write.h: video tensor -> raw YUV 4:2:0 frames (csrc/hv_yuv_write.hip), declared and parsed the same way
+YUVW_HEADER = os.path.join(os.path.dirname(HEADER), "hv_yuv_write.h")
+if not os.path.exists(YUVW_HEADER):
+    raise HVKernelError(f"{YUVW_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
+with open(YUVW_HEADER) as _f:
+    YUVW_DECLS, YUVW_MACROS = parse(_f.read())

@@ -36,6 +36,59 @@ def parse_yuv_name(name: str):
     return float(fps.group(1)), int(res.group(1)), int(res.group(2))
 
 
+Y4M_FRAME_MARK = b"FRAME\n"
+
+
+def parse_y4m_header(line: bytes, name: str = "y4m"):
+    """the stream header line of a YUV4MPEG2 file (without its newline) -> (fps, W, H).  Only 8-bit 4:2:0 (`C420*`; absent means 420jpeg)
+    and progressive (`Ip`; absent is taken as progressive) streams are accepted; anything else raises a ValueError that names the token"""
+    tokens = line.decode("ascii", "replace").split(" ")
+    if tokens[0] != "YUV4MPEG2":
+        raise ValueError(f"{name}: not a YUV4MPEG2 stream (it starts with {tokens[0][:16]!r})")
+    W = H = fps = None
+    for tok in tokens[1:]:
+        if not tok:
+            continue
+        tag, val = tok[0], tok[1:]
+        try:
+            if tag == "W":
+                W = int(val)
+            elif tag == "H":
+                H = int(val)
+            elif tag == "F":
+                num, den = val.split(":")
+                fps = int(num) / int(den)
+                if not fps > 0:
+                    raise ValueError
+        except (ValueError, ZeroDivisionError):
+            raise ValueError(f"{name}: malformed header token {tok!r}") from None
+        if tag == "C" and val not in ("420", "420jpeg", "420mpeg2", "420paldv"):      # C420p10 and friends are not 8-bit
+            raise ValueError(f"{name}: only 8-bit 4:2:0 streams are read, the header says {tok!r}")
+        if tag == "I" and val != "p":
+            raise ValueError(f"{name}: only progressive streams are read, the header says {tok!r}")
+    if W is None or H is None or fps is None:
+        raise ValueError(f"{name}: the header lacks {'W' if W is None else 'H' if H is None else 'F'} ({line[:80]!r})")
+    return fps, W, H
+
+
+def read_y4m_header(path: str):
+    """-> (fps, W, H, offset of the first FRAME marker)"""
+    with open(path, "rb") as f:
+        head = f.read(1024)
+    end = head.find(b"\n")
+    if end < 0:
+        raise ValueError(f"{path}: no YUV4MPEG2 header line in the first {len(head)} bytes")
+    return parse_y4m_header(head[:end], os.path.basename(path)) + (end + 1,)
+
+
+def clip_file_info(path: str):
+    """-> (fps, W, H, offset of the first frame record, bytes in front of every frame): a `.y4m` file says it in its header and has a
+    `FRAME` line in front of every frame, a raw `.yuv` file in its name"""
+    if path.endswith(".y4m"):
+        return read_y4m_header(path) + (len(Y4M_FRAME_MARK),)
+    return parse_yuv_name(os.path.basename(path)) + (0, 0)
+
+
 def yuv_frame_bytes(W: int, H: int) -> int:
     if W < 2 or H < 2 or W % 2 or H % 2:
         raise ValueError(f"YUV 4:2:0 frames have even, positive sizes, got {W} x {H}")
@@ -132,13 +185,16 @@ def yuv_to_clip(raw: torch.Tensor, W: int, H: int, fmt: str = "I420", out_dtype=
 def read_yuv_clip(path: str, device="cuda", fmt: str = "I420", start=None, end=None, target_height=None, dtype=torch.float16,
                   frames_per_chunk=None):
     """One `.yuv` file -> (clip [3,T,OH,OW] on `device`, fps).  Size and frame rate come from the file name (`parse_yuv_name`), the frames
-    [start, end) from `yuv_frame_range`; ValueError if no whole frame is in range.  The file is read `frames_per_chunk` whole frames at a
+    [start, end) from `yuv_frame_range`; ValueError if no whole frame is in range.  A `.y4m` file (always I420: `fmt` must say so) carries
+    size and rate in its header; the host drops its `FRAME` lines while staging, so the device sees the same bytes as for a `.yuv`.  The file is read `frames_per_chunk` whole frames at a
     time (default: as many as fit 64 MiB) into at most two pinned staging buffers, so host memory stays bounded whatever the file's
     length; each chunk is uploaded with non_blocking=True and converted straight into its frame slice of the output on the current
     stream, and a staging buffer is refilled only after the event behind its upload has passed."""
-    fps, W, H = parse_yuv_name(os.path.basename(path))
+    fps, W, H, data0, mark = clip_file_info(path)
+    if mark and fmt != "I420":
+        raise ValueError(f"{path}: a .y4m file is I420, not {fmt}")
     frame = yuv_frame_bytes(W, H)
-    first, last = yuv_frame_range(os.path.getsize(path), W, H, start, end)
+    first, last = yuv_frame_range((os.path.getsize(path) - data0) // (frame + mark) * frame, W, H, start, end)
     T = last - first
     if T < 1:
         raise ValueError(f"{path}: no whole frame in [{start}, {end})")
@@ -159,7 +215,7 @@ def read_yuv_clip(path: str, device="cuda", fmt: str = "I420", start=None, end=N
         staged = [torch.empty(per * frame, dtype=torch.uint8, device=device) for _ in range(nbuf)]
         uploaded = [None] * nbuf
         with open(path, "rb", buffering=0) as f:
-            f.seek(first * frame)
+            f.seek(data0 + first * (frame + mark))
             for i, t0 in enumerate(range(0, T, per)):
                 n = min(per, T - t0)
                 b = i % nbuf
@@ -168,7 +224,15 @@ def read_yuv_clip(path: str, device="cuda", fmt: str = "I420", start=None, end=N
                 view = memoryview(pinned[b].numpy())[:n * frame]
                 got = 0
                 while got < n * frame:
-                    k = f.readinto(view[got:])
+                    stop = n * frame
+                    if mark:                             # a FRAME line in front of every frame: checked and dropped
+                        if got % frame == 0:
+                            line = f.read(mark)
+                            if line != Y4M_FRAME_MARK:
+                                raise ValueError(f"{path}: frame {first + t0 + got // frame} starts with {line!r}, not a bare FRAME line "
+                                                 "(frame parameters are not read)")
+                        stop = (got // frame + 1) * frame
+                    k = f.readinto(view[got:stop])
                     if not k:
                         raise IOError(f"{path}: ended {n * frame - got} bytes early (it shrank while being read)")
                     got += k
@@ -183,7 +247,7 @@ def read_yuv_clip(path: str, device="cuda", fmt: str = "I420", start=None, end=N
 
 
 class YuvClipDataset:
-    """The surface of infer.py's VideoTensorDataset over a folder of raw `.yuv` files: sorted names, `ds[i]` -> (clip [3,T,H,W] on the
+    """The surface of infer.py's VideoTensorDataset over a folder of raw `.yuv` (and, for I420, `.y4m`) files: sorted names, `ds[i]` -> (clip [3,T,H,W] on the
     device, file name), with the fork's flags (yuv_tensor.py:16-24).  A file whose name does not parse or that has no whole frame in
     [start, end) is skipped with a printed line, as the fork skips it.  `fps[name]` holds each file's frame rate."""
 
@@ -194,10 +258,14 @@ class YuvClipDataset:
         self.tensor_dir, self.device, self.fmt, self.start, self.end = video_dir, device, fmt, start, end
         self.target_height, self.dtype, self.frames_per_chunk = target_height, dtype, frames_per_chunk
         self.tensor_files, self.fps, self.skipped = [], {}, []
-        for name in sorted(f for f in os.listdir(video_dir) if f.endswith(".yuv")):
+        for name in sorted(f for f in os.listdir(video_dir) if f.endswith((".yuv", ".y4m"))):
             try:
-                fps, W, H = parse_yuv_name(name)
-                first, last = yuv_frame_range(os.path.getsize(os.path.join(video_dir, name)), W, H, start, end)
+                path = os.path.join(video_dir, name)
+                fps, W, H, data0, mark = clip_file_info(path)
+                if mark and fmt != "I420":
+                    raise ValueError(f"a .y4m file is I420, not {fmt}")
+                first, last = yuv_frame_range((os.path.getsize(path) - data0) // (yuv_frame_bytes(W, H) + mark) * yuv_frame_bytes(W, H),
+                                              W, H, start, end)
             except ValueError as e:
                 print(f"Skipping {name}: {e}")
                 self.skipped.append(name)
@@ -247,4 +315,4 @@ def dataset_from_args(args, device="cuda"):
 
 def clip_stem(file_name: str) -> str:
     """the name a driver's outputs carry: the input file's stem"""
-    return file_name[:-len(".yuv")] if file_name.endswith(".yuv") else file_name.replace(".pt", "")
+    return file_name[:-len(".yuv")] if file_name.endswith((".yuv", ".y4m")) else file_name.replace(".pt", "")

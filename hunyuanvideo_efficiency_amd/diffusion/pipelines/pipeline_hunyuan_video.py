@@ -103,14 +103,16 @@ class HunyuanVideoPipeline:
                  callback_steps: int = 1, prompt=None, negative_prompt=None, num_videos_per_prompt: int = 1, data_type: str = "video",
                  is_progress_bar: bool = False, attention_mask: Optional[torch.Tensor] = None, device=None,
                  negative_prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_mask: Optional[torch.Tensor] = None,
-                 negative_prompt_embeds_2: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0):
+                 negative_prompt_embeds_2: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0,
+                 return_on_device: bool = False):
         """Either the reference's keyword surface (`prompt=...`, text encoders attached: pipeline_hunyuan_video.py:664-1100) or
         pre-computed `prompt_embeds` / `prompt_mask` / `prompt_embeds_2` (synthetic benchmarks, tests).
         Batches: B prompts (a list, or B rows of pre-computed embeddings) x `num_videos_per_prompt` give B*N videos, prompt-major;
         `generator` is one torch.Generator or a list of B*N (one per video: inference.resolve_seeds / seed_generators).  The
         transformer and the VAE take the videos one after another through the same kernels and workspaces, so video i equals the
         single-video run with generator[i] (with guidance_rescale > 0 only up to the rounding of its batched std), and N videos cost N
-        times one."""
+        times one.  `return_on_device=True` returns the post-processed fp32 video on the GPU instead of the host (video_io writes it
+        from there): only the copy is skipped."""
         # classifier-free guidance (:966-1019; the non-distilled model): batch [uncond | cond] through the transformer, then
         # uncond + scale (cond - uncond); the CFG-distilled model runs with guidance_scale = 1 and never doubles the batch
         do_cfg = guidance_scale > 1.0
@@ -204,7 +206,8 @@ class HunyuanVideoPipeline:
                 self.vae.enable_tiling()
             image = self.vae.decode(latents, return_dict=False, generator=generator)[0]
             image = vae_ops.postprocess(image.contiguous())   # (image / 2 + 0.5).clamp(0, 1) in fp16, then fp32
-        image = image.cpu().float()
+        # return_on_device: the post-processed video stays on the card (video_io writes it from there); only the copy is skipped
+        image = image.float() if return_on_device else image.cpu().float()
         if not return_dict:
             return image
         return SimpleNamespace(videos=image)

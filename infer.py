@@ -4,7 +4,9 @@
 --config-json (t_ops_config.json) and write the reconstruction to --output-dir/<name>.pt.  Same flags as the reference; input
 tensors and checkpoints are read with torch.load(weights_only=True) only.  With --yuv-format {I420,NV12,YV12} --tensor-dir is a folder
 of raw planar YUV 4:2:0 files instead, converted to clips on the GPU (hunyuanvideo_efficiency_amd/dataset.py; --target-height,
---start-frame, --end-frame as dataset_processor/yuv_tensor.py takes them); outputs keep the input file's stem.  Without --vae-path
+--start-frame, --end-frame as dataset_processor/yuv_tensor.py takes them); outputs keep the input file's stem.  With --save-yuv
+{y4m,I420,YV12,NV12} every reconstruction is also written as 8-bit YUV 4:2:0, converted on the GPU
+(hunyuanvideo_efficiency_amd/video_io.py), under a name that --yuv-format reads back.  Without --vae-path
 the VAE gets deterministic synthetic weights (there are no checkpoints in this environment): the plumbing and the kernels are what is
 exercised."""
 import argparse
@@ -30,7 +32,7 @@ class VideoTensorDataset:
 
 
 def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, scorer=None, save=True, spectrum_dir=None, fps=None,
-              content_dir=None):
+              content_dir=None, save_yuv=None):
     """Reconstructs the first `max_files` tensors, `batch_size` at a time (tensors of one batch must have equal shapes, as a
     DataLoader's default collate requires); every input still gets its own <name>.pt of shape [1, C, T, H, W].
     `scorer` (a metrics.MetricsAccumulator): each reconstruction is scored against its input while both are on the device
@@ -40,7 +42,10 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
     theory_analysis.ipynb) of the input, of the posterior mean the forward already returns and of the reconstruction, with `freq` axes
     when `fps` is given.  `content_dir`: also write <name>_content.json there per input - {"input", "reconstruction"}, each the dict
     of metrics.content_entropy (inter- / intra-frame entropy of the 8-bit gray frames, this project's definition): comparing the two
-    `inter_entropy` values shows how much frame-to-frame detail the configuration removed."""
+    `inter_entropy` values shows how much frame-to-frame detail the configuration removed.
+    `save_yuv` ("y4m" | "I420" | "YV12" | "NV12"): every reconstruction is also written as 8-bit YUV 4:2:0, converted on the device
+    (video_io.save_reconstruction), whatever `save` says: <name>.y4m or <name>_<n>fps_<w>x<h>.yuv, at the input file's rate, else `fps`,
+    else 24; their paths are returned too."""
     if batch_size < 1:
         raise ValueError(f"--batch-size must be >= 1, got {batch_size}")
     os.makedirs(output_dir, exist_ok=True)
@@ -92,6 +97,12 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
                 if scorer.gssim:
                     lp += f" SSIM3D {m['ssim3d'][b]:.6f} SSIM2D {m['ssim2d'][b]:.6f}"
                 print(f"Scored {name}: PSNR {m['psnr'][b].mean():.4f} SSIM {m['ssim'][b].mean():.6f}{lp} ({m['psnr'].shape[1]} frames)")
+        if save_yuv is not None:
+            from hunyuanvideo_efficiency_amd.video_io import save_reconstruction
+            for b, name in enumerate(names):
+                rate = file_fps.get(items[b][1], fps)
+                done.append(save_reconstruction(recon[b], output_dir, name, save_yuv, rate))
+                print(f"Saved reconstructed video to {done[-1]}, {recon.shape[2]} frames of {recon.shape[4]} x {recon.shape[3]}")
         if not save:
             continue
         recon = recon.cpu().float()
@@ -128,14 +139,17 @@ def parse_args(argv=None):
     add_fvd_arguments(p)                 # --fvd-i3d PATH | --fvd-synthetic, with --score
     p.add_argument("--spectrum", action="store_true", help="with --score: write <name>_spectrum.json per clip into the results directory - "
                                                           "temporal spectra of input, latent and reconstruction and their high-band shares")
-    p.add_argument("--fps", type=float, default=None, help="with --spectrum: frame rate of the clips, adds the frequency axes "
-                                                           "(default with --yuv-format: the rate in each file's name)")
+    p.add_argument("--fps", type=float, default=None, help="with --spectrum: frame rate of the clips, adds the frequency axes; with "
+                                                           "--save-yuv: the rate written (default with --yuv-format: the rate in each "
+                                                           "file's name)")
     p.add_argument("--content", action="store_true", help="with --score: write <name>_content.json per clip into the results directory - "
                                                          "inter- / intra-frame entropy of input and reconstruction (this project's definition)")
     from hunyuanvideo_efficiency_amd.metrics import add_gssim_arguments
     add_gssim_arguments(p)               # --gssim, --metrics-csv PATH, with --score
     from hunyuanvideo_efficiency_amd.dataset import add_yuv_arguments, check_yuv_arguments
     add_yuv_arguments(p)                 # --yuv-format {I420,NV12,YV12} [--target-height N] [--start-frame A] [--end-frame B]
+    from hunyuanvideo_efficiency_amd.video_io import add_save_yuv_argument
+    add_save_yuv_argument(p)             # --save-yuv {y4m,I420,YV12,NV12}
     a = p.parse_args(argv)
     check_yuv_arguments(a, p)
     if a.spectrum and not a.score:
@@ -144,8 +158,8 @@ def parse_args(argv=None):
         p.error("--content is only valid with --score")
     if (a.gssim or a.metrics_csv) and not a.score:
         p.error("--gssim and --metrics-csv are only valid with --score")
-    if a.fps is not None and not a.spectrum:
-        p.error("--fps is only valid with --spectrum")
+    if a.fps is not None and not (a.spectrum or a.save_yuv):
+        p.error("--fps is only valid with --spectrum or --save-yuv")
     if a.fps is not None and not a.fps > 0:
         p.error("--fps must be positive")
     if (a.lpips_alexnet or a.lpips_linear or a.lpips_synthetic) and not a.score:
@@ -158,8 +172,8 @@ def parse_args(argv=None):
         p.error("--fvd-* flags are only valid with --score")
     if a.fvd_i3d and a.fvd_synthetic:
         p.error("--fvd-synthetic and --fvd-i3d exclude each other")
-    if a.no_save and not a.score:
-        p.error("--no-save is only valid with --score (nothing would be produced)")
+    if a.no_save and not (a.score or a.save_yuv):
+        p.error("--no-save is only valid with --score or --save-yuv (nothing would be produced)")
     if a.results_dir and not a.score:
         p.error("--results-dir is only valid with --score")
     return a
@@ -186,11 +200,12 @@ def main(argv=None):
     else:
         dataset = VideoTensorDataset(a.tensor_dir)
     if not a.score:
-        return infer_vae(vae, dataset, device, a.output_dir, a.max_files, a.batch_size)
+        return infer_vae(vae, dataset, device, a.output_dir, a.max_files, a.batch_size, save=not a.no_save, fps=a.fps, save_yuv=a.save_yuv)
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator, fvd_from_args, lpips_from_args
     scorer = MetricsAccumulator(lpips=lpips_from_args(a), fvd=fvd_from_args(a, score=a.score), gssim=a.gssim, csv=bool(a.metrics_csv))
     done = infer_vae(vae, dataset, device, a.output_dir, a.max_files, a.batch_size, scorer, not a.no_save,
-                     (a.results_dir or a.output_dir) if a.spectrum else None, a.fps, (a.results_dir or a.output_dir) if a.content else None)
+                     (a.results_dir or a.output_dir) if a.spectrum else None, a.fps, (a.results_dir or a.output_dir) if a.content else None,
+                     a.save_yuv)
     results = scorer.result()
     print(f"Results over {scorer.frames} frames: {results}" + (" (LPIPS under synthetic weights: not comparable with published LPIPS)"
                                                                if a.lpips_synthetic else "") + scorer.fvd_note())

@@ -22,7 +22,7 @@ def _seed_arg(v: str):
     return vals[0] if len(vals) == 1 and "," not in v else vals
 
 
-def parse_args():
+def parse_args(argv=None):
     p = argparse.ArgumentParser(description="HunyuanVideo denoise + decode on MI355X kernels")
     p.add_argument("--model", default="HYVideo-T/2-cfgdistill")
     p.add_argument("--precision", default="bf16", choices=["bf16"])
@@ -67,11 +67,20 @@ def parse_args():
     p.add_argument("--apply-final-norm", action="store_true")
     p.add_argument("--tiny", action="store_true", help="tiny DiT (d=256, 1+1 blocks) and reduced VAE: plumbing check")
     p.add_argument("--save-path", default="./results")
-    return p.parse_args()
+    p.add_argument("--save-format", choices=["auto", "y4m", "yuv"], default="auto", help="auto: mp4 through imageio where it exists, else "
+                   "GIF / .npy (save_videos_grid); y4m | yuv: 8-bit YUV 4:2:0 converted on the GPU (the video never leaves it as floats) - "
+                   "a YUV4MPEG2 file any player opens, or a raw I420 <name>_24fps_<w>x<h>.yuv")
+    p.add_argument("--save-chroma", choices=["mean", "topleft"], default=None, help="with --save-format y4m | yuv: chroma of a 2x2 block "
+                   "from the four pixels' mean (default) or from its top-left pixel, as OpenCV's COLOR_RGB2YUV_I420 takes it")
+    a = p.parse_args(argv)
+    if a.save_chroma is not None and a.save_format == "auto":
+        p.error("--save-chroma is only valid with --save-format y4m or yuv")
+    return a
 
 
-def main():
-    a = parse_args()
+def main(argv=None):
+    """-> (the pipeline's output, the paths written by this rank)"""
+    a = parse_args(argv)
     from hunyuanvideo_efficiency_amd import synthetic as syn
     from hunyuanvideo_efficiency_amd.inference import (init_distributed, parallelize_transformer, get_rotary_pos_embed, resolve_seeds,
                                                        seed_generators)
@@ -159,6 +168,9 @@ def main():
     common = dict(callback=progress, callback_steps=5, height=h, width=w, video_length=a.video_length, num_inference_steps=a.infer_steps, guidance_scale=a.cfg_scale,
                   embedded_guidance_scale=a.embedded_cfg_scale if cfg.guidance_embed else None, generator=gen, freqs_cis=freqs, vae_ver=a.vae,
                   enable_tiling=a.vae_tiling, n_tokens=freqs[0].shape[0], num_videos_per_prompt=a.num_videos)
+    to_yuv = a.save_format != "auto"
+    if to_yuv:                 # the video stays on the card: video_io converts it there and only bytes cross to the host
+        common["return_on_device"] = True
     if a.prompt is not None:
         # without a CLIP encoder the pooled vectors are synthetic, the negative one included (the CFG batch needs both)
         no_clip = text_encoder_2 is None
@@ -170,18 +182,24 @@ def main():
         out = pipe(ts.to(torch.float16), tm, ts2.to(torch.float16), **neg, **common)
         prompts = ["synthetic" if n_prompts == 1 else f"synthetic{i}" for i in range(n_prompts)]
     dt = time.time() - t0
+    written = []
     if rank == 0:
         v = out.videos
+        ext = a.save_format if to_yuv else "mp4"
+        save_kw = dict(chroma=a.save_chroma or "mean") if to_yuv else {}
         print(f"Success, time: {dt:.2f} s; video tensor {tuple(v.shape)} {v.dtype} range [{float(v.min()):.3f}, {float(v.max()):.3f}]")
         os.makedirs(a.save_path, exist_ok=True)
         from hunyuanvideo_efficiency_amd.utils.file_utils import save_videos_grid
         if v.shape[0] == 1:      # one video: the names of a single-video run
-            torch.save(v[:, :, :1].clone(), os.path.join(a.save_path, "first_frame.pt"))
-            print("Sample save to:", save_videos_grid(v, os.path.join(a.save_path, f"seed{seeds[0]}.mp4"), fps=24))
+            torch.save(v[:, :, :1].cpu().clone(), os.path.join(a.save_path, "first_frame.pt"))
+            written.append(save_videos_grid(v, os.path.join(a.save_path, f"seed{seeds[0]}.{ext}"), fps=24, **save_kw))
+            print("Sample save to:", written[-1])
         else:                    # the reference's loop (sample_video.py:48-55): video i of prompt i // N
             for i in range(v.shape[0]):
-                name = f"seed{seeds[i]}_{prompts[i // a.num_videos][:100].replace('/', '')}.mp4"
-                print("Sample save to:", save_videos_grid(v[i:i + 1], os.path.join(a.save_path, name), fps=24))
+                name = f"seed{seeds[i]}_{prompts[i // a.num_videos][:100].replace('/', '')}.{ext}"
+                written.append(save_videos_grid(v[i:i + 1], os.path.join(a.save_path, name), fps=24, **save_kw))
+                print("Sample save to:", written[-1])
+    return out, written
 
 
 if __name__ == "__main__":

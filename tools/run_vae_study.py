@@ -56,7 +56,7 @@ def build_vae(config_json, vae_path, reduced, device):
 
 
 def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, lpips=None, spectra=None, fps=None, fvd=None,
-               input_logits=None, input_content=None, gssim=False):
+               input_logits=None, input_content=None, gssim=False, save_yuv=None, save_dir=None):
     """-> the study.jsonl record of one configuration.  `fvd` (an I3D, --fvd-i3d / --fvd-synthetic): the record gains "fvd" - FVD
     (videogpt I3D logits) between the inputs and this configuration's reconstructions, None below two clips - and "fvd_clips";
     `input_logits` (a dict the caller keeps across configurations) holds every input clip's logits, which do not depend on the
@@ -64,7 +64,8 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
     "spectrum" and the dict is filled with the configuration's mean spectra (`mean_spectra`).  `input_content` (a dict the caller keeps
     across configurations, --content): the record gains "content" (metrics.content_summary); the dict holds every input clip's
     statistics, computed once.  `gssim` (--gssim): the record gains "ssim3d" and "ssim2d", the Gaussian-window SSIMs of the fork's rebuttal
-    tables (metrics.gaussian_ssim), each the mean over the clips"""
+    tables (metrics.gaussian_ssim), each the mean over the clips.  `save_yuv` (--save-yuv) with `save_dir`: every reconstruction is written
+    there as 8-bit YUV 4:2:0, converted on the device (video_io.save_reconstruction); the record gains "saved", the folder"""
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator
     rec = {"config": os.path.basename(config_json)}
     try:
@@ -93,6 +94,12 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
                 if idx not in input_content:
                     content_jobs.append((idx, metrics._content_enqueue(video[0])))
                 content_jobs.append((None, metrics._content_enqueue(recon[0])))
+            if save_yuv is not None:
+                from hunyuanvideo_efficiency_amd.dataset import clip_stem
+                from hunyuanvideo_efficiency_amd.video_io import save_reconstruction
+                # the input file's rate first, as infer.py does
+                save_reconstruction(recon[0], save_dir, clip_stem(file_name), save_yuv, getattr(dataset, "fps", {}).get(file_name, fps))
+                rec["saved"] = save_dir
             t_in += video.shape[2]
             t_lat += z.shape[2]
         res = acc.result()
@@ -249,10 +256,12 @@ def parse_args(argv=None):
     add_fvd_arguments(p)
     from hunyuanvideo_efficiency_amd.dataset import add_yuv_arguments, check_yuv_arguments
     add_yuv_arguments(p)
+    from hunyuanvideo_efficiency_amd.video_io import add_save_yuv_argument
+    add_save_yuv_argument(p)             # --save-yuv {y4m,I420,YV12,NV12}: under <output-dir>/recon_<config>/
     a = p.parse_args(argv)
     check_yuv_arguments(a, p)
-    if a.fps is not None and not (a.spectrum and a.fps > 0):
-        p.error("--fps needs --spectrum and a positive rate")
+    if a.fps is not None and not ((a.spectrum or a.save_yuv) and a.fps > 0):
+        p.error("--fps needs --spectrum or --save-yuv and a positive rate")
     if (a.base_config is None) == (a.config_dir is None):
         p.error("give exactly one of --base-config (enumerate) or --config-dir (ready-made configurations)")
     if a.interp_mode is not None and a.base_config is None:
@@ -307,7 +316,8 @@ def run_sweep(a, configs, dataset, output_dir, lpips, fvd, input_logits, input_c
     records = []
     for cfg in configs:
         spectra = {} if a.spectrum else None
-        rec = run_config(cfg, dataset, a.vae_path, a.reduced, "cuda", a.max_files, lpips, spectra, a.fps, fvd, input_logits, input_content, a.gssim)
+        rec = run_config(cfg, dataset, a.vae_path, a.reduced, "cuda", a.max_files, lpips, spectra, a.fps, fvd, input_logits, input_content, a.gssim,
+                         a.save_yuv, os.path.join(output_dir, f"recon_{os.path.splitext(os.path.basename(cfg))[0]}"))
         if bucket is not None:
             rec["bucket"] = bucket
         if spectra:
