@@ -11,7 +11,8 @@ state dict plus the LPIPS linear file, or one full LPIPS state dict), none are s
 `LPIPS` line.  --fvd-i3d PATH (the I3D state dict i3d_pretrained_400.pt, user-supplied) adds an `FVD:` line when at least two pairs were
 scored; with an --fvd-* flag a pair of fewer than ten common frames is an error that stops the run (the reference asserts the same), it is
 not skipped: "FVD (videogpt I3D logits)", the fork's calculate_fvd with method='videogpt' - not interchangeable with
-the styleganv variant; --fvd-synthetic runs it under stand-in weights (not comparable with any published value).  uint8 frames (.npy, .mp4) go through the rescale=False path, so the network sees exactly those bytes."""
+the styleganv variant; --motion [--motion-block 8|16] [--motion-radius R] [--motion-lam L] adds `MotionEPE:` and `MotionMean:` lines
+(block-matching motion fields of both sides, metrics.motion_compare: this project's own measure, not FVMD); --fvd-synthetic runs it under stand-in weights (not comparable with any published value).  uint8 frames (.npy, .mp4) go through the rescale=False path, so the network sees exactly those bytes."""
 import argparse
 import os
 import sys
@@ -34,10 +35,12 @@ def parse_args(argv=None):
     p.add_argument("--lpips-alexnet", type=str, default=None, help="score LPIPS too: a torchvision AlexNet state dict (needs --lpips-linear), "
                                                                    "or one full LPIPS state dict (.pt / .pth / .safetensors; weights are not shipped)")
     p.add_argument("--lpips-linear", type=str, default=None, help="the LPIPS linear layers (lin{0..4}.model.1.weight)")
-    from hunyuanvideo_efficiency_amd.metrics import add_fvd_arguments, add_gssim_arguments
+    from hunyuanvideo_efficiency_amd.metrics import add_fvd_arguments, add_gssim_arguments, add_motion_arguments, motion_from_args
     add_fvd_arguments(p)
     add_gssim_arguments(p)               # --gssim, --metrics-csv PATH
+    add_motion_arguments(p)              # --motion [--motion-block B] [--motion-radius R] [--motion-lam L]: MotionEPE / MotionMean lines
     a = p.parse_args(argv)
+    a.motion_params = motion_from_args(a, p)
     if a.lpips_linear and not a.lpips_alexnet:
         p.error("--lpips-linear needs --lpips-alexnet")
     if a.fvd_i3d and a.fvd_synthetic:
@@ -84,8 +87,10 @@ def read_video(path):
     return x, True
 
 
-def score_folders(root1, root2, results_dir, device="cuda", lpips=None, fvd=None, gssim=False, metrics_csv=None):
-    from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator
+def score_folders(root1, root2, results_dir, device="cuda", lpips=None, fvd=None, gssim=False, metrics_csv=None, motion=None):
+    """`motion` ({"block", "radius", "lam"}, --motion): every pair's block-matching motion fields are compared too and the result file gains
+    `MotionEPE:` and `MotionMean:` lines (metrics.motion_compare; this project's own measure, not FVMD - the csv's `fvdm` stays blank)"""
+    from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator, motion_compare
     names = pair_files(root1, root2)
     if not names:
         print(f"No matching video files between {root1} and {root2}.")
@@ -100,6 +105,8 @@ def score_folders(root1, root2, results_dir, device="cuda", lpips=None, fvd=None
         dt = torch.float16 if v1.dtype == torch.float16 and v2.dtype == torch.float16 else torch.float32
         m = acc.add_video(v1.to(device, dtype=dt), v2.to(device, dtype=dt), rescale=r1,
                           names=[os.path.abspath(os.path.join(root2, name))] if acc.csv else None)
+        if motion is not None:
+            acc.add_motion(motion_compare(v1.to(device, dtype=dt), v2.to(device, dtype=dt), rescale=r1, **motion))
         print(f"{name}: PSNR {m['psnr_mean']:.4f} SSIM {m['ssim_mean']:.6f}" + (f" LPIPS {m['lpips_mean']:.6f}" if lpips is not None else "")
               + (f" SSIM3D {m['ssim3d']:.6f} SSIM2D {m['ssim2d']:.6f}" if gssim else "") + f" ({len(m['psnr'])} frames)")
     results = acc.result()
@@ -122,8 +129,9 @@ def main(argv=None):
     if subdirs and not list_videos(a.root2):            # one folder per experiment: one result file each
         csv_of = lambda d: None if a.metrics_csv is None else "{0}_{2}{1}".format(*os.path.splitext(a.metrics_csv), d)   # noqa: E731
         return [score_folders(a.root1, os.path.join(a.root2, d), os.path.join(a.results_dir, d), lpips=lpips, fvd=fvd, gssim=a.gssim,
-                              metrics_csv=csv_of(d)) for d in subdirs]
-    return [score_folders(a.root1, a.root2, a.results_dir, lpips=lpips, fvd=fvd, gssim=a.gssim, metrics_csv=a.metrics_csv)]
+                              metrics_csv=csv_of(d), motion=a.motion_params) for d in subdirs]
+    return [score_folders(a.root1, a.root2, a.results_dir, lpips=lpips, fvd=fvd, gssim=a.gssim, metrics_csv=a.metrics_csv,
+                          motion=a.motion_params)]
 
 
 if __name__ == "__main__":

@@ -20,6 +20,8 @@ Gaussian-window SSIM (`gaussian_ssim`, `gaussian_ssim_sums`; csrc/hv_gssim.hip) 
 Gaussian over T, H and W (run.py, pytorch_msssim) and per frame (calculate_ssim.py, cv2), in fp64 on the same 8-bit frames.
 Content statistics (`content_histograms`, `content_entropy`, `content_bucket`; csrc/hv_content.hip) give the measure behind the fork's
 InterEntropy bucket lists - the entropy of the gray frame-difference histogram, a definition of this project's own.
+Motion fields (`block_motion`, `motion_stats`, `motion_compare`; csrc/hv_motion.hip) say how much a clip moves and whether its
+reconstruction moves the same way: full-search block matching on the gray frames, this project's own measure too, not FVMD.
 What it is not: there is no video codec in between (the reference's frames went through libx264).  CPU tensors are refused like
 everywhere else in the package."""
 from __future__ import annotations
@@ -974,19 +976,23 @@ CONTENT_BUCKETS = (("Very_Low_InterEntropy_lt2", None, 2.0), ("Low_InterEntropy_
                    ("High_InterEntropy_gt6", 6.0, None))
 
 
+_BUCKET_WORDS = {"inter": "InterEntropy", "intra": "IntraEntropy", "motion": "Motion"}
+
+
 def _edge_text(v) -> str:
     return f"{float(v):g}"
 
 
 def content_bucket_labels(edges=CONTENT_EDGES, metric: str = "inter"):
     """the bucket labels for `edges` (ascending), lowest first: the fork's names for its own edges (2, 4, 6), the same pattern for others:
-    Very_Low / Low / Medium / High for four buckets, B<i> otherwise; `metric` "inter" | "intra" names the measure"""
+    Very_Low / Low / Medium / High for four buckets, B<i> otherwise; `metric` "inter" | "intra" | "motion" names the measure (`Motion`:
+    `motion_mean` of `motion_stats`, px/frame; its edges have no default - nobody has measured natural clips under that definition)"""
     edges = [float(e) for e in edges]
     if not edges or any(b <= a for a, b in zip(edges, edges[1:])):
         raise ValueError(f"bucket edges must be ascending and not empty, got {edges}")
-    if metric not in ("inter", "intra"):
-        raise ValueError(f"metric is 'inter' or 'intra', got {metric!r}")
-    word = "InterEntropy" if metric == "inter" else "IntraEntropy"
+    if metric not in _BUCKET_WORDS:
+        raise ValueError(f"metric is 'inter', 'intra' or 'motion', got {metric!r}")
+    word = _BUCKET_WORDS[metric]
     n = len(edges) + 1
     ranks = ("Very_Low", "Low", "Medium", "High") if n == 4 else tuple(f"B{i}" for i in range(n))
     out = []
@@ -1137,6 +1143,222 @@ def content_summary(inputs: list, recons: list) -> dict:
     return out
 
 
+# ---- block-matching motion fields (csrc/hv_motion.hip) ---------------------------------------------------------------------------------
+# The fork's per-video table has an `fvdm` column (FVMD: keypoint tracks of a third-party tracker) and its dataset tool a `large_motion`
+# folder; neither program is in the fork.  What follows is NOT FVMD and fills no `fvdm` column: it is dense full-search block matching on
+# the 8-bit gray frames, a measure of this project's own, and every record that carries a value says so.
+MOTION_DEFINITION = ("full-search block matching on 8-bit gray frames (SAD + lam (|dy| + |dx|), ties to the shorter vector), px/frame; "
+                     "this project's own measure, not FVMD")
+MOTION_MAX_RADIUS, MOTION_MAX_LAM = _abi.MOTION_MACROS["HV_MOTION_MAX_RADIUS"], _abi.MOTION_MACROS["HV_MOTION_MAX_LAM"]
+MOTION_BLOCKS = (8, 16)
+
+
+def motion_default_lam(block: int) -> int:
+    """block * block // 16: a displacement of one pixel must gain 1/16 gray code per pixel of the block to be taken.  This project's
+    choice (there is no reference to take it from)."""
+    return int(block) * int(block) // 16
+
+
+def _motion_params(block, radius, lam):
+    block, radius = int(block), int(radius)
+    if block not in MOTION_BLOCKS:
+        raise ValueError(f"motion block is 8 or 16, got {block}")
+    if not 1 <= radius <= MOTION_MAX_RADIUS:
+        raise ValueError(f"motion radius is in [1, {MOTION_MAX_RADIUS}], got {radius}")
+    lam = motion_default_lam(block) if lam is None else int(lam)
+    if not 0 <= lam <= MOTION_MAX_LAM:
+        raise ValueError(f"motion lam is in [0, {MOTION_MAX_LAM}], got {lam}")
+    return block, radius, lam
+
+
+def block_motion(x: torch.Tensor, block: int = 16, radius: int = 16, lam: int = None, rescale: bool = True, luma=GRAY_LUMA):
+    """The motion field of one clip `x` ([3,T,H,W] or [1,3,T,H,W]; GPU tensors only, fp16 or fp32, W contiguous, strided views allowed;
+    gray as in `content_histograms`), left on the device: for every pair of consecutive frames and every `block` x `block` block of the
+    later frame (edge blocks partial) the displacement (dy, dx) in [-radius, radius]^2 into the earlier frame (replicated edges) that
+    minimises SAD + lam (|dy| + |dx|), ties to the smaller dy^2 + dx^2, then dy, then dx.  -> `mv` int16 [T-1, Hb, Wb, 2], `sad` int32
+    [T-1, Hb, Wb] (the winner's SAD without the penalty), `sad0` int32 (the SAD at (0, 0)).  `lam` None = `motion_default_lam(block)`.
+    Exact integers; this project's own measure, not FVMD.  Nothing is synchronised."""
+    _content_check(x, luma)
+    block, radius, lam = _motion_params(block, radius, lam)
+    if x.dim() == 5:
+        if x.shape[0] != 1:
+            raise _lib.HVKernelError(f"block_motion takes one clip at a time, got a batch of {x.shape[0]}")
+        x = x[0]
+    _, T, H, W = x.shape
+    Hb, Wb = -(-H // block), -(-W // block)
+    dev = x.device
+    mv = torch.empty(T - 1, Hb, Wb, 2, dtype=torch.int16, device=dev)
+    sad = torch.empty(T - 1, Hb, Wb, dtype=torch.int32, device=dev)
+    sad0 = torch.empty(T - 1, Hb, Wb, dtype=torch.int32, device=dev)
+    wr, wg, wb, rnd, shift = (int(v) for v in luma)
+    pair = T > 1
+    _lib.call("block_motion", x, x.stride(0), x.stride(1), x.stride(2), _DTYPES[x.dtype], T, H, W, 1 if rescale else 0, wr, wg, wb, rnd,
+              shift, block, radius, lam, mv if pair else None, sad if pair else None, sad0 if pair else None)
+    return mv, sad, sad0
+
+
+def motion_epe(mv_a, mv_b) -> float:
+    """mean Euclidean distance between two vector fields of one shape [P, Hb, Wb, 2] (numpy float64); None without pairs"""
+    a, b = np.asarray(mv_a, dtype=np.float64), np.asarray(mv_b, dtype=np.float64)
+    if a.shape != b.shape:
+        raise ValueError(f"motion fields of different shapes: {a.shape}, {b.shape}")
+    if a.size == 0:
+        return None
+    return float(np.sqrt(((a - b) ** 2).sum(axis=-1)).mean())
+
+
+def motion_from_host(mv, sad, sad0, radius: int, block: int = None, lam: int = None) -> dict:
+    """The host rules on a motion field (numpy float64; pure, also used on CPU by the tests): mv [P, Hb, Wb, 2] = (dy, dx), sad and sad0
+    [P, Hb, Wb].  `motion_mean` - the mean over pairs of the mean over blocks of sqrt(dy^2 + dx^2), px/frame -, `motion_pairs` (per
+    pair), `motion_max`, `static_share` (blocks at (0, 0)), `border_share` (blocks with |dy| or |dx| at the radius: the search was too
+    small for them), `mc_gain` = 1 - sum sad / sum sad0 (0 when sum sad0 is 0), `frames`, `block`, `radius`, `lam`, `definition`.  Without
+    pairs (a single frame) the values are None."""
+    mv = np.asarray(mv, dtype=np.int64)
+    if mv.ndim != 4 or mv.shape[-1] != 2:
+        raise ValueError(f"a motion field is [pairs, Hb, Wb, 2], got {mv.shape}")
+    P = mv.shape[0]
+    d = {"motion_mean": None, "motion_pairs": [], "motion_max": None, "static_share": None, "border_share": None, "mc_gain": None,
+         "frames": P + 1, "block": None if block is None else int(block), "radius": int(radius), "lam": None if lam is None else int(lam),
+         "definition": MOTION_DEFINITION}
+    if P == 0:
+        return d
+    dy, dx = mv[..., 0], mv[..., 1]
+    mag = np.sqrt((dy * dy + dx * dx).astype(np.float64))
+    pairs = mag.reshape(P, -1).mean(axis=1)
+    s, s0 = int(np.asarray(sad, dtype=np.int64).sum()), int(np.asarray(sad0, dtype=np.int64).sum())
+    d.update(motion_mean=float(pairs.mean()), motion_pairs=pairs.tolist(), motion_max=float(mag.max()),
+             static_share=float(((dy == 0) & (dx == 0)).mean()),
+             border_share=float(((np.abs(dy) == int(radius)) | (np.abs(dx) == int(radius))).mean()),
+             mc_gain=(1.0 - s / s0) if s0 else 0.0)
+    return d
+
+
+def _motion_enqueue(x: torch.Tensor, block: int = 16, radius: int = 16, lam: int = None, rescale: bool = True, luma=GRAY_LUMA):
+    """the field of ONE clip, enqueued, nothing synchronised: a job for `_motion_to_host`"""
+    block, radius, lam = _motion_params(block, radius, lam)
+    return (*block_motion(x, block, radius, lam, rescale, luma), block, radius, lam)
+
+
+def _motion_to_host(jobs):
+    """jobs of `_motion_enqueue` on one device -> one synchronisation -> per job the host field {"mv", "sad", "sad0", "block", "radius",
+    "lam"} (numpy)"""
+    host = []
+    for job in jobs:
+        trio = []
+        for t in job[:3]:
+            h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+            h.copy_(t, non_blocking=True)
+            trio.append(h)
+        host.append(trio)
+    torch.cuda.current_stream(jobs[0][0].device).synchronize()
+    return [{"mv": m.numpy(), "sad": s.numpy(), "sad0": s0.numpy(), "block": job[3], "radius": job[4], "lam": job[5]}
+            for job, (m, s, s0) in zip(jobs, host)]
+
+
+def motion_field_stats(field: dict, pairs: int = None) -> dict:
+    """`motion_from_host` of a host field of `_motion_to_host`, of its first `pairs` pairs when given (a pair depends on its two frames
+    only, so the rows of a longer clip are the rows of its prefix)"""
+    p = slice(None) if pairs is None else slice(0, pairs)
+    return motion_from_host(field["mv"][p], field["sad"][p], field["sad0"][p], field["radius"], field["block"], field["lam"])
+
+
+def motion_stats(x: torch.Tensor, block: int = 16, radius: int = 16, lam: int = None, rescale: bool = True, luma=GRAY_LUMA) -> dict:
+    """How much one clip moves ([3,T,H,W] or [1,3,T,H,W], as `block_motion`): the dict of `motion_from_host`.  One host
+    synchronisation.  This project's own measure, not FVMD."""
+    return motion_field_stats(_motion_to_host([_motion_enqueue(x, block, radius, lam, rescale, luma)])[0])
+
+
+def motion_stats_many(clips, block: int = 16, radius: int = 16, lam: int = None, rescale: bool = True, luma=GRAY_LUMA) -> list:
+    """`motion_stats` of every clip of an iterable (a generator may load and drop one clip at a time: only the fields outlive the
+    launches), everything enqueued first: one host synchronisation for all of them"""
+    jobs = [_motion_enqueue(x, block, radius, lam, rescale, luma) for x in clips]
+    return [motion_field_stats(f) for f in _motion_to_host(jobs)] if jobs else []
+
+
+def motion_compare_fields(ref_field: dict, rec_field: dict) -> dict:
+    """two host fields of one geometry -> {"ref", "rec"} (`motion_from_host` of each over the pairs both have), `motion_epe` (the mean
+    Euclidean distance between the two vector fields, px) and `motion_mean_change` = rec - ref"""
+    if any(ref_field[k] != rec_field[k] for k in ("block", "radius", "lam")) or ref_field["mv"].shape[1:] != rec_field["mv"].shape[1:]:
+        raise ValueError("motion fields of different geometry")
+    P = min(ref_field["mv"].shape[0], rec_field["mv"].shape[0])
+    a, b = motion_field_stats(ref_field, P), motion_field_stats(rec_field, P)
+    change = None if a["motion_mean"] is None else b["motion_mean"] - a["motion_mean"]
+    return {"ref": a, "rec": b, "motion_epe": motion_epe(ref_field["mv"][:P], rec_field["mv"][:P]), "motion_mean_change": change,
+            "definition": MOTION_DEFINITION}
+
+
+def _motion_pair_check(ref, rec):
+    """the rules of the pair scorers (`video_stats`): one dtype, one device, shapes equal but for the frame count -> (ref, rec) as
+    [3,T,H,W] cut to the frames both have"""
+    _check_video(ref, "ref"), _check_video(rec, "rec")
+    if ref.dim() == 5 and ref.shape[0] == 1:
+        ref = ref[0]
+    if rec.dim() == 5 and rec.shape[0] == 1:
+        rec = rec[0]
+    if ref.dim() != 4 or rec.dim() != 4:
+        raise _lib.HVKernelError(f"motion_compare takes one clip and one reconstruction, got {tuple(ref.shape)} and {tuple(rec.shape)}")
+    if ref.dtype != rec.dtype:
+        raise _lib.HVKernelError(f"ref and rec must have one dtype, got {ref.dtype} and {rec.dtype}")
+    if ref.device != rec.device:
+        raise _lib.HVKernelError(f"ref and rec are on different devices: {ref.device}, {rec.device}")
+    if (ref.shape[0], ref.shape[2], ref.shape[3]) != (rec.shape[0], rec.shape[2], rec.shape[3]):
+        raise _lib.HVKernelError(f"ref {tuple(ref.shape)} and rec {tuple(rec.shape)} differ in more than the frame count")
+    T = min(ref.shape[1], rec.shape[1])
+    return ref[:, :T], rec[:, :T]
+
+
+def motion_compare(ref: torch.Tensor, rec: torch.Tensor, block: int = 16, radius: int = 16, lam: int = None, rescale: bool = True,
+                   luma=GRAY_LUMA) -> dict:
+    """Does the reconstruction move as its input does: both clips' `motion_stats` over the first min(T_ref, T_rec) frames (the pair
+    scorers' rule) plus `motion_epe` and `motion_mean_change` (`motion_compare_fields`).  One host synchronisation."""
+    ref, rec = _motion_pair_check(ref, rec)
+    a, b = _motion_to_host([_motion_enqueue(ref, block, radius, lam, rescale, luma), _motion_enqueue(rec, block, radius, lam, rescale, luma)])
+    return motion_compare_fields(a, b)
+
+
+_MOTION_MEANS = ("motion_mean", "motion_max", "static_share", "border_share", "mc_gain")
+
+
+def motion_summary(inputs: list, compares: list) -> dict:
+    """The `motion` entry of a driver's record: the fields of `motion_stats` averaged over the clips that have them, for the inputs
+    (`inputs`: their `motion_stats`) and for the reconstructions (`compares`: the `motion_compare` results), and the means of
+    `motion_epe` and `motion_mean_change`"""
+    def mean(ds, k):
+        v = [d[k] for d in ds if d[k] is not None]
+        return sum(v) / len(v) if v else None
+    recs = [c["rec"] for c in compares]
+    first = (inputs or recs or [{}])[0]
+    return {"input": {k: mean(inputs, k) for k in _MOTION_MEANS}, "reconstruction": {k: mean(recs, k) for k in _MOTION_MEANS},
+            "motion_epe": mean(compares, "motion_epe"), "motion_mean_change": mean(compares, "motion_mean_change"), "clips": len(inputs),
+            "block": first.get("block"), "radius": first.get("radius"), "lam": first.get("lam"), "definition": MOTION_DEFINITION}
+
+
+def add_motion_arguments(parser):
+    """--motion [--motion-block 8|16] [--motion-radius R] [--motion-lam L]: the block-matching motion score of the drivers"""
+    parser.add_argument("--motion", action="store_true", help="block-matching motion fields of input and reconstruction (mean px/frame, "
+                                                              "end-point error between the two fields); this project's own measure, not FVMD")
+    parser.add_argument("--motion-block", type=int, default=None, choices=MOTION_BLOCKS, help="with --motion: block size (default 16)")
+    parser.add_argument("--motion-radius", type=int, default=None, help=f"with --motion: search radius, 1..{MOTION_MAX_RADIUS} (default 16)")
+    parser.add_argument("--motion-lam", type=int, default=None, help=f"with --motion: penalty per pixel of |dy| + |dx|, 0..{MOTION_MAX_LAM} "
+                                                                     "(default block * block // 16)")
+
+
+def motion_from_args(args, parser):
+    """-> None without --motion, else {"block", "radius", "lam"}; the sub-flags without --motion and values out of range are errors"""
+    sub = [f for f, v in (("--motion-block", args.motion_block), ("--motion-radius", args.motion_radius), ("--motion-lam", args.motion_lam))
+           if v is not None]
+    if not args.motion:
+        if sub:
+            parser.error(f"{', '.join(sub)} only valid with --motion")
+        return None
+    try:
+        block, radius, lam = _motion_params(16 if args.motion_block is None else args.motion_block,
+                                            16 if args.motion_radius is None else args.motion_radius, args.motion_lam)
+    except ValueError as e:
+        parser.error(str(e))
+    return {"block": block, "radius": radius, "lam": lam}
+
+
 def add_lpips_arguments(parser, synthetic: bool = False):
     """--lpips-alexnet PATH [--lpips-linear PATH] (and --lpips-synthetic for the tools that have a synthetic-weight mode)"""
     parser.add_argument("--lpips-alexnet", type=str, default=None, help="score LPIPS too: a torchvision AlexNet state dict (needs "
@@ -1209,6 +1431,12 @@ class MetricsAccumulator:
         self.lpips_model = lpips
         self.fvd_model = fvd
         self.fvd_ref, self.fvd_rec = [], []        # one I3D logits vector [400] per input clip and per reconstruction
+        self.motion = []                           # add_motion: one motion_compare result per clip pair
+
+    def add_motion(self, compare: dict):
+        """a `motion_compare` result of one clip pair: result() gains "MotionEPE" and "MotionMean" (means over the clips that have
+        pairs of frames), present only once this was called"""
+        self.motion.append(compare)
 
     def add(self, psnr, ssim, lpips=None):
         """per-frame arrays of one video (or a [B,T] batch), e.g. video_metrics(...)["psnr"], ["ssim"] (and ["lpips"])"""
@@ -1278,6 +1506,10 @@ class MetricsAccumulator:
             out["SSIM2D"] = sum(self.ssim2d) / len(self.ssim2d)
         if len(self.fvd_ref) >= 2 and len(self.fvd_ref) == len(self.fvd_rec):
             out["FVD"] = frechet_distance(np.stack(self.fvd_ref), np.stack(self.fvd_rec))
+        if self.motion:                                     # this project's own measure, not FVMD: the `fvdm` column stays blank
+            s = motion_summary([c["ref"] for c in self.motion], self.motion)
+            out["MotionEPE"] = s["motion_epe"]
+            out["MotionMean"] = s["reconstruction"]["motion_mean"]
         return out
 
     def fvd_note(self) -> str:
@@ -1307,4 +1539,9 @@ class MetricsAccumulator:
         res = self.result()
         if "FVD" in res:
             res["FVD"] = fvd_line(res["FVD"], self.clips, self._fvd_synthetic())
+        if "MotionEPE" in res:
+            s = motion_summary([c["ref"] for c in self.motion], self.motion)
+            what = f"block {s['block']}, radius {s['radius']}, lam {s['lam']}; block matching on gray frames, this project's own measure, not FVMD"
+            res["MotionEPE"] = f"{res['MotionEPE']} (px between the input's and the reconstruction's vector fields; {what})"
+            res["MotionMean"] = f"{res['MotionMean']} (px/frame of the reconstructions; inputs {s['input']['motion_mean']})"
         return save_results(res, root1, root2, results_dir, timestamp)

@@ -8,7 +8,8 @@ of raw planar YUV 4:2:0 files instead, converted to clips on the GPU (hunyuanvid
 {y4m,I420,YV12,NV12} every reconstruction is also written as 8-bit YUV 4:2:0, converted on the GPU
 (hunyuanvideo_efficiency_amd/video_io.py), under a name that --yuv-format reads back.  Without --vae-path
 the VAE gets deterministic synthetic weights (there are no checkpoints in this environment): the plumbing and the kernels are what is
-exercised."""
+exercised.  With --score --motion [--motion-block 8|16] [--motion-radius R] [--motion-lam L] every clip also gets <name>_motion.json:
+block-matching motion of input and reconstruction (metrics.motion_compare; this project's own measure, not FVMD)."""
 import argparse
 import json
 import os
@@ -32,7 +33,7 @@ class VideoTensorDataset:
 
 
 def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, scorer=None, save=True, spectrum_dir=None, fps=None,
-              content_dir=None, save_yuv=None):
+              content_dir=None, save_yuv=None, motion_dir=None, motion=None):
     """Reconstructs the first `max_files` tensors, `batch_size` at a time (tensors of one batch must have equal shapes, as a
     DataLoader's default collate requires); every input still gets its own <name>.pt of shape [1, C, T, H, W].
     `scorer` (a metrics.MetricsAccumulator): each reconstruction is scored against its input while both are on the device
@@ -45,7 +46,10 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
     `inter_entropy` values shows how much frame-to-frame detail the configuration removed.
     `save_yuv` ("y4m" | "I420" | "YV12" | "NV12"): every reconstruction is also written as 8-bit YUV 4:2:0, converted on the device
     (video_io.save_reconstruction), whatever `save` says: <name>.y4m or <name>_<n>fps_<w>x<h>.yuv, at the input file's rate, else `fps`,
-    else 24; their paths are returned too."""
+    else 24; their paths are returned too.
+    `motion_dir` with `motion` ({"block", "radius", "lam"}): also write <name>_motion.json there per input - the dict of
+    metrics.motion_compare (block-matching motion of input and reconstruction, the end-point error between the two fields; this project's
+    own measure, not FVMD)."""
     if batch_size < 1:
         raise ValueError(f"--batch-size must be >= 1, got {batch_size}")
     os.makedirs(output_dir, exist_ok=True)
@@ -56,6 +60,9 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
     if content_dir is not None:
         from hunyuanvideo_efficiency_amd.metrics import content_entropy_many
         os.makedirs(content_dir, exist_ok=True)
+    if motion_dir is not None:
+        from hunyuanvideo_efficiency_amd.metrics import motion_compare
+        os.makedirs(motion_dir, exist_ok=True)
     file_fps = getattr(dataset, "fps", {})       # a YuvClipDataset knows each file's frame rate from its name
     n = len(dataset) if max_files is None else min(len(dataset), max_files)
     done = []
@@ -89,6 +96,15 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
                 print(f"Content {name}: inter-frame entropy input {fmt(c['input']['inter_entropy'])} reconstruction "
                       f"{fmt(c['reconstruction']['inter_entropy'])} bits, intra-frame {fmt(c['input']['intra_entropy'])} / "
                       f"{fmt(c['reconstruction']['intra_entropy'])} (this project's definition)")
+        if motion_dir is not None:
+            fmt = lambda v: "n/a" if v is None else f"{v:.4f}"          # noqa: E731  (a single frame has no motion)
+            for b, name in enumerate(names):
+                c = motion_compare(video[b], recon[b], **motion)
+                with open(os.path.join(motion_dir, f"{name}_motion.json"), "w") as f:
+                    json.dump(c, f)
+                print(f"Motion {name}: input {fmt(c['ref']['motion_mean'])} reconstruction {fmt(c['rec']['motion_mean'])} px/frame, "
+                      f"end-point error {fmt(c['motion_epe'])} px (block {motion['block']}, radius {motion['radius']}; this project's own "
+                      "measure, not FVMD)")
         if scorer is not None:
             m = scorer.add_video(video, recon, rescale=True,
                                  names=[os.path.abspath(os.path.join(output_dir, f"{name}.pt")) for name in names] if scorer.csv else None)
@@ -144,7 +160,8 @@ def parse_args(argv=None):
                                                            "file's name)")
     p.add_argument("--content", action="store_true", help="with --score: write <name>_content.json per clip into the results directory - "
                                                          "inter- / intra-frame entropy of input and reconstruction (this project's definition)")
-    from hunyuanvideo_efficiency_amd.metrics import add_gssim_arguments
+    from hunyuanvideo_efficiency_amd.metrics import add_gssim_arguments, add_motion_arguments, motion_from_args
+    add_motion_arguments(p)              # --motion [--motion-block B] [--motion-radius R] [--motion-lam L], with --score
     add_gssim_arguments(p)               # --gssim, --metrics-csv PATH, with --score
     from hunyuanvideo_efficiency_amd.dataset import add_yuv_arguments, check_yuv_arguments
     add_yuv_arguments(p)                 # --yuv-format {I420,NV12,YV12} [--target-height N] [--start-frame A] [--end-frame B]
@@ -156,6 +173,9 @@ def parse_args(argv=None):
         p.error("--spectrum is only valid with --score")
     if a.content and not a.score:
         p.error("--content is only valid with --score")
+    a.motion_params = motion_from_args(a, p)
+    if a.motion and not a.score:
+        p.error("--motion is only valid with --score")
     if (a.gssim or a.metrics_csv) and not a.score:
         p.error("--gssim and --metrics-csv are only valid with --score")
     if a.fps is not None and not (a.spectrum or a.save_yuv):
@@ -205,7 +225,7 @@ def main(argv=None):
     scorer = MetricsAccumulator(lpips=lpips_from_args(a), fvd=fvd_from_args(a, score=a.score), gssim=a.gssim, csv=bool(a.metrics_csv))
     done = infer_vae(vae, dataset, device, a.output_dir, a.max_files, a.batch_size, scorer, not a.no_save,
                      (a.results_dir or a.output_dir) if a.spectrum else None, a.fps, (a.results_dir or a.output_dir) if a.content else None,
-                     a.save_yuv)
+                     a.save_yuv, (a.results_dir or a.output_dir) if a.motion_params else None, a.motion_params)
     results = scorer.result()
     print(f"Results over {scorer.frames} frames: {results}" + (" (LPIPS under synthetic weights: not comparable with published LPIPS)"
                                                                if a.lpips_synthetic else "") + scorer.fvd_note())

@@ -11,7 +11,13 @@ over the frame pairs of a clip - is this project's own (metrics.content_entropy;
 Writes O/content.jsonl (one record per clip: "file", "name", the fields of metrics.content_entropy, "metric", "value", "bucket") and one
 list per non-empty bucket, O/<bucket>.txt, the input paths one per line, sorted; prints one line per bucket.  Buckets are half-open,
 [lo, hi): exactly 2.0 is Low.  A single-frame clip has no inter-frame entropy: its record has "bucket": null and it is in no list.
-All clips are enqueued before the one host synchronisation.  tools/run_vae_study.py --bucket-dir O then runs the sweep per list."""
+All clips are enqueued before the one host synchronisation.  tools/run_vae_study.py --bucket-dir O then runs the sweep per list.
+
+  ... --metric motion --edges E1 [E2 ...] [--motion-block 8|16] [--motion-radius R] [--motion-lam L]
+sorts by how much a clip moves instead (the fork's dataset tool reads a folder called `large_motion`; it does not say how the clips got
+there): `motion_mean` of metrics.motion_stats, the mean length in px/frame of the block-matching vectors - this project's own measure, not
+FVMD.  Nobody has measured natural clips under this definition, so --edges has no default here; the records go to O/motion.jsonl and the
+lists are named <rank>_Motion_<span>.txt."""
 import argparse
 import json
 import os
@@ -26,17 +32,33 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Content buckets of a clip folder by inter-frame entropy (this project's definition).")
     p.add_argument("--tensor-dir", required=True, help="input .pt video tensors [C,T,H,W] (or .yuv files with --yuv-format)")
     p.add_argument("--output-dir", required=True, help="content.jsonl and the <bucket>.txt lists go here")
-    p.add_argument("--metric", choices=("inter", "intra"), default="inter", help="bucket by the entropy of the frame difference (default) "
-                   "or of the gray frame itself")
-    p.add_argument("--edges", type=float, nargs="+", default=[2.0, 4.0, 6.0], help="ascending bucket edges in bits (default: the fork's 2 4 6)")
+    p.add_argument("--metric", choices=("inter", "intra", "motion"), default="inter", help="bucket by the entropy of the frame difference "
+                   "(default), of the gray frame itself, or by the mean block-matching motion in px/frame (needs --edges)")
+    p.add_argument("--edges", type=float, nargs="+", default=None, help="ascending bucket edges, in bits (default: the fork's 2 4 6) or, "
+                   "with --metric motion, in px/frame (no default)")
+    from hunyuanvideo_efficiency_amd import metrics
+    p.add_argument("--motion-block", type=int, default=None, choices=metrics.MOTION_BLOCKS, help="with --metric motion: block size (default 16)")
+    p.add_argument("--motion-radius", type=int, default=None, help="with --metric motion: search radius (default 16)")
+    p.add_argument("--motion-lam", type=int, default=None, help="with --metric motion: penalty per pixel of |dy| + |dx| (default block^2 // 16)")
     p.add_argument("--max-files", type=int, default=None)
     from hunyuanvideo_efficiency_amd.dataset import add_yuv_arguments, check_yuv_arguments
     add_yuv_arguments(p)
     a = p.parse_args(argv)
     check_yuv_arguments(a, p)
+    a.motion = a.metric == "motion"
+    sub = [f for f, v in (("--motion-block", a.motion_block), ("--motion-radius", a.motion_radius), ("--motion-lam", a.motion_lam)) if v is not None]
+    if sub and not a.motion:
+        p.error(f"{', '.join(sub)} only valid with --metric motion")
+    a.motion_params = metrics.motion_from_args(a, p)
+    if a.edges is None:
+        if a.motion:
+            p.error("--metric motion needs --edges in px/frame: nobody has measured natural clips under this definition, there is no default")
+        a.edges = [2.0, 4.0, 6.0]
     if any(b <= e for e, b in zip(a.edges, a.edges[1:])):
         p.error(f"--edges must be ascending, got {a.edges}")
-    if any(not 0.0 < e < 16.0 for e in a.edges):
+    if a.motion and any(not 0.0 < e < 2 ** 0.5 * a.motion_params["radius"] for e in a.edges):
+        p.error(f"--edges are vector lengths in px/frame, between 0 and radius * sqrt(2), got {a.edges}")
+    if not a.motion and any(not 0.0 < e < 16.0 for e in a.edges):
         p.error(f"--edges are entropies in bits, between 0 and 16, got {a.edges}")
     if a.max_files is not None and a.max_files < 1:
         p.error("--max-files must be positive")
@@ -57,13 +79,25 @@ def measure_on_gpu(dataset, n, device="cuda"):
     return metrics.content_entropy_many(clips())
 
 
+def motion_on_gpu(dataset, n, params, device="cuda"):
+    """metrics.motion_stats of the first n clips of `dataset`, as `measure_on_gpu` takes the entropies: one synchronisation"""
+    import torch
+    from hunyuanvideo_efficiency_amd import metrics
+
+    def clips():
+        for idx in range(n):
+            video, _ = dataset[idx]
+            yield video.to(device, dtype=torch.float16)
+    return metrics.motion_stats_many(clips(), **params)
+
+
 def bucket_records(files, tensor_dir, stats, metric, edges):
     """file names and their content_entropy dicts -> (records, {bucket label: sorted paths})"""
     from hunyuanvideo_efficiency_amd import metrics
     from hunyuanvideo_efficiency_amd.dataset import clip_stem
     records, lists = [], {}
     for name, d in zip(files, stats):
-        value = d["inter_entropy"] if metric == "inter" else d["intra_entropy"]
+        value = d[{"inter": "inter_entropy", "intra": "intra_entropy", "motion": "motion_mean"}[metric]]
         label = metrics.content_bucket(value, edges, metric)
         path = os.path.join(tensor_dir, name)
         records.append(dict(file=path, name=clip_stem(name), **d, metric=metric, value=value, bucket=label))
@@ -72,8 +106,9 @@ def bucket_records(files, tensor_dir, stats, metric, edges):
     return records, {k: sorted(v) for k, v in lists.items()}
 
 
-def main(argv=None, measure=measure_on_gpu):
-    """`measure(dataset, n)` -> the content_entropy dict of each of the first n clips (the tests pass a numpy double)"""
+def main(argv=None, measure=measure_on_gpu, measure_motion=motion_on_gpu):
+    """`measure(dataset, n)` -> the content_entropy dict of each of the first n clips, `measure_motion(dataset, n, params)` -> the
+    motion_stats dict of each (the tests pass numpy doubles)"""
     a = parse_args(argv)
     from hunyuanvideo_efficiency_amd import metrics
     if a.yuv_format:
@@ -85,10 +120,11 @@ def main(argv=None, measure=measure_on_gpu):
     n = len(dataset) if a.max_files is None else min(len(dataset), a.max_files)
     if n == 0:
         raise SystemExit(f"no clips in {a.tensor_dir}")
-    stats = measure(dataset, n)
+    stats = measure_motion(dataset, n, a.motion_params) if a.motion else measure(dataset, n)
     records, lists = bucket_records(dataset.tensor_files[:n], a.tensor_dir, stats, a.metric, a.edges)
     os.makedirs(a.output_dir, exist_ok=True)
-    with open(os.path.join(a.output_dir, "content.jsonl"), "w") as f:
+    jsonl = os.path.join(a.output_dir, "motion.jsonl" if a.motion else "content.jsonl")
+    with open(jsonl, "w") as f:
         for r in records:
             f.write(json.dumps(r) + "\n")
     for label in metrics.content_bucket_labels(a.edges, a.metric):
@@ -98,12 +134,15 @@ def main(argv=None, measure=measure_on_gpu):
         with open(os.path.join(a.output_dir, label + ".txt"), "w") as f:
             f.write("".join(p + "\n" for p in paths))
         vals = [r["value"] for r in records if r["bucket"] == label]
-        print(f"{label}: {len(paths)} clips, mean {a.metric}-frame entropy {sum(vals) / len(vals):.4f} bits "
-              f"[{min(vals):.4f}, {max(vals):.4f}] (this project's definition)")
+        what = "motion" if a.motion else f"{a.metric}-frame entropy"
+        unit = "px/frame" if a.motion else "bits"
+        tail = "this project's own measure, not FVMD" if a.motion else "this project's definition"
+        print(f"{label}: {len(paths)} clips, mean {what} {sum(vals) / len(vals):.4f} {unit} "
+              f"[{min(vals):.4f}, {max(vals):.4f}] ({tail})")
     unbucketed = [r["name"] for r in records if r["bucket"] is None]
     if unbucketed:
-        print(f"no bucket (a single frame has no inter-frame entropy): {', '.join(unbucketed)}")
-    print(f"{len(records)} clips -> {os.path.join(a.output_dir, 'content.jsonl')}")
+        print(f"no bucket (a single frame has no inter-frame {'motion' if a.motion else 'entropy'}): {', '.join(unbucketed)}")
+    print(f"{len(records)} clips -> {jsonl}")
     return records
 
 

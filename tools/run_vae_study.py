@@ -19,6 +19,9 @@ fork's shell drivers' background batches over several cards are not reproduced.
                                         device; with --spectrum and no --fps each file name's frame rate gives the frequency axes
   ... --gssim                           each record gains "ssim3d" and "ssim2d": the Gaussian-window SSIMs of the fork's rebuttal tables
                                         (run.py's pytorch_msssim call, whose window spans frames, and calculate_ssim.py's per-frame one)
+  ... --motion [--motion-block 8|16] [--motion-radius R] [--motion-lam L]
+                                        each record gains "motion": block-matching motion of inputs and reconstructions and the end-point
+                                        error between their fields (metrics.motion_summary; this project's own measure, not FVMD)
   ... --content                         each record gains "content": inter- / intra-frame entropy, mean |difference| and TI of the inputs
                                         and of the reconstructions (metrics.content_entropy, this project's definition) and
                                         "inter_entropy_drop", the frame-to-frame detail the configuration removed; the inputs' values
@@ -56,7 +59,7 @@ def build_vae(config_json, vae_path, reduced, device):
 
 
 def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, lpips=None, spectra=None, fps=None, fvd=None,
-               input_logits=None, input_content=None, gssim=False, save_yuv=None, save_dir=None):
+               input_logits=None, input_content=None, gssim=False, save_yuv=None, save_dir=None, motion=None, input_motion=None):
     """-> the study.jsonl record of one configuration.  `fvd` (an I3D, --fvd-i3d / --fvd-synthetic): the record gains "fvd" - FVD
     (videogpt I3D logits) between the inputs and this configuration's reconstructions, None below two clips - and "fvd_clips";
     `input_logits` (a dict the caller keeps across configurations) holds every input clip's logits, which do not depend on the
@@ -65,7 +68,10 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
     across configurations, --content): the record gains "content" (metrics.content_summary); the dict holds every input clip's
     statistics, computed once.  `gssim` (--gssim): the record gains "ssim3d" and "ssim2d", the Gaussian-window SSIMs of the fork's rebuttal
     tables (metrics.gaussian_ssim), each the mean over the clips.  `save_yuv` (--save-yuv) with `save_dir`: every reconstruction is written
-    there as 8-bit YUV 4:2:0, converted on the device (video_io.save_reconstruction); the record gains "saved", the folder"""
+    there as 8-bit YUV 4:2:0, converted on the device (video_io.save_reconstruction); the record gains "saved", the folder.  `motion`
+    ({"block", "radius", "lam"}, --motion) with `input_motion` (a dict the caller keeps across configurations): the record gains "motion"
+    (metrics.motion_summary: block-matching motion of inputs and reconstructions and the end-point error between their fields, this
+    project's own measure, not FVMD); the dict holds every input clip's field, computed once"""
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator
     rec = {"config": os.path.basename(config_json)}
     try:
@@ -75,6 +81,7 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
         t_in = t_lat = 0
         reports = []
         content_jobs = []                               # (clip index or None for a reconstruction, enqueued job): one synchronisation below
+        motion_jobs = []                                # the same for the motion fields
         n = len(dataset) if max_files is None else min(len(dataset), max_files)
         for idx in range(n):
             video, file_name = dataset[idx]
@@ -94,6 +101,11 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
                 if idx not in input_content:
                     content_jobs.append((idx, metrics._content_enqueue(video[0])))
                 content_jobs.append((None, metrics._content_enqueue(recon[0])))
+            if motion is not None:
+                from hunyuanvideo_efficiency_amd import metrics
+                if idx not in input_motion:
+                    motion_jobs.append((idx, metrics._motion_enqueue(video[0], **motion)))
+                motion_jobs.append((None, metrics._motion_enqueue(recon[0], **motion)))
             if save_yuv is not None:
                 from hunyuanvideo_efficiency_amd.dataset import clip_stem
                 from hunyuanvideo_efficiency_amd.video_io import save_reconstruction
@@ -121,6 +133,13 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
             stats = metrics._content_to_host([j for _, j in content_jobs]) if content_jobs else []
             input_content.update({i: d for (i, _), d in zip(content_jobs, stats) if i is not None})
             rec["content"] = metrics.content_summary([input_content[i] for i in range(n)], [d for (i, _), d in zip(content_jobs, stats) if i is None])
+        if motion is not None:
+            from hunyuanvideo_efficiency_amd import metrics
+            fields = metrics._motion_to_host([j for _, j in motion_jobs]) if motion_jobs else []
+            input_motion.update({i: f for (i, _), f in zip(motion_jobs, fields) if i is not None})
+            recs = [f for (i, _), f in zip(motion_jobs, fields) if i is None]
+            rec["motion"] = metrics.motion_summary([metrics.motion_field_stats(input_motion[i]) for i in range(n)],
+                                                   [metrics.motion_compare_fields(input_motion[i], recs[i]) for i in range(n)])
         if spectra is not None:
             rec["spectrum"] = {f"{name}_high_band_share": (sum(r[name]["high_band_share"] for r in reports) / len(reports) if reports else None)
                                for name in ("input", "latent", "reconstruction")}
@@ -252,6 +271,8 @@ def parse_args(argv=None):
                    "of each enumerated configuration (default: what the base configuration says)")
     from hunyuanvideo_efficiency_amd.metrics import add_fvd_arguments, add_gssim_arguments, add_lpips_arguments
     add_gssim_arguments(p, csv=False)    # --gssim: each record gains "ssim3d", "ssim2d"
+    from hunyuanvideo_efficiency_amd.metrics import add_motion_arguments, motion_from_args
+    add_motion_arguments(p)              # --motion [--motion-block B] [--motion-radius R] [--motion-lam L]: each record gains "motion"
     add_lpips_arguments(p, synthetic=True)
     add_fvd_arguments(p)
     from hunyuanvideo_efficiency_amd.dataset import add_yuv_arguments, check_yuv_arguments
@@ -260,6 +281,7 @@ def parse_args(argv=None):
     add_save_yuv_argument(p)             # --save-yuv {y4m,I420,YV12,NV12}: under <output-dir>/recon_<config>/
     a = p.parse_args(argv)
     check_yuv_arguments(a, p)
+    a.motion_params = motion_from_args(a, p)
     if a.fps is not None and not ((a.spectrum or a.save_yuv) and a.fps > 0):
         p.error("--fps needs --spectrum or --save-yuv and a positive rate")
     if (a.base_config is None) == (a.config_dir is None):
@@ -299,25 +321,28 @@ def main(argv=None):
     else:
         dataset = VideoTensorDataset(a.tensor_dir)
     if a.bucket_dir is None:
-        return run_sweep(a, configs, dataset, a.output_dir, lpips, fvd, input_logits, {} if a.content else None)
+        return run_sweep(a, configs, dataset, a.output_dir, lpips, fvd, input_logits, {} if a.content else None,
+                         input_motion={} if a.motion_params else None)
     records = []
     for bucket, indices in read_bucket_lists(a.bucket_dir, dataset.tensor_files):
         print(f"bucket {bucket}: {len(indices)} clips")
         sub_dir = os.path.join(a.output_dir, bucket)
         os.makedirs(sub_dir, exist_ok=True)
         # the caches are keyed by the position in the subset: one pair per bucket
-        records += run_sweep(a, configs, ClipSubset(dataset, indices), sub_dir, lpips, fvd, {}, {} if a.content else None, bucket)
+        records += run_sweep(a, configs, ClipSubset(dataset, indices), sub_dir, lpips, fvd, {}, {} if a.content else None, bucket,
+                             {} if a.motion_params else None)
     return records
 
 
-def run_sweep(a, configs, dataset, output_dir, lpips, fvd, input_logits, input_content, bucket=None):
+def run_sweep(a, configs, dataset, output_dir, lpips, fvd, input_logits, input_content, bucket=None, input_motion=None):
     """every configuration on `dataset` -> <output_dir>/study.jsonl; `bucket`: the label every record carries"""
     out =os.path.join(output_dir, "study.jsonl")
     records = []
     for cfg in configs:
         spectra = {} if a.spectrum else None
         rec = run_config(cfg, dataset, a.vae_path, a.reduced, "cuda", a.max_files, lpips, spectra, a.fps, fvd, input_logits, input_content, a.gssim,
-                         a.save_yuv, os.path.join(output_dir, f"recon_{os.path.splitext(os.path.basename(cfg))[0]}"))
+                         a.save_yuv, os.path.join(output_dir, f"recon_{os.path.splitext(os.path.basename(cfg))[0]}"),
+                         getattr(a, "motion_params", None), input_motion)
         if bucket is not None:
             rec["bucket"] = bucket
         if spectra:
