@@ -68,3 +68,10 @@ if not os.path.exists(MOTION_HEADER):
     raise HVKernelError(f"{MOTION_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
 with open(MOTION_HEADER) as _f:
     MOTION_DECLS, MOTION_MACROS = parse(_f.read())
+
+# include/hv_mjpeg.h: video tensor -> baseline JPEG frames (csrc/hv_mjpeg.hip), declared and parsed the same way
+MJPEG_HEADER = os.path.join(os.path.dirname(HEADER), "hv_mjpeg.h")
+if not os.path.exists(MJPEG_HEADER):
+    raise HVKernelError(f"{MJPEG_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
+with open(MJPEG_HEADER) as _f:
+    MJPEG_DECLS, MJPEG_MACROS = parse(_f.read())

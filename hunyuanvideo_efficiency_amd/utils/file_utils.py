@@ -34,10 +34,16 @@ def frames_uint8(videos: torch.Tensor, rescale: bool = False, n_rows: int = 1):
     return outs
 
 
-def save_videos_grid(videos: torch.Tensor, path: str, rescale: bool = False, n_rows: int = 1, fps: int = 24, chroma: str = "mean") -> str:
+def save_videos_grid(videos: torch.Tensor, path: str, rescale: bool = False, n_rows: int = 1, fps: int = 24, chroma: str = "mean",
+                     quality: int = None) -> str:
     """Returns the path actually written (the extension changes when no mp4 writer is available).  A path ending in `.y4m` or `.yuv`
     with a GPU tensor takes the GPU route (video_io.save_videos_yuv: 8-bit YUV 4:2:0 from the same uint8 frames, `chroma` as
-    video_io.clip_to_yuv takes it; a ValueError for an odd grid size); every other call is what it was."""
+    video_io.clip_to_yuv takes it; a ValueError for an odd grid size), one ending in `.avi` the Motion-JPEG route
+    (mjpeg_io.save_videos_mjpeg: JPEG frames of the same uint8 frames at `quality`, default 90; any grid size); every other call is what
+    it was."""
+    if path.endswith(".avi") and isinstance(videos, torch.Tensor) and videos.is_cuda:
+        from ..mjpeg_io import DEFAULT_QUALITY, save_videos_mjpeg
+        return save_videos_mjpeg(videos, path, rescale, n_rows, fps, DEFAULT_QUALITY if quality is None else quality)
     if path.endswith((".y4m", ".yuv")) and isinstance(videos, torch.Tensor) and videos.is_cuda:
         from ..video_io import save_videos_yuv
         return save_videos_yuv(videos, path, rescale, n_rows, fps, chroma=chroma)

@@ -6,7 +6,9 @@ tensors and checkpoints are read with torch.load(weights_only=True) only.  With 
 of raw planar YUV 4:2:0 files instead, converted to clips on the GPU (hunyuanvideo_efficiency_amd/dataset.py; --target-height,
 --start-frame, --end-frame as dataset_processor/yuv_tensor.py takes them); outputs keep the input file's stem.  With --save-yuv
 {y4m,I420,YV12,NV12} every reconstruction is also written as 8-bit YUV 4:2:0, converted on the GPU
-(hunyuanvideo_efficiency_amd/video_io.py), under a name that --yuv-format reads back.  Without --vae-path
+(hunyuanvideo_efficiency_amd/video_io.py), under a name that --yuv-format reads back; with --save-mjpeg [--save-quality Q]
+[--save-strip N] as <name>.avi, Motion-JPEG coded on the GPU (hunyuanvideo_efficiency_amd/mjpeg_io.py; lossy, for people to look at,
+never read back), and <name>_strip.jpg, N evenly spaced frames side by side.  Without --vae-path
 the VAE gets deterministic synthetic weights (there are no checkpoints in this environment): the plumbing and the kernels are what is
 exercised.  With --score --motion [--motion-block 8|16] [--motion-radius R] [--motion-lam L] every clip also gets <name>_motion.json:
 block-matching motion of input and reconstruction (metrics.motion_compare; this project's own measure, not FVMD)."""
@@ -33,7 +35,7 @@ class VideoTensorDataset:
 
 
 def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, scorer=None, save=True, spectrum_dir=None, fps=None,
-              content_dir=None, save_yuv=None, motion_dir=None, motion=None):
+              content_dir=None, save_yuv=None, motion_dir=None, motion=None, mjpeg=None):
     """Reconstructs the first `max_files` tensors, `batch_size` at a time (tensors of one batch must have equal shapes, as a
     DataLoader's default collate requires); every input still gets its own <name>.pt of shape [1, C, T, H, W].
     `scorer` (a metrics.MetricsAccumulator): each reconstruction is scored against its input while both are on the device
@@ -47,6 +49,8 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
     `save_yuv` ("y4m" | "I420" | "YV12" | "NV12"): every reconstruction is also written as 8-bit YUV 4:2:0, converted on the device
     (video_io.save_reconstruction), whatever `save` says: <name>.y4m or <name>_<n>fps_<w>x<h>.yuv, at the input file's rate, else `fps`,
     else 24; their paths are returned too.
+    `mjpeg` ({"quality", "strip"}): every reconstruction is also written as <name>.avi (mjpeg_io.save_reconstruction_mjpeg), and as
+    <name>_strip.jpg when "strip" is a frame count, at the same rate, whatever `save` says; their paths are returned too.
     `motion_dir` with `motion` ({"block", "radius", "lam"}): also write <name>_motion.json there per input - the dict of
     metrics.motion_compare (block-matching motion of input and reconstruction, the end-point error between the two fields; this project's
     own measure, not FVMD)."""
@@ -119,6 +123,12 @@ def infer_vae(model, dataset, device, output_dir, max_files=None, batch_size=1, 
                 rate = file_fps.get(items[b][1], fps)
                 done.append(save_reconstruction(recon[b], output_dir, name, save_yuv, rate))
                 print(f"Saved reconstructed video to {done[-1]}, {recon.shape[2]} frames of {recon.shape[4]} x {recon.shape[3]}")
+        if mjpeg is not None:
+            from hunyuanvideo_efficiency_amd.mjpeg_io import save_reconstruction_mjpeg
+            for b, name in enumerate(names):
+                for path in save_reconstruction_mjpeg(recon[b], output_dir, name, file_fps.get(items[b][1], fps), mjpeg["quality"], mjpeg["strip"]):
+                    done.append(path)
+                    print(f"Saved reconstructed video to {path}, {recon.shape[2]} frames of {recon.shape[4]} x {recon.shape[3]}")
         if not save:
             continue
         recon = recon.cpu().float()
@@ -156,7 +166,7 @@ def parse_args(argv=None):
     p.add_argument("--spectrum", action="store_true", help="with --score: write <name>_spectrum.json per clip into the results directory - "
                                                           "temporal spectra of input, latent and reconstruction and their high-band shares")
     p.add_argument("--fps", type=float, default=None, help="with --spectrum: frame rate of the clips, adds the frequency axes; with "
-                                                           "--save-yuv: the rate written (default with --yuv-format: the rate in each "
+                                                           "--save-yuv / --save-mjpeg: the rate written (default with --yuv-format: the rate in each "
                                                            "file's name)")
     p.add_argument("--content", action="store_true", help="with --score: write <name>_content.json per clip into the results directory - "
                                                          "inter- / intra-frame entropy of input and reconstruction (this project's definition)")
@@ -167,8 +177,12 @@ def parse_args(argv=None):
     add_yuv_arguments(p)                 # --yuv-format {I420,NV12,YV12} [--target-height N] [--start-frame A] [--end-frame B]
     from hunyuanvideo_efficiency_amd.video_io import add_save_yuv_argument
     add_save_yuv_argument(p)             # --save-yuv {y4m,I420,YV12,NV12}
+    from hunyuanvideo_efficiency_amd.mjpeg_io import add_save_mjpeg_arguments, check_save_mjpeg_arguments
+    add_save_mjpeg_arguments(p)          # --save-mjpeg [--save-quality Q] [--save-strip N]
     a = p.parse_args(argv)
     check_yuv_arguments(a, p)
+    quality = check_save_mjpeg_arguments(p, a)
+    a.mjpeg_params = dict(quality=quality, strip=a.save_strip) if a.save_mjpeg else None
     if a.spectrum and not a.score:
         p.error("--spectrum is only valid with --score")
     if a.content and not a.score:
@@ -178,8 +192,8 @@ def parse_args(argv=None):
         p.error("--motion is only valid with --score")
     if (a.gssim or a.metrics_csv) and not a.score:
         p.error("--gssim and --metrics-csv are only valid with --score")
-    if a.fps is not None and not (a.spectrum or a.save_yuv):
-        p.error("--fps is only valid with --spectrum or --save-yuv")
+    if a.fps is not None and not (a.spectrum or a.save_yuv or a.save_mjpeg):
+        p.error("--fps is only valid with --spectrum, --save-yuv or --save-mjpeg")
     if a.fps is not None and not a.fps > 0:
         p.error("--fps must be positive")
     if (a.lpips_alexnet or a.lpips_linear or a.lpips_synthetic) and not a.score:
@@ -192,8 +206,8 @@ def parse_args(argv=None):
         p.error("--fvd-* flags are only valid with --score")
     if a.fvd_i3d and a.fvd_synthetic:
         p.error("--fvd-synthetic and --fvd-i3d exclude each other")
-    if a.no_save and not (a.score or a.save_yuv):
-        p.error("--no-save is only valid with --score or --save-yuv (nothing would be produced)")
+    if a.no_save and not (a.score or a.save_yuv or a.save_mjpeg):
+        p.error("--no-save is only valid with --score, --save-yuv or --save-mjpeg (nothing would be produced)")
     if a.results_dir and not a.score:
         p.error("--results-dir is only valid with --score")
     return a
@@ -220,12 +234,13 @@ def main(argv=None):
     else:
         dataset = VideoTensorDataset(a.tensor_dir)
     if not a.score:
-        return infer_vae(vae, dataset, device, a.output_dir, a.max_files, a.batch_size, save=not a.no_save, fps=a.fps, save_yuv=a.save_yuv)
+        return infer_vae(vae, dataset, device, a.output_dir, a.max_files, a.batch_size, save=not a.no_save, fps=a.fps, save_yuv=a.save_yuv,
+                         mjpeg=a.mjpeg_params)
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator, fvd_from_args, lpips_from_args
     scorer = MetricsAccumulator(lpips=lpips_from_args(a), fvd=fvd_from_args(a, score=a.score), gssim=a.gssim, csv=bool(a.metrics_csv))
     done = infer_vae(vae, dataset, device, a.output_dir, a.max_files, a.batch_size, scorer, not a.no_save,
                      (a.results_dir or a.output_dir) if a.spectrum else None, a.fps, (a.results_dir or a.output_dir) if a.content else None,
-                     a.save_yuv, (a.results_dir or a.output_dir) if a.motion_params else None, a.motion_params)
+                     a.save_yuv, (a.results_dir or a.output_dir) if a.motion_params else None, a.motion_params, a.mjpeg_params)
     results = scorer.result()
     print(f"Results over {scorer.frames} frames: {results}" + (" (LPIPS under synthetic weights: not comparable with published LPIPS)"
                                                                if a.lpips_synthetic else "") + scorer.fvd_note())

@@ -67,14 +67,20 @@ def parse_args(argv=None):
     p.add_argument("--apply-final-norm", action="store_true")
     p.add_argument("--tiny", action="store_true", help="tiny DiT (d=256, 1+1 blocks) and reduced VAE: plumbing check")
     p.add_argument("--save-path", default="./results")
-    p.add_argument("--save-format", choices=["auto", "y4m", "yuv"], default="auto", help="auto: mp4 through imageio where it exists, else "
+    p.add_argument("--save-format", choices=["auto", "y4m", "yuv", "avi"], default="auto", help="auto: mp4 through imageio where it exists, else "
                    "GIF / .npy (save_videos_grid); y4m | yuv: 8-bit YUV 4:2:0 converted on the GPU (the video never leaves it as floats) - "
-                   "a YUV4MPEG2 file any player opens, or a raw I420 <name>_24fps_<w>x<h>.yuv")
+                   "a YUV4MPEG2 file any player opens, or a raw I420 <name>_24fps_<w>x<h>.yuv; avi: Motion-JPEG coded on the GPU, about a "
+                   "tenth of the .y4m (lossy: for people to look at)")
     p.add_argument("--save-chroma", choices=["mean", "topleft"], default=None, help="with --save-format y4m | yuv: chroma of a 2x2 block "
                    "from the four pixels' mean (default) or from its top-left pixel, as OpenCV's COLOR_RGB2YUV_I420 takes it")
+    p.add_argument("--save-quality", type=int, default=None, help="with --save-format avi: JPEG quality 1 .. 100 (default 90)")
     a = p.parse_args(argv)
-    if a.save_chroma is not None and a.save_format == "auto":
+    if a.save_chroma is not None and a.save_format not in ("y4m", "yuv"):
         p.error("--save-chroma is only valid with --save-format y4m or yuv")
+    if a.save_quality is not None and a.save_format != "avi":
+        p.error("--save-quality is only valid with --save-format avi")
+    if a.save_quality is not None and not 1 <= a.save_quality <= 100:
+        p.error(f"--save-quality is 1 .. 100, got {a.save_quality}")
     return a
 
 
@@ -169,7 +175,7 @@ def main(argv=None):
                   embedded_guidance_scale=a.embedded_cfg_scale if cfg.guidance_embed else None, generator=gen, freqs_cis=freqs, vae_ver=a.vae,
                   enable_tiling=a.vae_tiling, n_tokens=freqs[0].shape[0], num_videos_per_prompt=a.num_videos)
     to_yuv = a.save_format != "auto"
-    if to_yuv:                 # the video stays on the card: video_io converts it there and only bytes cross to the host
+    if to_yuv:                 # the video stays on the card: video_io / mjpeg_io convert it there and only bytes cross to the host
         common["return_on_device"] = True
     if a.prompt is not None:
         # without a CLIP encoder the pooled vectors are synthetic, the negative one included (the CFG batch needs both)
@@ -186,7 +192,7 @@ def main(argv=None):
     if rank == 0:
         v = out.videos
         ext = a.save_format if to_yuv else "mp4"
-        save_kw = dict(chroma=a.save_chroma or "mean") if to_yuv else {}
+        save_kw = dict(quality=a.save_quality) if a.save_format == "avi" else dict(chroma=a.save_chroma or "mean") if to_yuv else {}
         print(f"Success, time: {dt:.2f} s; video tensor {tuple(v.shape)} {v.dtype} range [{float(v.min()):.3f}, {float(v.max()):.3f}]")
         os.makedirs(a.save_path, exist_ok=True)
         from hunyuanvideo_efficiency_amd.utils.file_utils import save_videos_grid

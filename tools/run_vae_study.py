@@ -59,7 +59,8 @@ def build_vae(config_json, vae_path, reduced, device):
 
 
 def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, lpips=None, spectra=None, fps=None, fvd=None,
-               input_logits=None, input_content=None, gssim=False, save_yuv=None, save_dir=None, motion=None, input_motion=None):
+               input_logits=None, input_content=None, gssim=False, save_yuv=None, save_dir=None, motion=None, input_motion=None,
+               mjpeg=None):
     """-> the study.jsonl record of one configuration.  `fvd` (an I3D, --fvd-i3d / --fvd-synthetic): the record gains "fvd" - FVD
     (videogpt I3D logits) between the inputs and this configuration's reconstructions, None below two clips - and "fvd_clips";
     `input_logits` (a dict the caller keeps across configurations) holds every input clip's logits, which do not depend on the
@@ -71,7 +72,9 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
     there as 8-bit YUV 4:2:0, converted on the device (video_io.save_reconstruction); the record gains "saved", the folder.  `motion`
     ({"block", "radius", "lam"}, --motion) with `input_motion` (a dict the caller keeps across configurations): the record gains "motion"
     (metrics.motion_summary: block-matching motion of inputs and reconstructions and the end-point error between their fields, this
-    project's own measure, not FVMD); the dict holds every input clip's field, computed once"""
+    project's own measure, not FVMD); the dict holds every input clip's field, computed once.  `mjpeg` ({"quality", "strip"},
+    --save-mjpeg) with `save_dir`: every reconstruction is written there as <name>.avi, Motion-JPEG coded on the device
+    (mjpeg_io.save_reconstruction_mjpeg), and as <name>_strip.jpg when "strip" is a frame count; the record gains "saved" as well"""
     from hunyuanvideo_efficiency_amd.metrics import MetricsAccumulator
     rec = {"config": os.path.basename(config_json)}
     try:
@@ -111,6 +114,12 @@ def run_config(config_json, dataset, vae_path, reduced, device, max_files=None, 
                 from hunyuanvideo_efficiency_amd.video_io import save_reconstruction
                 # the input file's rate first, as infer.py does
                 save_reconstruction(recon[0], save_dir, clip_stem(file_name), save_yuv, getattr(dataset, "fps", {}).get(file_name, fps))
+                rec["saved"] = save_dir
+            if mjpeg is not None:         # --save-mjpeg: <name>.avi (and <name>_strip.jpg) in the same folder, at the same rate
+                from hunyuanvideo_efficiency_amd.dataset import clip_stem
+                from hunyuanvideo_efficiency_amd.mjpeg_io import save_reconstruction_mjpeg
+                save_reconstruction_mjpeg(recon[0], save_dir, clip_stem(file_name), getattr(dataset, "fps", {}).get(file_name, fps),
+                                          mjpeg["quality"], mjpeg["strip"])
                 rec["saved"] = save_dir
             t_in += video.shape[2]
             t_lat += z.shape[2]
@@ -261,7 +270,8 @@ def parse_args(argv=None):
     p.add_argument("--reduced", action="store_true", help="synthetic-weight mode only: reduced channel widths")
     p.add_argument("--spectrum", action="store_true", help="temporal spectra of input, latent and reconstruction: each record gains "
                    "\"spectrum\" (three high-band shares, averaged over clips), each configuration a spectra_<config>.json")
-    p.add_argument("--fps", type=float, default=None, help="with --spectrum: frame rate of the clips, adds the frequency axes")
+    p.add_argument("--fps", type=float, default=None, help="with --spectrum: frame rate of the clips, adds the frequency axes; with "
+                   "--save-yuv / --save-mjpeg: the rate written where the input file names none")
     p.add_argument("--content", action="store_true", help="content statistics of inputs and reconstructions: each record gains \"content\" "
                    "(inter- / intra-frame entropy, this project's definition, mean |difference|, TI, and the inter-frame entropy the "
                    "configuration removed)")
@@ -279,11 +289,15 @@ def parse_args(argv=None):
     add_yuv_arguments(p)
     from hunyuanvideo_efficiency_amd.video_io import add_save_yuv_argument
     add_save_yuv_argument(p)             # --save-yuv {y4m,I420,YV12,NV12}: under <output-dir>/recon_<config>/
+    from hunyuanvideo_efficiency_amd.mjpeg_io import add_save_mjpeg_arguments, check_save_mjpeg_arguments
+    add_save_mjpeg_arguments(p)          # --save-mjpeg [--save-quality Q] [--save-strip N]: <name>.avi, <name>_strip.jpg in the same folder
     a = p.parse_args(argv)
     check_yuv_arguments(a, p)
     a.motion_params = motion_from_args(a, p)
-    if a.fps is not None and not ((a.spectrum or a.save_yuv) and a.fps > 0):
-        p.error("--fps needs --spectrum or --save-yuv and a positive rate")
+    quality = check_save_mjpeg_arguments(p, a)
+    a.mjpeg_params = dict(quality=quality, strip=a.save_strip) if a.save_mjpeg else None
+    if a.fps is not None and not ((a.spectrum or a.save_yuv or a.save_mjpeg) and a.fps > 0):
+        p.error("--fps needs --spectrum, --save-yuv or --save-mjpeg and a positive rate")
     if (a.base_config is None) == (a.config_dir is None):
         p.error("give exactly one of --base-config (enumerate) or --config-dir (ready-made configurations)")
     if a.interp_mode is not None and a.base_config is None:
@@ -342,7 +356,7 @@ def run_sweep(a, configs, dataset, output_dir, lpips, fvd, input_logits, input_c
         spectra = {} if a.spectrum else None
         rec = run_config(cfg, dataset, a.vae_path, a.reduced, "cuda", a.max_files, lpips, spectra, a.fps, fvd, input_logits, input_content, a.gssim,
                          a.save_yuv, os.path.join(output_dir, f"recon_{os.path.splitext(os.path.basename(cfg))[0]}"),
-                         getattr(a, "motion_params", None), input_motion)
+                         getattr(a, "motion_params", None), input_motion, getattr(a, "mjpeg_params", None))
         if bucket is not None:
             rec["bucket"] = bucket
         if spectra:
