@@ -4,7 +4,8 @@ sub-folder per experiment, its compute_metrics_threads.py; the kernel needs no t
 
 Files are paired by name.  `.pt` (torch.load(weights_only=True); [C,T,H,W] or [1,C,T,H,W], values in [-1, 1] as infer.py writes
 them) and `.npy` (the same layouts, or uint8 frames [T,H,W,C] as save_videos_grid's fallback writes them) are read directly; `.mp4`
-only if imageio is importable - otherwise an .mp4 pair is an error, not a silent skip.  Scores are per frame over the common frames
+only if imageio is importable - otherwise an .mp4 pair is an error, not a silent skip; `.avi` (Motion-JPEG, what --save-mjpeg writes) is
+decoded on the GPU (mjpeg_io.read_mjpeg_clip) to the bytes a player shows and scored like other uint8 frames.  Scores are per frame over the common frames
 and averaged over all frames of all pairs; the result file has the reference's lines.  LPIPS (AlexNet, the reference's
 compute_lpips) is scored only with --lpips-alexnet PATH [--lpips-linear PATH]: the weights are user-supplied (a torchvision AlexNet
 state dict plus the LPIPS linear file, or one full LPIPS state dict), none are shipped or fetched; without them the result file has no
@@ -24,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-EXTS = (".pt", ".npy", ".mp4")
+EXTS = (".pt", ".npy", ".mp4", ".avi")
 
 
 def parse_args(argv=None):
@@ -58,8 +59,11 @@ def pair_files(root1, root2):
 
 
 def read_video(path):
-    """-> (tensor [C,T,H,W] on the host, rescale): float videos are in [-1, 1] (rescale=True), uint8 frames become [0, 1] floats"""
+    """-> (tensor [C,T,H,W] on the host (an .avi: on the GPU), rescale): float videos are in [-1, 1] (rescale=True), uint8 frames become [0, 1] floats"""
     ext = os.path.splitext(path)[1]
+    if ext == ".avi":                                   # decoded on the device to byte / 255, the floats of the uint8 branch below
+        from hunyuanvideo_efficiency_amd.mjpeg_io import read_mjpeg_clip
+        return read_mjpeg_clip(path, "cuda", dtype=torch.float32, unit=True)[0], False
     if ext == ".pt":
         x = torch.load(path, map_location="cpu", weights_only=True)
     elif ext == ".npy":

@@ -287,6 +287,42 @@ class YuvClipDataset:
         return clip, name
 
 
+class MjpegClipDataset:
+    """The surface of YuvClipDataset over a folder of Motion-JPEG `.avi` files (what --save-mjpeg / write_mjpeg_clip write, or any AVI 1.0
+    of baseline 4:2:0 JPEG frames): sorted names, `ds[i]` -> (clip [3,T,H,W] on the device in [-1, 1], file name), decoded on the GPU
+    (mjpeg_io.read_mjpeg_clip).  A file that does not parse or has no frame in [start, end) is skipped with a printed line.
+    `fps[name]` holds each file's frame rate."""
+
+    def __init__(self, video_dir, device="cuda", start=None, end=None, dtype=torch.float16, frames_per_chunk=None):
+        from .mjpeg_io import mjpeg_frame_range, parse_avi
+        self.tensor_dir, self.device, self.start, self.end = video_dir, device, start, end
+        self.dtype, self.frames_per_chunk = dtype, frames_per_chunk
+        self.tensor_files, self.fps, self.skipped = [], {}, []
+        for name in sorted(f for f in os.listdir(video_dir) if f.endswith(".avi")):
+            try:
+                W, H, fps, index = parse_avi(os.path.join(video_dir, name))
+            except ValueError as e:
+                print(f"Skipping {name}: {e}")
+                self.skipped.append(name)
+                continue
+            first, last = mjpeg_frame_range(len(index), start, end)
+            if last <= first:
+                print(f"Skipping {name}: no frame in range")
+                self.skipped.append(name)
+                continue
+            self.tensor_files.append(name)
+            self.fps[name] = fps
+
+    def __len__(self):
+        return len(self.tensor_files)
+
+    def __getitem__(self, idx):
+        from .mjpeg_io import read_mjpeg_clip
+        name = self.tensor_files[idx]
+        clip, _ = read_mjpeg_clip(os.path.join(self.tensor_dir, name), self.device, self.start, self.end, self.dtype, self.frames_per_chunk)
+        return clip, name
+
+
 def add_yuv_arguments(parser):
     """--yuv-format and the flags valid only with it"""
     parser.add_argument("--yuv-format", choices=sorted(YUV_FORMATS), default=None, help="read --tensor-dir as a folder of raw planar YUV "
@@ -297,6 +333,14 @@ def add_yuv_arguments(parser):
 
 
 def check_yuv_arguments(args, parser):
+    if getattr(args, "mjpeg_input", False):          # --mjpeg-input (mjpeg_io.add_mjpeg_input_arguments): frames may be selected, nothing else
+        if args.yuv_format is not None:
+            parser.error("--mjpeg-input and --yuv-format are two ways to read --tensor-dir: give one")
+        if args.target_height is not None:
+            parser.error("--target-height is only valid with --yuv-format")
+        if (args.start_frame is not None and args.start_frame < 0) or (args.end_frame is not None and args.end_frame < 0):
+            parser.error("--start-frame and --end-frame are non-negative")
+        return
     if args.yuv_format is None:
         for flag in ("target_height", "start_frame", "end_frame"):
             if getattr(args, flag) is not None:
@@ -309,10 +353,13 @@ def check_yuv_arguments(args, parser):
 
 
 def dataset_from_args(args, device="cuda"):
-    """the YuvClipDataset the flags of add_yuv_arguments ask for (fp16 clips, what the drivers feed the VAE)"""
+    """the YuvClipDataset the flags of add_yuv_arguments ask for (fp16 clips, what the drivers feed the VAE); with --mjpeg-input the
+    MjpegClipDataset"""
+    if getattr(args, "mjpeg_input", False):
+        return MjpegClipDataset(args.tensor_dir, device, args.start_frame, args.end_frame)
     return YuvClipDataset(args.tensor_dir, device, args.yuv_format, args.start_frame, args.end_frame, args.target_height)
 
 
 def clip_stem(file_name: str) -> str:
     """the name a driver's outputs carry: the input file's stem"""
-    return file_name[:-len(".yuv")] if file_name.endswith((".yuv", ".y4m")) else file_name.replace(".pt", "")
+    return file_name[:-len(".yuv")] if file_name.endswith((".yuv", ".y4m", ".avi")) else file_name.replace(".pt", "")

@@ -7,8 +7,8 @@ of raw planar YUV 4:2:0 files instead, converted to clips on the GPU (hunyuanvid
 --start-frame, --end-frame as dataset_processor/yuv_tensor.py takes them); outputs keep the input file's stem.  With --save-yuv
 {y4m,I420,YV12,NV12} every reconstruction is also written as 8-bit YUV 4:2:0, converted on the GPU
 (hunyuanvideo_efficiency_amd/video_io.py), under a name that --yuv-format reads back; with --save-mjpeg [--save-quality Q]
-[--save-strip N] as <name>.avi, Motion-JPEG coded on the GPU (hunyuanvideo_efficiency_amd/mjpeg_io.py; lossy, for people to look at,
-never read back), and <name>_strip.jpg, N evenly spaced frames side by side.  Without --vae-path
+[--save-strip N] as <name>.avi, Motion-JPEG coded on the GPU (hunyuanvideo_efficiency_amd/mjpeg_io.py; lossy), and <name>_strip.jpg, N evenly spaced frames side by side; with --mjpeg-input
+[--start-frame A] [--end-frame B] --tensor-dir is a folder of such .avi files, decoded on the GPU.  Without --vae-path
 the VAE gets deterministic synthetic weights (there are no checkpoints in this environment): the plumbing and the kernels are what is
 exercised.  With --score --motion [--motion-block 8|16] [--motion-radius R] [--motion-lam L] every clip also gets <name>_motion.json:
 block-matching motion of input and reconstruction (metrics.motion_compare; this project's own measure, not FVMD)."""
@@ -179,6 +179,8 @@ def parse_args(argv=None):
     add_save_yuv_argument(p)             # --save-yuv {y4m,I420,YV12,NV12}
     from hunyuanvideo_efficiency_amd.mjpeg_io import add_save_mjpeg_arguments, check_save_mjpeg_arguments
     add_save_mjpeg_arguments(p)          # --save-mjpeg [--save-quality Q] [--save-strip N]
+    from hunyuanvideo_efficiency_amd.mjpeg_io import add_mjpeg_input_arguments
+    add_mjpeg_input_arguments(p)         # --mjpeg-input [--start-frame A] [--end-frame B]: --tensor-dir holds .avi files
     a = p.parse_args(argv)
     check_yuv_arguments(a, p)
     quality = check_save_mjpeg_arguments(p, a)
@@ -228,7 +230,7 @@ def main(argv=None):
         if a.config_json:
             from hunyuanvideo_efficiency_amd.vae import _apply_t_ops_config_to_vae, load_t_ops_config
             _apply_t_ops_config_to_vae(vae, load_t_ops_config(a.config_json))
-    if a.yuv_format:
+    if a.yuv_format or a.mjpeg_input:
         from hunyuanvideo_efficiency_amd.dataset import dataset_from_args
         dataset = dataset_from_args(a, device)
     else:

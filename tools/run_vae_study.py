@@ -291,6 +291,8 @@ def parse_args(argv=None):
     add_save_yuv_argument(p)             # --save-yuv {y4m,I420,YV12,NV12}: under <output-dir>/recon_<config>/
     from hunyuanvideo_efficiency_amd.mjpeg_io import add_save_mjpeg_arguments, check_save_mjpeg_arguments
     add_save_mjpeg_arguments(p)          # --save-mjpeg [--save-quality Q] [--save-strip N]: <name>.avi, <name>_strip.jpg in the same folder
+    from hunyuanvideo_efficiency_amd.mjpeg_io import add_mjpeg_input_arguments
+    add_mjpeg_input_arguments(p)         # --mjpeg-input [--start-frame A] [--end-frame B]: --tensor-dir holds .avi files
     a = p.parse_args(argv)
     check_yuv_arguments(a, p)
     a.motion_params = motion_from_args(a, p)
@@ -329,7 +331,7 @@ def main(argv=None):
     else:
         configs = [os.path.join(a.config_dir, f) for f in sorted((f for f in os.listdir(a.config_dir) if f.endswith(".json")), key=_exp_order)]
         configs = configs[:a.limit] if a.limit is not None else configs
-    if a.yuv_format:
+    if a.yuv_format or a.mjpeg_input:
         from hunyuanvideo_efficiency_amd.dataset import dataset_from_args
         dataset = ConvertedOnce(dataset_from_args(a, "cuda"))
     else:
