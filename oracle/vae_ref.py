@@ -40,6 +40,12 @@ class Prec:
 FP32 = Prec(False)
 
 
+def _wide(x: Tensor) -> Tensor:
+    """the working precision of the norms and the attention: fp32 for every input dtype but fp64, which is kept (with Prec(False) and fp64
+    inputs and weights the whole oracle then runs in fp64)"""
+    return x if x.dtype == torch.float64 else x.float()
+
+
 def causal_conv3d(x: Tensor, w: Tensor, b: Optional[Tensor], p: Prec) -> Tensor:
     """CausalConv3d.forward, vae/unet_causal_3d_blocks.py:61-75: replicate pad (W k//2,k//2; H k//2,k//2; T k-1,0)
     then Conv3d stride 1."""
@@ -50,7 +56,8 @@ def causal_conv3d(x: Tensor, w: Tensor, b: Optional[Tensor], p: Prec) -> Tensor:
 
 def group_norm_silu(x: Tensor, w: Tensor, b: Tensor, groups: int = 32, eps: float = 1e-6, silu: bool = True) -> Tensor:
     """nn.GroupNorm(32, C, eps=1e-6, affine) [+ SiLU]: unet_causal_3d_blocks.py:302,323,361-363,399-405; fp32."""
-    y = F.group_norm(x.float(), groups, w.float(), b.float(), eps)
+    x = _wide(x)
+    y = F.group_norm(x, groups, w.to(x.dtype), b.to(x.dtype), eps)
     return F.silu(y) if silu else y
 
 
@@ -90,8 +97,9 @@ def mid_attention(sd, pre: str, x: Tensor, p: Prec) -> Tensor:
     PARITY UNPINNED).  x: [B,C,T,H,W]."""
     B, C, T, H, W = x.shape
     tok = x.permute(0, 2, 3, 4, 1).reshape(B, T * H * W, C)
-    n = F.group_norm(tok.float().transpose(1, 2), 32, sd[pre + "group_norm.weight"].float(),
-                     sd[pre + "group_norm.bias"].float(), 1e-6).transpose(1, 2)
+    tokw = _wide(tok)
+    n = F.group_norm(tokw.transpose(1, 2), 32, sd[pre + "group_norm.weight"].to(tokw.dtype),
+                     sd[pre + "group_norm.bias"].to(tokw.dtype), 1e-6).transpose(1, 2)
     lin = lambda t, name: p.r(F.linear(p.r(t), p.r(sd[pre + name + ".weight"]), p.r(sd[pre + name + ".bias"])))
     q, k, v = lin(n, "to_q"), lin(n, "to_k"), lin(n, "to_v")
     s = torch.matmul(q, k.transpose(1, 2)) * (1.0 / math.sqrt(C))

@@ -349,6 +349,171 @@ def install_vae_mid_attention(monkeypatch, softmax_mutant=None):
     return vae_ops
 
 
+# ---- the rest of the VAE tile coder (AutoencoderKLCausal3D._decode_tile / _encode_tile): the unit-stride conv with its fused nearest
+# upsample, residual and GroupNorm statistics, the sub-pixel upsampler conv, the temporal ops, latent_tile and copy4d_, with the rounding
+# points include/hv_kernels.h documents, so that the whole tile coder runs on device="cpu" (tests/test_vae_wiring_cpu.py)
+def gn_stats_of(y):
+    """the statistics a conv epilogue leaves for the fp16 tensor y [M, C] it stored, as ONE partial row in the documented entry format
+    (include/hv_kernels.h, gn_partial): per pair of adjacent columns (c, c + 1), c even, over the k = 2 M values: [c] = (S = sum, C2 = sum
+    of (x - S / k)^2), [c + 1] = (0, k) - a vae_ops.GNStats with rows = 1, which vae_groupnorm_affine_from_stats folds"""
+    from hunyuanvideo_efficiency_amd.vae_ops import GNStats
+    m, c = y.shape
+    pair = y.double().reshape(m, c // 2, 2)
+    k = 2.0 * m
+    s = pair.sum((0, 2))
+    c2 = ((pair - (s / k)[None, :, None]) ** 2).sum((0, 2))
+    partial = torch.zeros(1, c, 2, dtype=torch.float32)
+    partial[0, 0::2, 0], partial[0, 0::2, 1], partial[0, 1::2, 1] = s.float(), c2.float(), k
+    return GNStats(partial, 1, m, c)
+
+
+def vae_groupnorm_affine_from_stats(st, weight, bias, groups=32, eps=1e-6):
+    """hv_groupnorm_finalize_f16: sum x^2 of an entry = C2 + S^2 / k, folded in fp64; sc = fp32(rstd w), sh = fp32(b - mean sc)"""
+    c = st.C
+    cpg = c // groups
+    assert cpg % 2 == 0, "the epilogue credits each pair of adjacent channels to the even one"
+    p = st.partial.reshape(st.rows, c, 2).double()
+    s, c2, k = p[:, 0::2, 0], p[:, 0::2, 1], p[:, 1::2, 1]
+    q = c2 + torch.where(k > 0, s * s / k.clamp(min=1.0), torch.zeros_like(s))
+    n = float(st.M * cpg)
+    sg, qg = s.sum(0).reshape(groups, cpg // 2).sum(-1), q.sum(0).reshape(groups, cpg // 2).sum(-1)
+    mean = sg / n
+    var = (qg / n - mean * mean).clamp(min=0.0)
+    rstd = 1.0 / torch.sqrt(var + float(torch.tensor(eps, dtype=torch.float32)))
+    sc = (rstd.repeat_interleave(cpg) * weight.double()).float()
+    sh = (bias.double() - mean.repeat_interleave(cpg) * sc.double()).float()
+    return torch.stack([sc, sh], 1).contiguous()
+
+
+def _up_rows(m, tap, oH, oW, src, up_t, up_hw):
+    """_gather_rows at unit stride with the nearest upsample folded into the gather: clamp on the UPSAMPLED extents, then halve"""
+    _, sH, sW = src
+    bH, bW = sH << int(up_hw), sW << int(up_hw)
+    t, h, w = m // (oH * oW), (m // oW) % oH, m % oW
+    ti = (t + tap // 9 - 2).clamp(min=0)
+    if up_t:
+        ti = torch.where(ti == 0, ti, 1 + (ti - 1) // 2)
+    hi = (h + (tap // 3) % 3 - 1).clamp(0, bH - 1) >> int(up_hw)
+    wi = (w + tap % 3 - 1).clamp(0, bW - 1) >> int(up_hw)
+    return (ti * sH + hi) * sW + wi
+
+
+def _conv_store(acc, bias, res, out, gn_stats):
+    """bias added last, one rounding to fp16, then fp16(res + y); the statistics are those of the stored tensor"""
+    if bias is not None:
+        acc = acc + bias.float()[None]
+    r = acc.to(F16)
+    if res is not None:
+        r = (res[:, :r.shape[1]].float() + r.float()).to(F16)
+    if out is None:
+        out = r
+    else:
+        out.copy_(r)
+    return (out, gn_stats_of(r)) if gn_stats else out
+
+
+def vae_conv3d_causal(x, w_taps, bias, T, H, W, cin, cout, up_t=False, up_hw=False, res=None, out=None, gn_stats=False):
+    """K-tile by K-tile (64 channels of one tap) into one fp32 accumulator over the OUTPUT grid T x H x W"""
+    assert (not up_t or T % 2 == 1) and (not up_hw or (H % 2 == 0 and W % 2 == 0)), (T, H, W, up_t, up_hw)
+    src = ((T + 1) // 2 if up_t else T, H >> int(up_hw), W >> int(up_hw))
+    assert x.shape[0] >= src[0] * src[1] * src[2], (tuple(x.shape), src)
+    m = torch.arange(T * H * W)
+    wt = w_taps.float().reshape(cout, 27, cin)
+    acc = torch.zeros(T * H * W, cout)
+    for tap in range(27):
+        a = x[_up_rows(m, tap, H, W, src, up_t, up_hw)][:, :cin].float()
+        for k0 in range(0, cin, 64):
+            acc = acc + a[:, k0:k0 + 64] @ wt[:, tap, k0:k0 + 64].T
+    return _conv_store(acc, bias, res, out, gn_stats)
+
+
+def vae_conv3d_upsampled_subpixel(x, w_sub, table, ntap, bias, sT, sH, sW, cin, cout, up_t, out=None, gn_stats=False):
+    """per parity class (pt, ph, pw) a conv over the source grid: tap j reads source voxel (max(kt + pt + ot, 0), clamp(kh + oh),
+    clamp(kw + ow)) with w_sub[class][:, j cin : (j + 1) cin]; class voxel (kt, kh, kw) is output (2 kt + pt | kt, 2 kh + ph, 2 kw + pw)"""
+    T2, H2, W2 = (2 * sT - 1 if up_t else sT), 2 * sH, 2 * sW
+    acc = torch.zeros(T2 * H2 * W2, cout)
+    tab = table.tolist()
+    for c in range(8 if up_t else 4):
+        pt, ph, pw = (c >> 2 if up_t else 0), (c >> 1) & 1, c & 1
+        frames = sT - 1 if (up_t and pt) else sT
+        if frames == 0:
+            continue
+        m = torch.arange(frames * sH * sW)
+        kt, kh, kw = m // (sH * sW), (m // sW) % sH, m % sW
+        a_c = torch.zeros(m.numel(), cout)
+        for j in range(ntap):
+            e = tab[c][j]
+            ot, oh, ow = (e & 15) - 8, ((e >> 4) & 15) - 8, ((e >> 8) & 15) - 8
+            rows = ((kt + pt + ot).clamp(min=0) * sH + (kh + oh).clamp(0, sH - 1)) * sW + (kw + ow).clamp(0, sW - 1)
+            a = x[rows][:, :cin].float()
+            wj = w_sub[c][:, j * cin:(j + 1) * cin].float()
+            for k0 in range(0, cin, 64):
+                a_c = a_c + a[:, k0:k0 + 64] @ wj[:, k0:k0 + 64].T
+        acc[((2 * kt + pt if up_t else kt) * H2 + 2 * kh + ph) * W2 + 2 * kw + pw] = a_c
+    return _conv_store(acc, bias, None, out, gn_stats)
+
+
+def vae_temporal_avg_pool(x, T, HW, k, s):
+    """frames t s + i - (k - 1), clamped at 0, summed in fp32 in the order i = 0 .. k - 1, times fp32(1 / k), one rounding to fp16"""
+    t_out = (T - 1) // s + 1
+    xf = x.float().reshape(T, HW, x.shape[1])
+    idx = (torch.arange(t_out)[:, None] * s + torch.arange(k)[None] - (k - 1)).clamp(min=0)
+    acc = torch.zeros(t_out, HW, x.shape[1])
+    for i in range(k):
+        acc = acc + xf[idx[:, i]]
+    return (acc * torch.tensor(1.0 / k, dtype=torch.float32)).to(F16).reshape(t_out * HW, x.shape[1]), t_out
+
+
+def vae_temporal_nearest_up(x, T, HW, s):
+    return x.reshape(T, 1, HW, x.shape[1]).expand(T, s, HW, x.shape[1]).reshape(T * s * HW, x.shape[1]).clone(), T * s
+
+
+def vae_temporal_linear_up(x, T, HW, s):
+    """output frame t: num = max(2 t + 1 - s, 0), t0 = num // 2 s, t1 = min(t0 + 1, T - 1), lambda = fp32((num mod 2 s) / 2 s);
+    y = fp16(x0 + lambda (x1 - x0)) in fp32; a bit copy of x0 where lambda = 0 or t0 = t1"""
+    t = torch.arange(T * s)
+    num = (2 * t + 1 - s).clamp(min=0)
+    t0 = num // (2 * s)
+    t1 = (t0 + 1).clamp(max=T - 1)
+    lam = ((num % (2 * s)).float() / float(2 * s))[:, None, None]
+    xf = x.float().reshape(T, HW, x.shape[1])
+    y = xf[t0] + lam * (xf[t1] - xf[t0])
+    return y.to(F16).reshape(T * s * HW, x.shape[1]), T * s
+
+
+def vae_latent_tile(z_f32_view, cpad):
+    """[C, T, H, W] fp32 (any strides) -> channels-last fp16 [T H W, cpad]: one rounding, zero in the columns [C, cpad)"""
+    c, t, h, w = z_f32_view.shape
+    out = torch.zeros(t * h * w, cpad, dtype=F16)
+    out[:, :c] = z_f32_view.permute(1, 2, 3, 0).reshape(t * h * w, c).to(F16)
+    return out
+
+
+def vae_copy4d_(src_view, dst_view):
+    assert src_view.shape == dst_view.shape and src_view.dim() == 4 and src_view.element_size() == 2 and dst_view.element_size() == 2
+    dst_view.copy_(src_view)
+    return dst_view
+
+
+# vae_ops name -> the double's name in this module
+VAE_TILE_CODER_NAMES = {"latent_tile": "vae_latent_tile", "gemm_f16": "vae_gemm_f16", "conv3d_causal": "vae_conv3d_causal",
+                        "conv3d_upsampled_subpixel": "vae_conv3d_upsampled_subpixel", "conv3d_causal_strided": "conv3d_causal_strided",
+                        "conv_cout4": "conv_cout4", "groupnorm_affine": "vae_groupnorm_affine",
+                        "groupnorm_affine_from_stats": "vae_groupnorm_affine_from_stats", "groupnorm_apply": "vae_groupnorm_apply",
+                        "softmax_rows": "vae_softmax_rows", "transpose_16b": "vae_transpose_16b",
+                        "temporal_avg_pool": "vae_temporal_avg_pool", "temporal_nearest_up": "vae_temporal_nearest_up",
+                        "temporal_linear_up": "vae_temporal_linear_up", "copy4d_": "vae_copy4d_"}
+
+
+def install_vae_tile_coder(monkeypatch):
+    """Install the doubles of every vae_ops entry point the tile coder calls, for the length of a test or module (monkeypatch undoes it)."""
+    from hunyuanvideo_efficiency_amd import vae_ops
+    g = globals()
+    for n, double in VAE_TILE_CODER_NAMES.items():
+        monkeypatch.setattr(vae_ops, n, g[double])
+    return vae_ops
+
+
 NAMES = ["ln_modulate", "qknorm_rope_", "gemm", "linear_smallm", "attn_fwd", "patchify", "unpatchify", "euler_step_",
          "masked_mean", "broadcast_row_", "timestep_embedding", "copy3d",
          "fp8_dequant", "quant_rows_fp8", "ln_modulate_fp8", "gemm_fp8"]

@@ -84,18 +84,34 @@ def make_x(kind, M, C, key):
     return x.to(F16)
 
 
-def ref_stats(x, C, chunk=1 << 22):
+def ref_stats(x, C, chunk=1 << 22, groups=GROUPS, eps=EPS):
     """fp64 two-pass mean and rstd per group of fp16 rows x [M, C] (chunked over rows: the production size is 545 M values)"""
-    M, cpg = x.shape[0], C // GROUPS
-    s = torch.zeros(GROUPS, dtype=torch.float64, device=x.device)
+    M, cpg = x.shape[0], C // groups
+    s = torch.zeros(groups, dtype=torch.float64, device=x.device)
     for r in range(0, M, chunk):
-        s += x[r:r + chunk].double().reshape(-1, GROUPS, cpg).sum((0, 2))
+        s += x[r:r + chunk].double().reshape(-1, groups, cpg).sum((0, 2))
     mean = s / (M * cpg)
     q = torch.zeros_like(s)
     for r in range(0, M, chunk):
-        q += ((x[r:r + chunk].double().reshape(-1, GROUPS, cpg) - mean[None, :, None]) ** 2).sum((0, 2))
+        q += ((x[r:r + chunk].double().reshape(-1, groups, cpg) - mean[None, :, None]) ** 2).sum((0, 2))
     var = q / (M * cpg)
-    return mean, 1.0 / torch.sqrt(var + EPS), var
+    return mean, 1.0 / torch.sqrt(var + eps), var
+
+
+AFFINE_TOL = 2e-4       # |x sc + sh - GroupNorm64(x)| <= 2e-4 (1 + |GroupNorm64(x)|): every affine path (own pass, conv epilogue, sub-pixel)
+
+
+def affine_error(x, aff, w, b, rows=None, groups=GROUPS, eps=EPS):
+    """(largest |x sc + sh - y_ref| / (1 + |y_ref|) over `rows` (default: all), y_ref) with y_ref the fp64 GroupNorm of x [M, C] at those
+    rows; shared with tests/vae_wiring.py"""
+    C = x.shape[1]
+    cpg = C // groups
+    mean, rstd, _ = ref_stats(x, C, groups=groups, eps=eps)
+    mean_c, rstd_c = mean.repeat_interleave(cpg), rstd.repeat_interleave(cpg)
+    xs = (x if rows is None else x[rows]).double()
+    y_ref = (xs - mean_c) * rstd_c * w.double() + b.double()
+    y_k = xs * aff[:, 0].double() + aff[:, 1].double()
+    return ((y_k - y_ref).abs() / (1.0 + y_ref.abs())).max(), y_ref
 
 
 def sample_rows(M, limit=1 << 18):
@@ -115,16 +131,10 @@ def fp16_ulp(r16, floor=2.0 ** -3):
 def check(V, x, aff, w, b, silu_too=True, what=""):
     """affine check over every row (or a deterministic sample at large M) + output check of hv_groupnorm_apply_f16"""
     M, C = x.shape
-    cpg = C // GROUPS
     assert torch.isfinite(aff).all(), f"{what}: non-finite affine"
-    mean, rstd, _ = ref_stats(x, C)
-    mean_c, rstd_c = mean.repeat_interleave(cpg), rstd.repeat_interleave(cpg)
     rows = sample_rows(M)
-    xs = x[rows].double()
-    y_ref = (xs - mean_c) * rstd_c * w.double() + b.double()
-    y_k = xs * aff[:, 0].double() + aff[:, 1].double()
-    err = ((y_k - y_ref).abs() / (1.0 + y_ref.abs())).max()
-    assert float(err) <= 2e-4, f"{what}: affine error {float(err):.3e} (bound 2e-4 (1 + |y|))"
+    err, y_ref = affine_error(x, aff, w, b, rows)
+    assert float(err) <= AFFINE_TOL, f"{what}: affine error {float(err):.3e} (bound 2e-4 (1 + |y|))"
     for silu in ((False, True) if silu_too else (False,)):
         got = V.groupnorm_apply(x, aff, silu)[rows]
         assert torch.isfinite(got).all(), f"{what}: non-finite output (silu={silu})"
