@@ -82,3 +82,11 @@ if not os.path.exists(MJPEG_READ_HEADER):
     raise HVKernelError(f"{MJPEG_READ_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
 with open(MJPEG_READ_HEADER) as _f:
     MJPEG_READ_DECLS, MJPEG_READ_MACROS = parse(_f.read())
+
+# include/hv_mjpeg_sync.h: the self-synchronising entropy stage for frames without restart markers (csrc/hv_mjpeg_sync.hip), declared and
+# parsed the same way
+MJPEG_SYNC_HEADER = os.path.join(os.path.dirname(HEADER), "hv_mjpeg_sync.h")
+if not os.path.exists(MJPEG_SYNC_HEADER):
+    raise HVKernelError(f"{MJPEG_SYNC_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
+with open(MJPEG_SYNC_HEADER) as _f:
+    MJPEG_SYNC_DECLS, MJPEG_SYNC_MACROS = parse(_f.read())

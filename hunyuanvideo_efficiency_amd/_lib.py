@@ -58,6 +58,9 @@ MJPEG_RESTYPES = {name: _ctype(ret, name) for ret, name, _ in _abi.MJPEG_DECLS}
 # and for include/hv_mjpeg_read.h
 MJPEG_READ_SIGNATURES = {name: [_ctype(t, f"{name}({p})") for t, p in params] for _, name, params in _abi.MJPEG_READ_DECLS}
 MJPEG_READ_RESTYPES = {name: _ctype(ret, name) for ret, name, _ in _abi.MJPEG_READ_DECLS}
+# and for include/hv_mjpeg_sync.h
+MJPEG_SYNC_SIGNATURES = {name: [_ctype(t, f"{name}({p})") for t, p in params] for _, name, params in _abi.MJPEG_SYNC_DECLS}
+MJPEG_SYNC_RESTYPES = {name: _ctype(ret, name) for ret, name, _ in _abi.MJPEG_SYNC_DECLS}
 _lib = _hv = None       # the loaded ctypes handle / torch.ops.hv namespace
 
 
@@ -80,13 +83,13 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in list(SIGNATURES.items()) + list(CONTENT_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()) + \
             list(GSSIM_SIGNATURES.items()) + list(YUVW_SIGNATURES.items()) + list(MOTION_SIGNATURES.items()) + list(MJPEG_SIGNATURES.items()) + \
-            list(MJPEG_READ_SIGNATURES.items()):
+            list(MJPEG_READ_SIGNATURES.items()) + list(MJPEG_SYNC_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
             raise HVKernelError(f"{LIB_PATH} does not export {name}") from e
         fn.argtypes = argtypes
-        fn.restype = {**MJPEG_READ_RESTYPES, **MJPEG_RESTYPES, **MOTION_RESTYPES, **YUVW_RESTYPES, **GSSIM_RESTYPES, **TEMPORAL_RESTYPES, **CONTENT_RESTYPES, **RESTYPES}[name]
+        fn.restype = {**MJPEG_SYNC_RESTYPES, **MJPEG_READ_RESTYPES, **MJPEG_RESTYPES, **MOTION_RESTYPES, **YUVW_RESTYPES, **GSSIM_RESTYPES, **TEMPORAL_RESTYPES, **CONTENT_RESTYPES, **RESTYPES}[name]
     v = lib.hv_abi_version()
     if v != ABI_VERSION:
         raise HVKernelError(f"libhv_kernels ABI {v} != expected {ABI_VERSION}: rebuild the extension")
@@ -122,7 +125,7 @@ def torch_ops():
     if v != ABI_VERSION:
         raise HVKernelError(f"libhv_torch_ops / libhv_kernels ABI {v} != expected {ABI_VERSION}: rebuild the extension")
     for name in list(SIGNATURES) + list(CONTENT_SIGNATURES) + list(TEMPORAL_SIGNATURES) + list(GSSIM_SIGNATURES) + list(YUVW_SIGNATURES) + \
-            list(MOTION_SIGNATURES) + list(MJPEG_SIGNATURES) + list(MJPEG_READ_SIGNATURES):
+            list(MOTION_SIGNATURES) + list(MJPEG_SIGNATURES) + list(MJPEG_READ_SIGNATURES) + list(MJPEG_SYNC_SIGNATURES):
         if not hasattr(hv, name[len("hv_"):]):
             raise HVKernelError(f"{TORCH_OPS_PATH} does not register torch.ops.hv.{name[len('hv_'):]}")
     _hv = hv

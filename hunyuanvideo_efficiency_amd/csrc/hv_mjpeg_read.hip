@@ -15,6 +15,7 @@
 //                        only in registers.
 #include "hv_common.hpp"
 #include "hv_mjpeg_decode.hpp"
+#include "hv_wg_scan.hpp"
 #include "../../include/hv_kernels.h"
 #include "../../include/hv_mjpeg_read.h"
 
@@ -34,21 +35,7 @@ constexpr int kBlocks = kYBlocks + 2 * kCBlocks;               // 80
 constexpr int kYLd = kTileX * 16, kCLd = kCBx * 8;
 constexpr int kWsLd = 65;                                      // int32 per block between the passes: blocks fall on different banks
 
-// exclusive prefix sum of v over the workgroup; total = the sum.  s: kThreads ints of LDS, free again on return.
-__device__ int wg_scan_excl(int v, int* s, int tid, int& total) {
-    s[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < kThreads; off <<= 1) {
-        const int a = tid >= off ? s[tid - off] : 0;
-        __syncthreads();
-        s[tid] += a;
-        __syncthreads();
-    }
-    total = s[kThreads - 1];
-    const int ex = s[tid] - v;
-    __syncthreads();
-    return ex;
-}
+static_assert(kThreads == kWgScanThreads, "wg_scan_excl (csrc/hv_wg_scan.hpp) sums over kThreads");
 
 __device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
 

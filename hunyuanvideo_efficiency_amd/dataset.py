@@ -293,8 +293,10 @@ class MjpegClipDataset:
     (mjpeg_io.read_mjpeg_clip).  A file that does not parse or has no frame in [start, end) is skipped with a printed line.
     `fps[name]` holds each file's frame rate."""
 
-    def __init__(self, video_dir, device="cuda", start=None, end=None, dtype=torch.float16, frames_per_chunk=None):
-        from .mjpeg_io import mjpeg_frame_range, parse_avi
+    def __init__(self, video_dir, device="cuda", start=None, end=None, dtype=torch.float16, frames_per_chunk=None, entropy="auto",
+                 sub_bytes=None):
+        from .mjpeg_io import _check_entropy, mjpeg_frame_range, parse_avi
+        self.entropy, self.sub_bytes = _check_entropy(entropy, sub_bytes, "MjpegClipDataset")
         self.tensor_dir, self.device, self.start, self.end = video_dir, device, start, end
         self.dtype, self.frames_per_chunk = dtype, frames_per_chunk
         self.tensor_files, self.fps, self.skipped = [], {}, []
@@ -319,7 +321,8 @@ class MjpegClipDataset:
     def __getitem__(self, idx):
         from .mjpeg_io import read_mjpeg_clip
         name = self.tensor_files[idx]
-        clip, _ = read_mjpeg_clip(os.path.join(self.tensor_dir, name), self.device, self.start, self.end, self.dtype, self.frames_per_chunk)
+        clip, _ = read_mjpeg_clip(os.path.join(self.tensor_dir, name), self.device, self.start, self.end, self.dtype, self.frames_per_chunk,
+                                  entropy=self.entropy, sub_bytes=self.sub_bytes)
         return clip, name
 
 
@@ -341,6 +344,8 @@ def check_yuv_arguments(args, parser):
         if (args.start_frame is not None and args.start_frame < 0) or (args.end_frame is not None and args.end_frame < 0):
             parser.error("--start-frame and --end-frame are non-negative")
         return
+    if getattr(args, "mjpeg_entropy", None) is not None:
+        parser.error("--mjpeg-entropy is only valid with --mjpeg-input")
     if args.yuv_format is None:
         for flag in ("target_height", "start_frame", "end_frame"):
             if getattr(args, flag) is not None:
@@ -356,7 +361,7 @@ def dataset_from_args(args, device="cuda"):
     """the YuvClipDataset the flags of add_yuv_arguments ask for (fp16 clips, what the drivers feed the VAE); with --mjpeg-input the
     MjpegClipDataset"""
     if getattr(args, "mjpeg_input", False):
-        return MjpegClipDataset(args.tensor_dir, device, args.start_frame, args.end_frame)
+        return MjpegClipDataset(args.tensor_dir, device, args.start_frame, args.end_frame, entropy=getattr(args, "mjpeg_entropy", None) or "auto")
     return YuvClipDataset(args.tensor_dir, device, args.yuv_format, args.start_frame, args.end_frame, args.target_height)
 
 

@@ -314,6 +314,14 @@ def save_reconstruction_mjpeg(recon: torch.Tensor, out_dir: str, stem: str, fps=
 HUFF_BYTES = _abi.MJPEG_READ_MACROS["HV_MJPEG_HUFF_BYTES"]
 QUANT_BYTES = _abi.MJPEG_READ_MACROS["HV_MJPEG_QUANT_BYTES"]
 RST_ORDER = _abi.MJPEG_READ_MACROS["HV_MJPEG_RST_ORDER"]
+SYNC_MACROS = _abi.MJPEG_SYNC_MACROS
+ENTROPY_CHOICES = ("auto", "serial", "sync")
+# the entropy stage (stage B) of a group of frames: "serial" = one decoder per restart interval (hv_mjpeg_decode_coefs), "sync" = the
+# self-synchronising workgroup per interval (hv_mjpeg_decode_coefs_sync, include/hv_mjpeg_sync.h), "auto" = sync when the group's mean
+# interval (scan bytes / intervals) is at least SYNC_MIN_INTERVAL_BYTES, i.e. for frames without restart markers.  Both stages write the
+# same bytes.  The two values are measured ones: profiles/metrics/bench_mjpeg_sync.json, DESIGN section 4.
+SYNC_MIN_INTERVAL_BYTES = 2048
+SYNC_SUB_BYTES = 256
 STATUS_REASONS = {1: "the entropy-coded data ran out", 2: "no Huffman code matches", 3: "a coefficient index past 63",
                   4: "an unexpected marker inside the interval"}
 # (W, H, quant, huff, Ri, scan_begin, scan_end): quant = (Y, chroma) of 64 steps in natural order; huff = ((BITS, HUFFVAL) of DC Y, AC Y,
@@ -628,7 +636,20 @@ def _check_out(out, T, H, W, dtype, device, who):
     return out
 
 
-def _decode_group(data, begins, ends, frame, out, coefs, checks, unit=False):
+def _check_entropy(entropy, sub_bytes, who):
+    if entropy not in ENTROPY_CHOICES:
+        raise ValueError(f"{who}: entropy is one of {', '.join(ENTROPY_CHOICES)}, got {entropy!r}")
+    if sub_bytes is not None and not SYNC_MACROS["HV_MJPEG_SYNC_MIN_SUB"] <= int(sub_bytes) <= SYNC_MACROS["HV_MJPEG_SYNC_MAX_SUB"]:
+        raise ValueError(f"{who}: sub_bytes is {SYNC_MACROS['HV_MJPEG_SYNC_MIN_SUB']} .. {SYNC_MACROS['HV_MJPEG_SYNC_MAX_SUB']}, got {sub_bytes!r}")
+    return entropy, None if sub_bytes is None else int(sub_bytes)
+
+
+def use_sync(entropy: str, scan_bytes: int, intervals: int) -> bool:
+    """whether a group of frames with `scan_bytes` of entropy-coded data in `intervals` restart intervals takes the sync stage"""
+    return entropy == "sync" or (entropy == "auto" and scan_bytes >= SYNC_MIN_INTERVAL_BYTES * intervals)
+
+
+def _decode_group(data, begins, ends, frame, out, coefs, checks, unit=False, entropy="auto", sub_bytes=None):
     """stages A (when the frames carry restart markers), B and C for frames of equal parameters; appends (found, status, ipf) to checks"""
     T, dev = len(begins), data.device
     W, H, Ri = frame.W, frame.H, frame.Ri
@@ -639,16 +660,21 @@ def _decode_group(data, begins, ends, frame, out, coefs, checks, unit=False):
         ib, ie = torch.empty(T * ipf, dtype=torch.int64, device=dev), torch.empty(T * ipf, dtype=torch.int64, device=dev)
         found = torch.empty(T, dtype=torch.int32, device=dev)
         _lib.call("mjpeg_find_restarts", data, data.numel(), b[:T], b[T:], T, ipf, ib, ie, found)
+    sync = use_sync(entropy, sum(ends) - sum(begins), T * ipf)
     _decode_intervals(data, ib, ie, T, H, W, Ri, ipf, huff_list(frame.huff), list(frame.quant[0]) + list(frame.quant[1]), out, coefs,
-                      checks, found, unit)
+                      checks, found, unit, sync, sub_bytes)
 
 
-def _decode_intervals(data, ib, ie, T, H, W, Ri, ipf, huff, quant, out, coefs, checks, found=None, unit=False):
+def _decode_intervals(data, ib, ie, T, H, W, Ri, ipf, huff, quant, out, coefs, checks, found=None, unit=False, sync=False, sub_bytes=None):
     need = coef_bytes(T, H, W)
     if coefs is None or coefs.numel() < need:
         coefs = torch.empty(need, dtype=torch.uint8, device=data.device)
     status = torch.empty(T * ipf, dtype=torch.int32, device=data.device)
-    _lib.call("mjpeg_decode_coefs", data, data.numel(), ib, ie, T, H, W, Ri, ipf, huff, coefs, coefs.numel(), status)
+    if sync:
+        _lib.call("mjpeg_decode_coefs_sync", data, data.numel(), ib, ie, T, H, W, Ri, ipf, huff, SYNC_SUB_BYTES if sub_bytes is None else sub_bytes,
+                  coefs, coefs.numel(), status, None)
+    else:
+        _lib.call("mjpeg_decode_coefs", data, data.numel(), ib, ie, T, H, W, Ri, ipf, huff, coefs, coefs.numel(), status)
     _lib.call("mjpeg_coefs_to_clip", coefs, coefs.numel(), quant, _value_table(out.dtype, data.device, unit), out, _DTYPES[out.dtype],
               out.stride(0), out.stride(1), out.stride(2), T, H, W)
     checks.append((found, status, ipf))
@@ -675,14 +701,16 @@ def _raise_on_status(checks, path, first_frame):
 
 
 def jpeg_to_clip(data: torch.Tensor, frames, out: torch.Tensor = None, dtype=torch.float16, coefs: torch.Tensor = None, path=None,
-                 first_frame: int = 0, unit: bool = False, checks: list = None) -> torch.Tensor:
+                 first_frame: int = 0, unit: bool = False, checks: list = None, entropy: str = "auto", sub_bytes: int = None) -> torch.Tensor:
     """data: uint8 on the GPU holding the frames; frames: one JpegFrame per frame, its scan_begin / scan_end counted in `data` ->
     the clip [3,T,H,W] in [-1, 1] (channels R, G, B; `out`: a fp16 / fp32 view to fill, W contiguous, e.g. a frame slice of a larger
     clip).  Consecutive frames with equal parameters (size, tables, restart interval) are decoded by one launch of each stage; a file of
     write_mjpeg_clip is one group.  `coefs`: a uint8 workspace to reuse (coef_bytes).  The status words of all launches are read back
     once, at the end: ValueError(path, frame, interval, reason) for the first frame that did not decode (first_frame is added to the
     frame number); `out` then holds unspecified pixels.  checks: a list to which the status tensors of this call are appended INSTEAD of
-    being read back, for a caller that makes several calls and reads them all once (read_mjpeg_clip; _raise_on_status).  unit: values byte / 255 in [0, 1] instead (compute_metrics' uint8 path)."""
+    being read back, for a caller that makes several calls and reads them all once (read_mjpeg_clip; _raise_on_status).  unit: values byte / 255 in [0, 1] instead (compute_metrics' uint8 path).
+    entropy, sub_bytes: the entropy stage of every group, see ENTROPY_CHOICES above (sub_bytes None: SYNC_SUB_BYTES); the result is the same."""
+    entropy, sub_bytes = _check_entropy(entropy, sub_bytes, "jpeg_to_clip")
     if not isinstance(data, torch.Tensor) or not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
         raise _lib.HVKernelError("jpeg_to_clip: expected contiguous uint8 on the GPU (this package has no CPU path), got "
                                  f"{(data.device, data.dtype) if isinstance(data, torch.Tensor) else type(data).__name__}")
@@ -704,16 +732,19 @@ def jpeg_to_clip(data: torch.Tensor, frames, out: torch.Tensor = None, dtype=tor
             while t1 < len(frames) and frames[t1][:5] == frames[t0][:5]:
                 t1 += 1
             _decode_group(data, [f.scan_begin for f in frames[t0:t1]], [f.scan_end for f in frames[t0:t1]], frames[t0], out[:, t0:t1],
-                          coefs, checks, unit)
+                          coefs, checks, unit, entropy, sub_bytes)
             t0 = t1
         if own:
             _raise_on_status(checks, path, first_frame)
     return out
 
 
-def mjpeg_roundtrip(x: torch.Tensor, quality: int = DEFAULT_QUALITY, rescale: bool = False, dtype=None) -> torch.Tensor:
+def mjpeg_roundtrip(x: torch.Tensor, quality: int = DEFAULT_QUALITY, rescale: bool = False, dtype=None, entropy: str = "auto",
+                    sub_bytes: int = None) -> torch.Tensor:
     """x [C,T,H,W] on the GPU -> [3,T,H,W] in [-1, 1]: the clip as a player of write_mjpeg_clip's file shows it, coded (clip_to_jpeg)
-    and decoded again (stages B and C on the interval offsets the coder already has) without leaving the card"""
+    and decoded again (stages B and C on the interval offsets the coder already has) without leaving the card.  entropy, sub_bytes: as
+    jpeg_to_clip takes them (the coder's one interval per MCU row is what "auto" hands to the serial stage)."""
+    entropy, sub_bytes = _check_entropy(entropy, sub_bytes, "mjpeg_roundtrip")
     scan, offsets, rows = _clip_to_intervals(x, quality, rescale, "mjpeg_roundtrip")
     C, T, H, W = x.shape
     out = _check_out(None, T, H, W, x.dtype if dtype is None else dtype, x.device, "mjpeg_roundtrip")
@@ -723,7 +754,7 @@ def mjpeg_roundtrip(x: torch.Tensor, quality: int = DEFAULT_QUALITY, rescale: bo
     checks = []
     with torch.cuda.device(x.device):
         _decode_intervals(scan, offsets[:-1], offsets[1:], T, H, W, (W + MCU - 1) // MCU, rows, huff_list(_ANNEX_K_HUFF), q[0] + q[1], out,
-                          None, checks)
+                          None, checks, sync=use_sync(entropy, scan.numel(), T * rows), sub_bytes=sub_bytes)
         _raise_on_status(checks, None, 0)
     return out
 
@@ -735,14 +766,18 @@ def mjpeg_frame_range(n_frames: int, start=None, end=None):
     return first, last
 
 
-def read_mjpeg_clip(path: str, device="cuda", start=None, end=None, dtype=torch.float16, frames_per_chunk=None, unit: bool = False):
+def read_mjpeg_clip(path: str, device="cuda", start=None, end=None, dtype=torch.float16, frames_per_chunk=None, unit: bool = False,
+                    entropy: str = "auto", sub_bytes: int = None):
     """One Motion-JPEG `.avi` -> (clip [3,T,H,W] on `device` in [-1, 1], fps): the frames [start, end) of parse_avi.  The file is read
     `frames_per_chunk` whole frames at a time (default: as many as decode to 64 MiB of 8-bit RGB) into at most two pinned staging
     buffers; each chunk is uploaded with non_blocking=True and decoded straight into its frame slice of the output, a staging buffer is
     refilled only after the event behind its upload has passed, and the coefficient workspace is sized for one chunk (the kernels of
     consecutive chunks share it in stream order).  Nothing is synchronised between chunks: the host reads and parses chunk i + 1 while
     the device decodes chunk i, and the status words of all chunks are read back once, behind the last.  The headers of
-    every frame are parsed on the host (parse_jpeg); ValueError(path, frame, interval, reason) for a frame that does not decode."""
+    every frame are parsed on the host (parse_jpeg); ValueError(path, frame, interval, reason) for a frame that does not decode.
+    entropy, sub_bytes: the entropy stage, as jpeg_to_clip takes them; "auto" gives files without restart markers (Pillow's, ffmpeg's, a
+    camera's) the self-synchronising stage and files of write_mjpeg_clip the serial one."""
+    entropy, sub_bytes = _check_entropy(entropy, sub_bytes, "read_mjpeg_clip")
     W, H, fps, index = parse_avi(path)
     first, last = mjpeg_frame_range(len(index), start, end)
     T = last - first
@@ -794,7 +829,7 @@ def read_mjpeg_clip(path: str, device="cuda", start=None, end=None, dtype=torch.
                 uploaded[b] = torch.cuda.Event()
                 uploaded[b].record(stream)
                 jpeg_to_clip(staged[b][:hi - lo], frames, out=clip[:, t0:t0 + len(part)], coefs=coefs, path=path, first_frame=first + t0,
-                             unit=unit, checks=checks)
+                             unit=unit, checks=checks, entropy=entropy, sub_bytes=sub_bytes)
         for e in uploaded:
             if e is not None:
                 e.synchronize()                              # the pinned buffers are freed on return
@@ -802,8 +837,10 @@ def read_mjpeg_clip(path: str, device="cuda", start=None, end=None, dtype=torch.
     return clip, fps
 
 
-def read_jpeg(path: str, device="cuda", dtype=torch.float16) -> torch.Tensor:
-    """One baseline 4:2:0 `.jpg` (a strip of write_jpeg_strip, or any such file) -> [3,1,H,W] on `device` in [-1, 1]"""
+def read_jpeg(path: str, device="cuda", dtype=torch.float16, entropy: str = "auto", sub_bytes: int = None) -> torch.Tensor:
+    """One baseline 4:2:0 `.jpg` (a strip of write_jpeg_strip, or any such file) -> [3,1,H,W] on `device` in [-1, 1]; entropy,
+    sub_bytes as jpeg_to_clip takes them"""
+    entropy, sub_bytes = _check_entropy(entropy, sub_bytes, "read_jpeg")
     with open(path, "rb") as f:
         raw = f.read()
     try:
@@ -814,9 +851,12 @@ def read_jpeg(path: str, device="cuda", dtype=torch.float16) -> torch.Tensor:
     if device.type != "cuda":
         raise _lib.HVKernelError(f"read_jpeg: expected a GPU device (this package has no CPU path), got {device}")
     data = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
-    return jpeg_to_clip(data, [fr], dtype=dtype, path=path)
+    return jpeg_to_clip(data, [fr], dtype=dtype, path=path, entropy=entropy, sub_bytes=sub_bytes)
 
 
 def add_mjpeg_input_arguments(parser):
     parser.add_argument("--mjpeg-input", action="store_true", help="read --tensor-dir as a folder of Motion-JPEG .avi files (what "
                         "--save-mjpeg writes), decoded on the GPU, instead of .pt tensors; --start-frame / --end-frame select frames")
+    parser.add_argument("--mjpeg-entropy", choices=ENTROPY_CHOICES, default=None, help="with --mjpeg-input: the entropy stage of the "
+                        "decoder (default auto: the self-synchronising stage for files without restart markers, the serial one for "
+                        "files --save-mjpeg wrote; the frames are the same)")

@@ -13,12 +13,13 @@ The entry points of include/hv_content.h go to csrc/hv_content_torch_ops.cpp the
 those of include/hv_temporal.h to csrc/hv_temporal_torch_ops.cpp, those of include/hv_gssim.h to csrc/hv_gssim_torch_ops.cpp, those of
 include/hv_yuv_write.h to csrc/hv_yuv_write_torch_ops.cpp, those of include/hv_motion.h to csrc/hv_motion_torch_ops.cpp,
 those of include/hv_mjpeg.h to csrc/hv_mjpeg_torch_ops.cpp, those of include/hv_mjpeg_read.h to csrc/hv_mjpeg_read_torch_ops.cpp (its two
-host tables, const uint8_t* huff_tables / quant_tables, are int[] of the header's HV_MJPEG_HUFF_BYTES / HV_MJPEG_QUANT_BYTES entries 0 .. 255).
-Run:  python tools/gen_torch_ops.py            (rewrites the eight .cpp files; tests/test_capi_cpu.py, tests/test_content_refusals_cpu.py,
+host tables, const uint8_t* huff_tables / quant_tables, are int[] of the header's HV_MJPEG_HUFF_BYTES / HV_MJPEG_QUANT_BYTES entries 0 .. 255),
+those of include/hv_mjpeg_sync.h to csrc/hv_mjpeg_sync_torch_ops.cpp.
+Run:  python tools/gen_torch_ops.py            (rewrites the nine .cpp files; tests/test_capi_cpu.py, tests/test_content_refusals_cpu.py,
                                                 tests/test_temporal_refusals_cpu.py, tests/test_gssim_refusals_cpu.py,
                                                 tests/test_yuv_write_refusals_cpu.py, tests/test_motion_refusals_cpu.py and
-                                                tests/test_mjpeg_refusals_cpu.py and tests/test_mjpeg_read_refusals_cpu.py check they are
-                                                up to date)
+                                                tests/test_mjpeg_refusals_cpu.py, tests/test_mjpeg_read_refusals_cpu.py and
+                                                tests/test_mjpeg_sync_cpu.py check they are up to date)
       python tools/gen_torch_ops.py --record-abi    (after a bump of HV_ABI_VERSION: writes tests/golden/abi_v<N>.json, the
                                                       declarations the same test holds the header to until the next bump)
 """
@@ -39,6 +40,7 @@ YUVW_OUT = os.path.join(ROOT, "hunyuanvideo_efficiency_amd", "csrc", "hv_yuv_wri
 MOTION_OUT = os.path.join(ROOT, "hunyuanvideo_efficiency_amd", "csrc", "hv_motion_torch_ops.cpp")   # from include/hv_motion.h
 MJPEG_OUT = os.path.join(ROOT, "hunyuanvideo_efficiency_amd", "csrc", "hv_mjpeg_torch_ops.cpp")   # from include/hv_mjpeg.h
 MJPEG_READ_OUT = os.path.join(ROOT, "hunyuanvideo_efficiency_amd", "csrc", "hv_mjpeg_read_torch_ops.cpp")   # from include/hv_mjpeg_read.h
+MJPEG_SYNC_OUT = os.path.join(ROOT, "hunyuanvideo_efficiency_amd", "csrc", "hv_mjpeg_sync_torch_ops.cpp")   # from include/hv_mjpeg_sync.h
 HOST_BYTES = {"huff_tables": _abi.MJPEG_READ_MACROS["HV_MJPEG_HUFF_BYTES"], "quant_tables": _abi.MJPEG_READ_MACROS["HV_MJPEG_QUANT_BYTES"]}
 HOST_ARRAYS = {"a_strides", "b_strides", "src_strides", "dst_strides", "dims"}
 HOST_ARRAY_LEN = 4      # every host array of the C ABI is a 4-vector (hv_vae_blend_f16, hv_copy4d_16b: strides / dims of a 4-D view)
@@ -209,7 +211,8 @@ if __name__ == "__main__":
     for path, text in ((OUT, gen()), (CONTENT_OUT, gen(_abi.CONTENT_DECLS, "hv_content.h")),
                        (TEMPORAL_OUT, gen(_abi.TEMPORAL_DECLS, "hv_temporal.h")), (GSSIM_OUT, gen(_abi.GSSIM_DECLS, "hv_gssim.h")),
                        (YUVW_OUT, gen(_abi.YUVW_DECLS, "hv_yuv_write.h")), (MOTION_OUT, gen(_abi.MOTION_DECLS, "hv_motion.h")),
-                       (MJPEG_OUT, gen(_abi.MJPEG_DECLS, "hv_mjpeg.h")), (MJPEG_READ_OUT, gen(_abi.MJPEG_READ_DECLS, "hv_mjpeg_read.h"))):
+                       (MJPEG_OUT, gen(_abi.MJPEG_DECLS, "hv_mjpeg.h")), (MJPEG_READ_OUT, gen(_abi.MJPEG_READ_DECLS, "hv_mjpeg_read.h")),
+                       (MJPEG_SYNC_OUT, gen(_abi.MJPEG_SYNC_DECLS, "hv_mjpeg_sync.h"))):
         with open(path, "w") as f:
             f.write(text)
         print(f"wrote {path}: {text.count('m.def(')} ops")
