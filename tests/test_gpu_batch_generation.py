@@ -182,8 +182,8 @@ def _tp_batch_worker(rank, world, port, outdir):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         torch.cuda.set_device(0)
-        from tests.test_gpu_sp_two_ranks import _stage_collectives_through_host
-        _stage_collectives_through_host()
+        from tests.sp_gpu_helpers import stage_collectives_through_host
+        stage_collectives_through_host()
         vae = _tiled_vae()
         vae.enable_tiling()
         z = (syn.hashed_uniform((2, 16, 6, 24, 20), "batch.vae.tp", 5) * 2.0).cuda()
