@@ -90,3 +90,10 @@ if not os.path.exists(MJPEG_SYNC_HEADER):
     raise HVKernelError(f"{MJPEG_SYNC_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
 with open(MJPEG_SYNC_HEADER) as _f:
     MJPEG_SYNC_DECLS, MJPEG_SYNC_MACROS = parse(_f.read())
+
+# include/hv_attn_fp8.h: the FP8 attention forward (csrc/hv_attn_fp8.hip), declared and parsed the same way
+ATTN_FP8_HEADER = os.path.join(os.path.dirname(HEADER), "hv_attn_fp8.h")
+if not os.path.exists(ATTN_FP8_HEADER):
+    raise HVKernelError(f"{ATTN_FP8_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
+with open(ATTN_FP8_HEADER) as _f:
+    ATTN_FP8_DECLS, ATTN_FP8_MACROS = parse(_f.read())

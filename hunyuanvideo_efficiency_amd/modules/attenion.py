@@ -82,15 +82,29 @@ def attention(q, k, v, mode="flash", drop_rate=0, attn_mask=None, causal=False, 
     return out
 
 
-def segment_attention_(hybrid_seq_parallel_attn, qkv: torch.Tensor, cat: torch.Tensor, s_img: int, cu1: int, heads: int, d: int):
+def check_fp8_attention(fp8_attention: bool, hybrid_seq_parallel_attn):
+    """fp8_attention together with sequence parallelism has no kernel (the exchange and the ring partials are bf16): an error, never a
+    silent bf16 run"""
+    if fp8_attention and hybrid_seq_parallel_attn is not None:
+        raise NotImplementedError("fp8_attention (enable_fp8_attention / --fp8-attention) together with hybrid_seq_parallel_attn "
+                                  "(sequence parallelism) is not implemented: run one of the two")
+
+
+def segment_attention_(hybrid_seq_parallel_attn, qkv: torch.Tensor, cat: torch.Tensor, s_img: int, cu1: int, heads: int, d: int,
+                       fp8_attention: bool = False, fp8_workspace=None):
     """Block-internal form: q|k|v live in the fused `qkv` rows [S, 3d]; output goes to cat[:, :d].
     Without SP: segment 1 = rows [0, cu1) (image + valid text), segment 2 = rows [cu1, S) (padding text)
     (attenion.py:34-57).  With SP the block's `hybrid_seq_parallel_attn` object runs the Ulysses exchange for
-    the first segment exactly as parallel_attention does (attenion.py:159-212)."""
+    the first segment exactly as parallel_attention does (attenion.py:159-212).
+    fp8_attention (off by default): segment 1 runs ops.attn_fwd_fp8 in `fp8_workspace` (include/hv_attn_fp8.h); the small padding
+    segment stays bf16."""
+    check_fp8_attention(fp8_attention, hybrid_seq_parallel_attn)
     s = qkv.shape[0]
     q, k, v, o = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], cat[:, :d]
     if hybrid_seq_parallel_attn is None:
-        if cu1 > 0:
+        if cu1 > 0 and fp8_attention:
+            ops.attn_fwd_fp8(q[:cu1], k[:cu1], v[:cu1], o[:cu1], heads, workspace=fp8_workspace)
+        elif cu1 > 0:
             ops.attn_fwd(q[:cu1], k[:cu1], v[:cu1], o[:cu1], heads)
     else:
         hybrid_seq_parallel_attn.run_fused(qkv, cat, s_img, cu1, heads, d)

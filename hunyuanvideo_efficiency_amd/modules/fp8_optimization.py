@@ -66,6 +66,20 @@ def enable_fp8_mfma(module, enable: bool = True) -> int:
     return n
 
 
+def enable_fp8_attention(module, enable: bool = True) -> int:
+    """Opt-in FP8 ATTENTION (include/hv_attn_fp8.h): every double / single block runs its main segment (image + valid text) with Q, K,
+    V and P quantised to e4m3 on v_mfma_scale_f32_32x32x64_f8f6f4 (ops.attn_fwd_fp8); the padding-text segment stays bf16.  Attention
+    has no weights, so this is independent of convert_fp8_linear / enable_fp8_mfma.  Not the reference's arithmetic: it adds the e4m3
+    rounding of the four operands; bound and tolerance: tests/test_gpu_attn_fp8.py.  Together with sequence parallelism the blocks
+    raise NotImplementedError.  Returns the number of blocks."""
+    n = 0
+    for key, block in module.named_modules():
+        if hasattr(block, "hybrid_seq_parallel_attn") and hasattr(block, "run"):
+            block.fp8_attention = bool(enable)
+            n += 1
+    return n
+
+
 def convert_fp8_linear(module, dit_weight_path: Optional[str], original_dtype, params_to_keep={}, fp8_map: Optional[Dict] = None):
     """fp8_optimization.py:82-100.  `<dit_weight_path>_map.pt` holds the per-layer scales of a real FP8 checkpoint and is
     read with torch.load(weights_only=True) (never unpickled).  Without a checkpoint (random-init benchmarks) pass

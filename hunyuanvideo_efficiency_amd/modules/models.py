@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .attenion import get_cu_seqlens, n_valid_text, segment_attention_, pad_segment_attention_
+from .attenion import get_cu_seqlens, n_valid_text, segment_attention_, pad_segment_attention_, check_fp8_attention
 from .token_refiner import SingleTokenRefiner
 from .layers import ParamLinear, ParamNormWeight, ModulateDiT, MLP, MLPEmbedder, TimestepEmbedder, PatchEmbed, FinalLayer
 
@@ -44,6 +44,13 @@ class _Workspace:
         self.final = None
         # FP8-MFMA path (allocated on first use): per-token quantised A operands + their row scales
         self.xq = self.xs = self.catq = self.cats = None
+        self.attn8 = None       # FP8 attention (opt-in): the workspace of include/hv_attn_fp8.h, allocated on first use, grow-only
+
+    def fp8_attention_workspace(self, n_rows: int, heads: int):
+        need = ops.attn_fp8_workspace_bytes(n_rows, n_rows, heads)
+        if self.attn8 is None or self.attn8.numel() < need:
+            self.attn8 = torch.empty(need, dtype=torch.uint8, device=self.x.device)
+        return self.attn8
 
     def fp8_buffers(self):
         if self.xq is None:
@@ -62,6 +69,15 @@ def _use_fp8_mfma(block, *layers) -> bool:
     reference's weight-only semantics (per-call dequantisation + bf16 MFMA)."""
     return bool(getattr(block, "fp8_mfma", False)) and all(
         l.weight.dtype == torch.float8_e4m3fn and l.in_features >= 384 and l.in_features % 128 == 0 for l in layers)
+
+
+def _attention(block, sp, ws: _Workspace, s_img: int, cu1: int, H: int, d: int):
+    """segment_attention_ with the block's opt-in FP8 attention flag (fp8_optimization.enable_fp8_attention)"""
+    if not getattr(block, "fp8_attention", False):
+        segment_attention_(sp, ws.qkv, ws.cat, s_img, cu1, H, d)             # the default: the call as it always was
+        return
+    segment_attention_(sp, ws.qkv, ws.cat, s_img, cu1, H, d, fp8_attention=True,
+                       fp8_workspace=ws.fp8_attention_workspace(cu1, H) if sp is None and cu1 > 0 else None)
 
 
 def _ln(ws: _Workspace, lo: int, hi: int, shift, scale, fp8: bool):
@@ -155,6 +171,7 @@ class MMDoubleStreamBlock(nn.Module):
         # txt first: under sequence parallelism its (replicated) q/k/v rows are the joint tensors of the exchange
         streams = (("txt", s_img, s_img + s_txt, 0), ("img", 0, s_img, s_img if cos is not None else 0))
         sp = self.hybrid_seq_parallel_attn
+        check_fp8_attention(bool(getattr(self, "fp8_attention", False)), sp)
         overlap = sp is not None and hasattr(sp, "send") and H % 2 == 0
         mods = {}
         fp8 = {s: _use_fp8_mfma(self, getattr(self, f"{s}_attn_qkv"), getattr(self, f"{s}_attn_proj"), getattr(self, f"{s}_mlp").fc1,
@@ -179,7 +196,7 @@ class MMDoubleStreamBlock(nn.Module):
             segs = sp.attend_async(ws.cat, ws.cat.stride(0))
             pad_segment_attention_(ws.qkv, ws.cat, cu1, H, d)
         else:
-            segment_attention_(sp, ws.qkv, ws.cat, s_img, cu1, H, d)
+            _attention(self, sp, ws, s_img, cu1, H, d)
         streams = (streams[1], streams[0])
         for s, lo, hi, _ in streams:
             _, _, g1, sh2, sc2, g2 = mods[s]
@@ -248,6 +265,7 @@ class MMSingleStreamBlock(nn.Module):
         s_all = ws.x.shape[0]
         _ln(ws, 0, s_all, shift, scale, fp8)
         sp = self.hybrid_seq_parallel_attn
+        check_fp8_attention(bool(getattr(self, "fp8_attention", False)), sp)
         n_rope = s_img if cos is not None else 0
         if sp is not None and hasattr(sp, "send") and H % 2 == 0:
             # sequence parallel: q | k | v | mlp as four column-chunk GEMMs of linear1; the all-to-all of each attention chunk
@@ -269,7 +287,7 @@ class MMSingleStreamBlock(nn.Module):
             # linear1: cols [0,3d) -> qkv ; cols [3d, 3d+mlp) -> GELU-tanh -> cat[:, d:]   (models.py:339-341,392)
             _gemm(ws, self.linear1, "xmod", 0, s_all, fp8, out=ws.qkv, n_split=3 * d, out1=ws.cat[:, d:], act1=ops.ACT_GELU_TANH)
             ops.qknorm_rope_(ws.qkv, self.q_norm.weight, self.k_norm.weight, cos, sin, n_rope, H, d)
-            segment_attention_(sp, ws.qkv, ws.cat, s_img, cu1, H, d)
+            _attention(self, sp, ws, s_img, cu1, H, d)
         _gemm(ws, self.linear2, "cat", 0, s_all, fp8, out=ws.x, gate=gate, res=ws.x)
 
     def forward(self, x, vec, txt_len, cu_seqlens_q=None, cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None,

@@ -357,3 +357,8 @@ def copy3d(src, dst, n_batch: int, rows: int, cols: int, src_bs: int, src_ld: in
     _chk(src, BF16, "src", False), _chk(dst, BF16, "dst", False)
     _lib.call("copy3d_bf16", src, dst, n_batch, rows, cols, src_bs, src_ld, dst_bs, dst_ld)
     return dst
+
+
+# FP8 attention (opt-in; include/hv_attn_fp8.h): the wrappers live in attn_fp8.py beside their layout restatement and are public here
+from .attn_fp8 import (ATTN_FP8, attn_fp8_layout, attn_fp8_quantise, attn_fp8_workspace_bytes,  # noqa: E402,F401
+                       attn_fwd_fp8)

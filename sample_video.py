@@ -45,6 +45,9 @@ def parse_args(argv=None):
     p.add_argument("--cfg-scale", type=float, default=1.0)
     p.add_argument("--embedded-cfg-scale", type=float, default=6.0)
     p.add_argument("--use-fp8", action="store_true")
+    p.add_argument("--fp8-attention", action="store_true", help="run the main attention segment of every block with Q, K, V and P in "
+                   "e4m3 on the CDNA4 FP8 matrix cores (include/hv_attn_fp8.h) - an opt-in approximation, independent of --use-fp8; not "
+                   "available with --ulysses-degree / --ring-degree > 1")
     p.add_argument("--ulysses-degree", type=int, default=1)
     p.add_argument("--ring-degree", type=int, default=1)
     p.add_argument("--text-len", type=int, default=256)
@@ -119,6 +122,9 @@ def main(argv=None):
         checkpoint.load_state_dict(a, model, a.model_base)
     elif a.use_fp8:
         convert_fp8_linear(model, None, torch.bfloat16)
+    if a.fp8_attention:
+        from hunyuanvideo_efficiency_amd.modules.fp8_optimization import enable_fp8_attention
+        enable_fp8_attention(model)
     if a.vae_path:
         from hunyuanvideo_efficiency_amd.vae import load_vae
         vae = load_vae(a.vae, a.vae_precision, vae_path=a.vae_path, device=dev)[0]
