@@ -97,3 +97,10 @@ if not os.path.exists(ATTN_FP8_HEADER):
     raise HVKernelError(f"{ATTN_FP8_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
 with open(ATTN_FP8_HEADER) as _f:
     ATTN_FP8_DECLS, ATTN_FP8_MACROS = parse(_f.read())
+
+# include/hv_attn_tile.h: the sliding-tile attention forward (csrc/hv_attn_tile.hip), declared and parsed the same way
+ATTN_TILE_HEADER = os.path.join(os.path.dirname(HEADER), "hv_attn_tile.h")
+if not os.path.exists(ATTN_TILE_HEADER):
+    raise HVKernelError(f"{ATTN_TILE_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
+with open(ATTN_TILE_HEADER) as _f:
+    ATTN_TILE_DECLS, ATTN_TILE_MACROS = parse(_f.read())

@@ -90,19 +90,38 @@ def check_fp8_attention(fp8_attention: bool, hybrid_seq_parallel_attn):
                                   "(sequence parallelism) is not implemented: run one of the two")
 
 
+def check_tile_plan(tile_plan, fp8_attention: bool, hybrid_seq_parallel_attn):
+    """a sliding-tile plan together with sequence parallelism (the exchange moves natural-order shards) or with fp8_attention (the FP8
+    kernel has no window) has no kernel: an error, never a silent dense run"""
+    if tile_plan is not None and hybrid_seq_parallel_attn is not None:
+        raise NotImplementedError("tile_plan (enable_sliding_tile_attention / --sliding-tile-attention) together with "
+                                  "hybrid_seq_parallel_attn (sequence parallelism) is not implemented: run one of the two")
+    if tile_plan is not None and fp8_attention:
+        raise NotImplementedError("tile_plan (enable_sliding_tile_attention / --sliding-tile-attention) together with fp8_attention "
+                                  "(enable_fp8_attention / --fp8-attention) is not implemented: run one of the two")
+
+
 def segment_attention_(hybrid_seq_parallel_attn, qkv: torch.Tensor, cat: torch.Tensor, s_img: int, cu1: int, heads: int, d: int,
-                       fp8_attention: bool = False, fp8_workspace=None):
+                       fp8_attention: bool = False, fp8_workspace=None, tile_plan=None):
     """Block-internal form: q|k|v live in the fused `qkv` rows [S, 3d]; output goes to cat[:, :d].
     Without SP: segment 1 = rows [0, cu1) (image + valid text), segment 2 = rows [cu1, S) (padding text)
     (attenion.py:34-57).  With SP the block's `hybrid_seq_parallel_attn` object runs the Ulysses exchange for
     the first segment exactly as parallel_attention does (attenion.py:159-212).
     fp8_attention (off by default): segment 1 runs ops.attn_fwd_fp8 in `fp8_workspace` (include/hv_attn_fp8.h); the small padding
-    segment stays bf16."""
+    segment stays bf16.
+    tile_plan (None by default; ops.tile_plan): segment 1 becomes two launches - the image rows through ops.attn_fwd_tile (the plan's
+    window of tiles plus the valid text [s_img, cu1)), the valid-text query rows through ops.attn_fwd against all keys [0, cu1)."""
     check_fp8_attention(fp8_attention, hybrid_seq_parallel_attn)
+    check_tile_plan(tile_plan, fp8_attention, hybrid_seq_parallel_attn)
     s = qkv.shape[0]
     q, k, v, o = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], cat[:, :d]
     if hybrid_seq_parallel_attn is None:
-        if cu1 > 0 and fp8_attention:
+        if tile_plan is not None:
+            if s_img > 0:
+                ops.attn_fwd_tile(q[:s_img], k[:cu1], v[:cu1], o[:s_img], heads, tile_plan, dense=(s_img, cu1))
+            if cu1 > s_img:
+                ops.attn_fwd(q[s_img:cu1], k[:cu1], v[:cu1], o[s_img:cu1], heads)
+        elif cu1 > 0 and fp8_attention:
             ops.attn_fwd_fp8(q[:cu1], k[:cu1], v[:cu1], o[:cu1], heads, workspace=fp8_workspace)
         elif cu1 > 0:
             ops.attn_fwd(q[:cu1], k[:cu1], v[:cu1], o[:cu1], heads)

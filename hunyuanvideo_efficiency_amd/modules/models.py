@@ -23,7 +23,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .attenion import get_cu_seqlens, n_valid_text, segment_attention_, pad_segment_attention_, check_fp8_attention
+from ..attn_tile import model_plan
+from .attenion import get_cu_seqlens, n_valid_text, segment_attention_, pad_segment_attention_, check_fp8_attention, check_tile_plan
 from .token_refiner import SingleTokenRefiner
 from .layers import ParamLinear, ParamNormWeight, ModulateDiT, MLP, MLPEmbedder, TimestepEmbedder, PatchEmbed, FinalLayer
 
@@ -44,6 +45,7 @@ class _Workspace:
         self.final = None
         # FP8-MFMA path (allocated on first use): per-token quantised A operands + their row scales
         self.xq = self.xs = self.catq = self.cats = None
+        self.tile_plan = None   # sliding-tile attention (opt-in): the plan of this forward's token grid, set by the transformer's forward
         self.attn8 = None       # FP8 attention (opt-in): the workspace of include/hv_attn_fp8.h, allocated on first use, grow-only
 
     def fp8_attention_workspace(self, n_rows: int, heads: int):
@@ -72,7 +74,15 @@ def _use_fp8_mfma(block, *layers) -> bool:
 
 
 def _attention(block, sp, ws: _Workspace, s_img: int, cu1: int, H: int, d: int):
-    """segment_attention_ with the block's opt-in FP8 attention flag (fp8_optimization.enable_fp8_attention)"""
+    """segment_attention_ with the block's opt-in flags: FP8 attention (fp8_optimization.enable_fp8_attention) and sliding-tile
+    attention (attn_tile.enable_sliding_tile_attention; the plan waits in ws.tile_plan)"""
+    if getattr(block, "sliding_tile", False):
+        if ws.tile_plan is None:
+            raise RuntimeError("sliding-tile attention is enabled on this block but no tile plan was built: run the block through "
+                               "HYVideoDiffusionTransformer.forward, which knows the token grid")
+        segment_attention_(sp, ws.qkv, ws.cat, s_img, cu1, H, d, fp8_attention=bool(getattr(block, "fp8_attention", False)),
+                           tile_plan=ws.tile_plan)
+        return
     if not getattr(block, "fp8_attention", False):
         segment_attention_(sp, ws.qkv, ws.cat, s_img, cu1, H, d)             # the default: the call as it always was
         return
@@ -172,6 +182,7 @@ class MMDoubleStreamBlock(nn.Module):
         streams = (("txt", s_img, s_img + s_txt, 0), ("img", 0, s_img, s_img if cos is not None else 0))
         sp = self.hybrid_seq_parallel_attn
         check_fp8_attention(bool(getattr(self, "fp8_attention", False)), sp)
+        check_tile_plan(ws.tile_plan if getattr(self, "sliding_tile", False) else None, bool(getattr(self, "fp8_attention", False)), sp)
         overlap = sp is not None and hasattr(sp, "send") and H % 2 == 0
         mods = {}
         fp8 = {s: _use_fp8_mfma(self, getattr(self, f"{s}_attn_qkv"), getattr(self, f"{s}_attn_proj"), getattr(self, f"{s}_mlp").fc1,
@@ -266,6 +277,7 @@ class MMSingleStreamBlock(nn.Module):
         _ln(ws, 0, s_all, shift, scale, fp8)
         sp = self.hybrid_seq_parallel_attn
         check_fp8_attention(bool(getattr(self, "fp8_attention", False)), sp)
+        check_tile_plan(ws.tile_plan if getattr(self, "sliding_tile", False) else None, bool(getattr(self, "fp8_attention", False)), sp)
         n_rope = s_img if cos is not None else 0
         if sp is not None and hasattr(sp, "send") and H % 2 == 0:
             # sequence parallel: q | k | v | mlp as four column-chunk GEMMs of linear1; the all-to-all of each attention chunk
@@ -420,6 +432,7 @@ class HYVideoDiffusionTransformer(nn.Module):
         tt, th, tw = ot // self.patch_size[0], oh // self.patch_size[1], ow // self.patch_size[2]
         s_img, s_txt, d = tt * th * tw, text_states.shape[1], self.hidden_size
         ws = self._workspace(s_img, s_txt, dev)
+        ws.tile_plan = model_plan(self, (tt, th, tw), dev)               # None unless enable_sliding_tile_attention was called
 
         # ---- modulation vector (models.py:618-631)
         t32 = t.reshape(-1).to(torch.float32)

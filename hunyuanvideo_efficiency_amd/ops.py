@@ -362,3 +362,6 @@ def copy3d(src, dst, n_batch: int, rows: int, cols: int, src_bs: int, src_ld: in
 # FP8 attention (opt-in; include/hv_attn_fp8.h): the wrappers live in attn_fp8.py beside their layout restatement and are public here
 from .attn_fp8 import (ATTN_FP8, attn_fp8_layout, attn_fp8_quantise, attn_fp8_workspace_bytes,  # noqa: E402,F401
                        attn_fwd_fp8)
+
+# Sliding-tile attention (opt-in; include/hv_attn_tile.h): plan builder and wrapper live in attn_tile.py and are public here
+from .attn_tile import ATTN_TILE, TilePlan, attn_fwd_tile, tile_plan  # noqa: E402,F401

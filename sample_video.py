@@ -48,6 +48,13 @@ def parse_args(argv=None):
     p.add_argument("--fp8-attention", action="store_true", help="run the main attention segment of every block with Q, K, V and P in "
                    "e4m3 on the CDNA4 FP8 matrix cores (include/hv_attn_fp8.h) - an opt-in approximation, independent of --use-fp8; not "
                    "available with --ulysses-degree / --ring-degree > 1")
+    p.add_argument("--sliding-tile-attention", action="store_true", help="image queries attend a window of 3-D token tiles plus the valid "
+                   "text instead of every key (include/hv_attn_tile.h) - an opt-in approximation whose effect on generated video has not "
+                   "been measured; not available with --fp8-attention or --ulysses-degree / --ring-degree > 1")
+    p.add_argument("--sta-tile", type=int, nargs=3, default=None, metavar=("T", "H", "W"), help="with --sliding-tile-attention: tokens per "
+                   "tile along (t, h, w), at most 256 in all (default 4 8 8)")
+    p.add_argument("--sta-window", type=int, nargs=3, default=None, metavar=("T", "H", "W"), help="with --sliding-tile-attention: tiles per "
+                   "window along (t, h, w) (default 3 3 3)")
     p.add_argument("--ulysses-degree", type=int, default=1)
     p.add_argument("--ring-degree", type=int, default=1)
     p.add_argument("--text-len", type=int, default=256)
@@ -78,6 +85,8 @@ def parse_args(argv=None):
                    "from the four pixels' mean (default) or from its top-left pixel, as OpenCV's COLOR_RGB2YUV_I420 takes it")
     p.add_argument("--save-quality", type=int, default=None, help="with --save-format avi: JPEG quality 1 .. 100 (default 90)")
     a = p.parse_args(argv)
+    if (a.sta_tile is not None or a.sta_window is not None) and not a.sliding_tile_attention:
+        p.error("--sta-tile and --sta-window are only valid with --sliding-tile-attention")
     if a.save_chroma is not None and a.save_format not in ("y4m", "yuv"):
         p.error("--save-chroma is only valid with --save-format y4m or yuv")
     if a.save_quality is not None and a.save_format != "avi":
@@ -125,6 +134,9 @@ def main(argv=None):
     if a.fp8_attention:
         from hunyuanvideo_efficiency_amd.modules.fp8_optimization import enable_fp8_attention
         enable_fp8_attention(model)
+    if a.sliding_tile_attention:
+        from hunyuanvideo_efficiency_amd.attn_tile import enable_sliding_tile_attention
+        enable_sliding_tile_attention(model, tuple(a.sta_tile or (4, 8, 8)), tuple(a.sta_window or (3, 3, 3)))
     if a.vae_path:
         from hunyuanvideo_efficiency_amd.vae import load_vae
         vae = load_vae(a.vae, a.vae_precision, vae_path=a.vae_path, device=dev)[0]
