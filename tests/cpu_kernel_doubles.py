@@ -308,6 +308,116 @@ def attn_fwd(q, k, v, out, n_heads, scale=None, kv_split_workspace=True):
     return out
 
 
+# ---- the opt-in attention paths (hunyuanvideo_efficiency_amd/attn_tile.py, attn_fp8.py; public as ops.attn_fwd_tile, ops.attn_fp8_quantise,
+# ops.attn_fwd_fp8)
+def _attn_fwd_tile(q, k, v, out, n_heads, plan, dense, scale, mutant=None):
+    """attn_fwd_tile with one changed line where `mutant` names it (tests/test_kernel_doubles_cpu.py): "keys-once" (a key row counts
+    once however often the lists and the dense range name it), "no-output-scatter" (perm gathers queries and keys, the rows are stored
+    at their slots) and "empty-is-0/0" (a tile without keys gets O / l = 0 / 0)"""
+    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out")):
+        _chk(t, BF16, nm)
+        assert t.dim() == 2
+    n_q, n_kv, d = q.shape[0], k.shape[0], n_heads * 128
+    assert v.shape[0] == n_kv and out.shape[0] == n_q
+    if plan.n_img != n_q:
+        raise ValueError(f"attn_fwd_tile: the plan is for {plan.n_img} image tokens, q has {n_q} rows")
+    if plan.perm.device != q.device:
+        raise ValueError(f"attn_fwd_tile: the plan is on {plan.perm.device}, q on {q.device}")
+    if plan.n_lists not in (1, n_heads):
+        raise ValueError(f"attn_fwd_tile: the plan has {plan.n_lists} window lists for {n_heads} heads")
+    lo, hi = int(dense[0]), int(dense[1])
+    _abi(n_heads > 0 and n_kv >= n_q and plan.n_tiles > 0 and 0 <= lo <= hi <= n_kv and all(t.stride(0) % 8 == 0 for t in (q, k, v))
+         and out.stride(0) % 4 == 0 and _pitch_ok(n_q, out.stride(0), d), "attn_fwd_tile")
+    assert all(t.shape[1] >= d for t in (q, k, v, out)), "attn_fwd_tile: a view narrower than n_heads * 128 columns"
+    if n_q == 0:
+        return out
+    _abi(plan.n_tiles <= n_q, "attn_fwd_tile n_tiles")
+    qh, kh, vh = (t[:, :d].float().reshape(t.shape[0], n_heads, 128) for t in (q, k, v))
+    sc = 1.0 / math.sqrt(128) if scale is None else float(scale)
+    perm, start, ptr, idx = (t.tolist() for t in (plan.perm, plan.tile_start, plan.nb_ptr, plan.nb_idx))
+    for h in range(n_heads):
+        row_ptr = ptr[h if plan.n_lists > 1 else 0]
+        for i in range(plan.n_tiles):
+            slots = list(range(start[i], start[i + 1]))
+            rows = [perm[s] for s in slots]
+            keys = [perm[s] for t in idx[row_ptr[i]:row_ptr[i + 1]] for s in range(start[t], start[t + 1])] + list(range(lo, hi))
+            if mutant == "keys-once":
+                keys = list(dict.fromkeys(keys))
+            dst = slots if mutant == "no-output-scatter" else rows
+            if not keys and mutant != "empty-is-0/0":
+                out[dst, h * 128:(h + 1) * 128] = 0
+                continue
+            s = qh[rows, h] @ kh[keys, h].T * sc
+            e = torch.exp(s - s.amax(dim=-1, keepdim=True)) if keys else s
+            o = (e.to(BF16).float() @ vh[keys, h]) / e.sum(dim=-1, keepdim=True)
+            out[dst, h * 128:(h + 1) * 128] = _bf(o)
+    return out
+
+
+def attn_fwd_tile(q, k, v, out, n_heads, plan, dense=(0, 0), scale=None):
+    """per (tile, head) the arithmetic of attn_fwd above (q NOT rounded after the scale) over the key rows of the tile's neighbour list,
+    gathered through plan.perm WITH multiplicity, then the dense range; rows scattered through perm; a tile without keys gets zero rows;
+    nothing outside the image rows x n_heads * 128 columns is written.  The wrapper's ValueErrors, the C ABI's refusals and the narrow-
+    view assertion of the other attention doubles."""
+    return _attn_fwd_tile(q, k, v, out, n_heads, plan, dense, scale)
+
+
+def _attn_fp8_args(q, k, v, n_heads, workspace):
+    """what attn_fp8._attn_fp8_args checks and allocates; hv_attn_fp8_workspace_bytes restated: the layout's total, 0 for refused extents"""
+    from hunyuanvideo_efficiency_amd.attn_fp8 import attn_fp8_layout
+    for t, nm in ((q, "q"), (k, "k"), (v, "v")):
+        _chk(t, BF16, nm)
+        assert t.dim() == 2
+    n_q, n_kv = q.shape[0], k.shape[0]
+    assert v.shape[0] == n_kv
+    ok = 0 < n_heads <= 65535 and n_kv <= 2 ** 31 - 2049 and not (n_q > 0 and n_kv == 0)
+    need = attn_fp8_layout(n_q, n_kv, n_heads)["total"] if ok else 0
+    if need == 0 and n_q > 0:
+        raise ValueError(f"attn_fwd_fp8: extents n_q {n_q}, n_kv {n_kv}, n_heads {n_heads} are outside include/hv_attn_fp8.h")
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8)
+    _chk(workspace, torch.uint8, "workspace")
+    if workspace.dim() != 1 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"attn_fwd_fp8: workspace must be a contiguous uint8 vector of at least {need} bytes, got {tuple(workspace.shape)}")
+    _abi(ok and all(t.stride(0) % 8 == 0 for t in (q, k, v)) and workspace.data_ptr() % 16 == 0, "attn_fp8_quantise")
+    assert all(t.shape[1] >= n_heads * 128 for t in (q, k, v)), "attn_fp8_quantise: a view narrower than n_heads * 128 columns"
+    return n_q, n_kv, workspace
+
+
+def attn_fp8_quantise(q, k, v, n_heads, scale=None, workspace=None):
+    """the quantisation rules of include/hv_attn_fp8.h in fp32 torch (tests/attn_fp8_ref.restate), written in the header's workspace
+    layout (attn_fp8_ref.pack); the scratch area `part`, the alignment gaps and the bytes behind the layout's total are not written"""
+    from hunyuanvideo_efficiency_amd.attn_fp8 import ATTN_FP8
+    from tests import attn_fp8_ref as F8
+    n_q, n_kv, workspace = _attn_fp8_args(q, k, v, n_heads, workspace)
+    if n_q > 0:
+        d = n_heads * 128
+        F8.pack(F8.restate(q[:, :d], k[:, :d], v[:, :d], n_heads, ATTN_FP8["HV_ATTN_FP8_STAT_KEYS"], scale), workspace, n_q, n_kv, n_heads)
+    return workspace
+
+
+def attn_fwd_fp8(q, k, v, out, n_heads, scale=None, workspace=None):
+    """quantise, then attention over the DEQUANTISED workspace in fp32 (log2 domain): s = (q8 . k8) sq sk, p = 2^(s - max), the row sum
+    from the unrounded p, P = e4m3(p 2^8) for P.V, O = (P . v8) sv / (l 2^8) as bf16"""
+    from tests import attn_fp8_ref as F8
+    _chk(out, BF16, "out")
+    assert out.dim() == 2 and out.shape[0] == q.shape[0]
+    workspace = attn_fp8_quantise(q, k, v, n_heads, scale, workspace)
+    n_q, n_kv, d = q.shape[0], k.shape[0], n_heads * 128
+    _abi(out.stride(0) % 4 == 0 and _pitch_ok(n_q, out.stride(0), d), "attn_fwd_fp8 out")
+    assert out.shape[1] >= d
+    if n_q == 0:
+        return out
+    u = F8.unpack(workspace, n_q, n_kv, n_heads)
+    for h in range(n_heads):
+        s = (u["q8"][:, h].float() @ u["k8"][h, :n_kv].float().T) * u["sq"][:, h, None] * u["sk"][h].repeat_interleave(64)[None, :n_kv]
+        p = torch.exp2(s - s.amax(dim=-1, keepdim=True))
+        p8 = (p * 256.0).to(FP8).float()
+        o = (p8 @ u["v8"][h, :n_kv].float()) * u["sv"][h][None] / (p.sum(dim=-1, keepdim=True) * 256.0)
+        out[:, h * 128:(h + 1) * 128] = _bf(o)
+    return out
+
+
 # ---- ring attention: the partial format of hv_attn_partial_bf16 / hv_attn_merge_bf16 (log2-domain max m, unnormalised fp32 o and row sum l)
 class AttnPartials:
     """ops.AttnPartials on the CPU: the same attributes, shapes and dtypes"""
@@ -822,7 +932,8 @@ def install_vae_tile_coder(monkeypatch):
 
 NAMES = ["ln_modulate", "qknorm_rope_", "gemm", "linear_smallm", "attn_fwd", "patchify", "unpatchify", "euler_step_",
          "masked_mean", "broadcast_row_", "timestep_embedding", "copy3d",
-         "fp8_dequant", "quant_rows_fp8", "ln_modulate_fp8", "gemm_fp8"]
+         "fp8_dequant", "quant_rows_fp8", "ln_modulate_fp8", "gemm_fp8",
+         "attn_fwd_tile", "attn_fp8_quantise", "attn_fwd_fp8"]
 
 
 def install():

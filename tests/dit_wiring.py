@@ -39,6 +39,14 @@ class Case:
     use_attention_mask: bool = True
     rope: bool = True               # False: freqs_cos = freqs_sin = None (n_rope = 0)
     guidance_embed: bool = True
+    flag: str = ""                  # "sta": enable_sliding_tile_attention(tile, window); "fp8attn": enable_fp8_attention
+    tile: tuple = (4, 8, 8)         # the defaults of enable_sliding_tile_attention
+    window: tuple = (3, 3, 3)       # one triple, or one per head
+
+    @property
+    def grid(self) -> tuple:
+        t, h, w = self.thw
+        return (t, h // 2, w // 2)
 
     @property
     def s_img(self) -> int:
@@ -53,10 +61,13 @@ class Case:
     def name(self) -> str:
         flags = "".join(f"-{n}" for n, on in (("nomask", not self.mask), ("noattnmask", not self.use_attention_mask),
                                              ("norope", not self.rope), ("noguidance", not self.guidance_embed)) if on)
-        return f"img{self.s_img}-txt{self.s_txt}v{self.n_valid}{flags}"
+        opt = "" if not self.flag else f"-{self.flag}" + ("" if self.flag != "sta" else "-t" + "x".join(map(str, self.tile)) + "-w" + str(self.window).replace(" ", ""))
+        return f"img{self.s_img}-txt{self.s_txt}v{self.n_valid}{flags}{opt}"
 
     @property
     def model_kind(self) -> str:
+        if self.flag:
+            return self.flag
         return "tiny" + ("" if self.guidance_embed else "-noguidance") + ("" if self.use_attention_mask else "-noattnmask")
 
 
@@ -80,8 +91,28 @@ CASES = [
 FP8_CASES = [Case((1, 2, 2), 32, 11), Case((3, 6, 10), 32, 0), Case((1, 2, 514), 32, 32), Case((3, 6, 10), 9, 4)]
 
 
+# the opt-in attention paths at model level: each case stands for one edge (the tiny config: 2 heads)
+_W = dict(flag="sta", tile=(2, 2, 2), window=(1, 1, 3))
+STA_CASES = [
+    Case((3, 6, 10), 32, 11, **_W),                                             # mid case
+    Case((3, 6, 10), 32, 0, **_W),                                              # empty dense range, no text-query launch, NaN text rows
+    Case((3, 6, 10), 32, 32, **_W),                                             # no padding segment
+    Case((1, 16, 16), 32, 1, flag="sta", tile=(1, 8, 8), window=(1, 1, 1)),     # one tile, one chunk
+    Case((5, 16, 16), 32, 31, flag="sta", window=(1, 1, 1)),                    # the default tile: a 256-row tile and a ragged 64
+    Case((1, 2, 2), 9, 4, flag="sta"),                                          # one image token
+    Case((3, 6, 10), 32, 32, mask=False, **_W),                                 # text_mask=None
+    Case((3, 6, 10), 32, 11, flag="sta", tile=(2, 2, 2), window=((1, 1, 3), (3, 1, 1))),     # one window per head
+]
+FP8ATTN_CASES = [dataclasses.replace(c, flag="fp8attn", tile=(4, 8, 8), window=(3, 3, 3)) for c in STA_CASES[:5]]
+FP8ATTN_RANGE_TOL = 1e-1        # an FP8 approximation against non-FP8 semantics (tests/test_gpu_fp8_mfma.py, test_model_with_fp8_attention)
+
+
+def _fp8_mfma(kind: str) -> bool:
+    return kind.startswith("fp8") and kind != "fp8attn"
+
+
 def config(kind: str) -> syn.DiTConfig:
-    if kind.startswith("fp8"):
+    if _fp8_mfma(kind):
         return syn.DiTConfig(hidden_size=512, heads_num=4, mm_double_blocks_depth=1, mm_single_blocks_depth=2)
     cfg = syn.tiny_config()
     cfg.guidance_embed = "-noguidance" not in kind
@@ -103,10 +134,16 @@ class Harness:
         from hunyuanvideo_efficiency_amd.builders import build_model
         model = build_model(config(kind), self.dev)
         model.use_attention_mask = "-noattnmask" not in kind
-        if kind.startswith("fp8"):
+        if _fp8_mfma(kind):
             from hunyuanvideo_efficiency_amd.modules.fp8_optimization import convert_fp8_linear, enable_fp8_mfma
             convert_fp8_linear(model, None, BF16)
             assert enable_fp8_mfma(model) == 3
+        if kind == "sta":
+            from hunyuanvideo_efficiency_amd.attn_tile import enable_sliding_tile_attention
+            assert enable_sliding_tile_attention(model) == 2
+        if kind == "fp8attn":
+            from hunyuanvideo_efficiency_amd.modules.fp8_optimization import enable_fp8_attention
+            assert enable_fp8_attention(model) == 2
         model.wiring_kind = kind
         if not fresh:
             self._models[kind] = model
@@ -118,7 +155,7 @@ class Harness:
         if hit is None:
             sd = {k: p.float().cpu() for k, p in model.state_dict().items()}
             prec = E
-            if model.wiring_kind.startswith("fp8"):
+            if _fp8_mfma(model.wiring_kind):
                 prec = R.Fp8MfmaPrec()
                 for name, layer in model.named_modules():
                     if hasattr(layer, "fp8_scale"):
@@ -296,9 +333,11 @@ def check_stages(h: Harness, model, case: Case, inp: dict, out: torch.Tensor, re
 def check_whole_output(h: Harness, model, case: Case, inp: dict, out: torch.Tensor, kind: Optional[str] = None) -> float:
     sd, prec = h.oracle_weights(model)
     err = range_error(out, oracle_forward(sd, config(kind or case.model_kind), case, inp, prec))
-    h.note("whole output / 3e-2" + (" (fp8)" if (kind or "").startswith("fp8") else ""), err / RANGE_TOL, case)
+    tol = FP8ATTN_RANGE_TOL if case.flag == "fp8attn" else RANGE_TOL
+    label = {"sta": " (sta)", "fp8attn": " (fp8attn)"}.get(case.flag, " (fp8)" if _fp8_mfma(kind or "") else "")
+    h.note("whole output / " + ("1e-1" if case.flag == "fp8attn" else "3e-2") + label, err / tol, case)
     print(f"[dit wiring] {case.name}: whole output vs oracle {err:.3e} of range")
-    assert err < RANGE_TOL, f"{case.name}: whole output {err:.3e} of range"
+    assert err < tol, f"{case.name}: whole output {err:.3e} of range"
     return err
 
 
@@ -517,6 +556,163 @@ def check_fp8_case(h: Harness, case: Case, other: Case):
     assert model._ws.xq is not None
 
 
+# ------------------------------------------------------------------------------------------------------------------ opt-in attention
+@contextlib.contextmanager
+def windowed_oracle(case: Case, heads: int):
+    """oracle.dit_ref.attention_varlen for a model under enable_sliding_tile_attention: segment 1 is R.sdpa with a mask - image query i
+    sees image key j iff allowed(grid, tile, window of the head)[i, j], and all of [s_img, cu1); text queries see all of [0, cu1).  The
+    window is restated from index arithmetic (tests/attn_tile_plans.allowed), not read from the plan.  Any other case: the oracle as it is."""
+    if case.flag != "sta":
+        yield
+        return
+    from tests.attn_tile_plans import allowed
+    windows = case.window if isinstance(case.window[0], (tuple, list)) else (case.window,)
+    ok = torch.stack([allowed(case.grid, case.tile, windows[h % len(windows)])[0] for h in range(heads)])
+    s_img = case.s_img
+
+    def attention_varlen(q, k, v, cu, p):
+        b, s, h, d = q.shape
+        assert b == 1 and h == heads
+        cu1 = int(cu[1])
+        mask = torch.ones(h, cu1, cu1, dtype=torch.bool)
+        mask[:, :s_img, :s_img] = ok
+        out = torch.zeros(1, s, h, d)
+        out[:, :cu1] = R.sdpa(q[:, :cu1], k[:, :cu1], v[:, :cu1], p, mask[None])
+        if s > cu1:
+            out[:, cu1:] = R.sdpa(q[:, cu1:], k[:, cu1:], v[:, cu1:], p)
+        return out.reshape(1, s, h * d)
+    with _patch_attr(R, "attention_varlen", attention_varlen):
+        yield
+
+
+def flag_model(h: Harness, case: Case, fresh: bool = False):
+    model = h.model(case.flag, fresh=fresh)
+    if case.flag == "sta":
+        from hunyuanvideo_efficiency_amd.attn_tile import enable_sliding_tile_attention
+        enable_sliding_tile_attention(model, tile=case.tile, window=case.window)
+    return model
+
+
+def check_flag_case(h: Harness, case: Case):
+    """"sta": A against the windowed oracle at the block tolerance (the tile kernel keeps the dense kernel's arithmetic contract), the whole
+    output at 3e-2 of range, B1, B3, B4.  "fp8attn": no stage check (no bound is derived for a whole block under FP8 attention); the
+    whole output within 1e-1 of the range of the UNFLAGGED oracle, B1, B4."""
+    model = flag_model(h, case)
+    inp = h.inputs(case)
+    out, rec = h.run_traced(model, inp)
+    if case.flag == "fp8attn":
+        assert model._ws.attn8 is not None, "the FP8 attention path did not run"
+    else:
+        assert model._ws.tile_plan is not None and model._ws.tile_plan.grid == case.grid, "the sliding-tile path did not run on this grid"
+    with windowed_oracle(case, config(case.model_kind).heads_num):
+        if case.flag == "sta":
+            check_stages(h, model, case, inp, out, rec)
+        check_whole_output(h, model, case, inp, out)
+    check_repeat(h, model, case, inp, out)
+    if padding_applies(case):
+        check_padding_content(h, model, case, inp, out, rec)
+    if case.rope and case.flag == "sta":
+        check_rope_table_edge(h, model, case, inp, out)
+
+
+GRID_A, GRID_B = (2, 8, 16), (4, 8, 8)      # latents of equal s_img = 64 and other token grids: (2, 4, 8) and (4, 4, 4)
+
+
+def check_grid_change(h: Harness):
+    """grid A, then B, then A on one model under enable_sliding_tile_attention: the workspace key (s_img, s_txt) does not change, the
+    plan must.  The third output has the bits of the first, the second those of a fresh model."""
+    a, b = (Case(g, 32, 11, **_W) for g in (GRID_A, GRID_B))
+    assert a.s_img == b.s_img and a.grid != b.grid
+    model = flag_model(h, a, fresh=True)
+    first = h.run(model, h.inputs(a))
+    ws = model._ws
+    second = h.run(model, h.inputs(b))
+    assert model._ws is ws, "the workspace was re-keyed: the case does not test the plan alone"
+    assert bits_equal(second, h.run(flag_model(h, b, fresh=True), h.inputs(b))), "grid B after grid A differs from grid B on a fresh model: a stale plan"
+    assert bits_equal(first, h.run(model, h.inputs(a))), "grid A after grid B differs from the first run of grid A"
+
+
+def check_no_plan_raises(h: Harness):
+    """block.forward (the reference call surface, which does not know the token grid) with the flag on: the documented RuntimeError"""
+    case = STA_CASES[0]
+    model = flag_model(h, case, fresh=True)
+    d, S = config("sta").hidden_size, case.s_img + case.s_txt
+    z = lambda n: torch.zeros(1, n, d, dtype=BF16, device=h.dev)
+    vec, cu = torch.zeros(1, d, dtype=BF16, device=h.dev), _cu(case)
+    for call in (lambda: model.double_blocks[0](z(case.s_img), z(case.s_txt), vec, cu, cu, S, S, None),
+                 lambda: model.single_blocks[0](z(S), vec, case.s_txt, cu, cu, S, S, None)):
+        try:
+            with torch.no_grad():
+                call()
+        except RuntimeError as e:
+            assert "no tile plan was built" in str(e), str(e)
+        else:
+            raise AssertionError("a block under enable_sliding_tile_attention ran without a tile plan")
+
+
+def check_flag_rekey(h: Harness, flag: str):
+    """B5 under a flag.  "sta": between two grids.  "fp8attn": larger -> smaller -> larger, so that the grow-only FP8 workspace is
+    reused at a smaller cu1"""
+    big, small = ((Case((5, 16, 16), 32, 31, **_W), Case((3, 6, 10), 32, 11, **_W)) if flag == "sta" else (FP8ATTN_CASES[4], FP8ATTN_CASES[0]))
+    model = flag_model(h, big, fresh=True)
+    check_rekey(h, model, big, small, flag)
+    if flag == "fp8attn":
+        assert model._ws.attn8 is not None
+
+
+def _all_rows(t):
+    """the view `t` stretched over every row its storage holds behind its first (a column block of the fused qkv / cat buffer)"""
+    room = (t.untyped_storage().nbytes() // t.element_size() - t.storage_offset() - t.shape[1]) // t.stride(0) + 1
+    return torch.as_strided(t, (room, t.shape[1]), t.stride(), t.storage_offset())
+
+
+def _mutant_tile_dense(kind):
+    """the sliding-tile launch of segment_attention_ as a slip of the pen would make it: "to-S" hands it k, v up to S and
+    dense=(s_img, S) (the padding text inside the image's key set), "lo+1" dense=(s_img + 1, cu1) (the first valid text token lost)"""
+    from hunyuanvideo_efficiency_amd import ops
+    inner = ops.attn_fwd_tile
+
+    def attn_fwd_tile(q, k, v, out, n_heads, plan, dense=(0, 0), scale=None):
+        if kind == "to-S":
+            k, v = _all_rows(k), _all_rows(v)
+            dense = (dense[0], k.shape[0])
+        elif dense[1] > dense[0]:
+            dense = (dense[0] + 1, dense[1])
+        return inner(q, k, v, out, n_heads, plan, dense=dense, scale=scale)
+    return _patch_attr(ops, "attn_fwd_tile", attn_fwd_tile)
+
+
+def _mutant_text_queries_not_launched():
+    """segment_attention_ under a tile plan without its second launch: the only ops.attn_fwd call with fewer queries than keys"""
+    from hunyuanvideo_efficiency_amd import ops
+    inner = ops.attn_fwd
+    return _patch_attr(ops, "attn_fwd", lambda q, k, *a, **kw: None if q.shape[0] < k.shape[0] else inner(q, k, *a, **kw))
+
+
+def _mutant_fp8_over_all_rows():
+    """under fp8_attention, segment 1 run over [0, S) (in a workspace of its own: the caller's is sized for cu1)"""
+    from hunyuanvideo_efficiency_amd import ops
+    inner = ops.attn_fwd_fp8
+    return _patch_attr(ops, "attn_fwd_fp8", lambda q, k, v, out, n_heads, scale=None, workspace=None:
+                       inner(_all_rows(q), _all_rows(k), _all_rows(v), _all_rows(out), n_heads, scale, None))
+
+
+def _mutant_plan_keyed_on_s_img():
+    """a plan cache keyed on the token COUNT: the plan of the previous grid is reused at equal s_img"""
+    from hunyuanvideo_efficiency_amd.modules import models
+    inner = models.model_plan
+
+    def model_plan(model, grid, device):
+        if getattr(model, "sliding_tile", None) is None:
+            return None
+        cache = model.__dict__.setdefault("_stale_plans", {})
+        n = grid[0] * grid[1] * grid[2]
+        if n not in cache:
+            cache[n] = inner(model, grid, device)
+        return cache[n]
+    return _patch_attr(models, "model_plan", model_plan)
+
+
 # ------------------------------------------------------------------------------------------------------------------ mutants
 # Each is a context manager that mis-wires the host code (or the double it calls) the way a slip of the pen would; `check` names the
 # check that must reject it and `case` where.  "A" = check_stages, "A block call surfaces" = the tolerance part of
@@ -536,7 +732,8 @@ def _patch_attr(obj, name, value):
 def _mutant_cu1(delta):
     from hunyuanvideo_efficiency_amd.modules import models
     inner = models.segment_attention_
-    return _patch_attr(models, "segment_attention_", lambda sp, qkv, cat, s_img, cu1, heads, d: inner(sp, qkv, cat, s_img, cu1 + delta, heads, d))
+    return _patch_attr(models, "segment_attention_",
+                       lambda sp, qkv, cat, s_img, cu1, heads, d, **kw: inner(sp, qkv, cat, s_img, cu1 + delta, heads, d, **kw))
 
 
 def _mutant_refiner_n_valid(delta):
@@ -630,6 +827,20 @@ MUTANTS = {
     "shift<->scale": (lambda m: _mutant_mod_chunks([(0, 1), (3, 4)]), "A block call surfaces", _MID, "surface.double.img"),
     "refiner cache ignores _version": (lambda m: _mutant_cache_ignores_version(), "B6 cache", None, None),
     "batch row b reads row 0's mask": (lambda m: _mutant_batch_row0_mask(), "B7 batch", None, None),
+    # the opt-in attention paths: the segment check ((s_img, n_valid)) on the ops call sites of segment_attention_, B1 on the real blocks
+    # under the flag, the grid change
+    "sta dense=(s_img, S)": (lambda m: _mutant_tile_dense("to-S"), "segment sta", (45, 1), None),
+    "sta dense=(s_img, S) (forward)": (lambda m: _mutant_tile_dense("to-S"), "B1 padding content", STA_CASES[0], None),
+    "sta dense=(s_img + 1, cu1)": (lambda m: _mutant_tile_dense("lo+1"), "segment sta", (45, 1), None),
+    "sta text queries not launched": (lambda m: _mutant_text_queries_not_launched(), "segment sta", (45, 1), None),
+    "sta plan of the previous grid reused": (lambda m: _mutant_plan_keyed_on_s_img(), "grid change", None, None),
+    "fp8attn segment 1 over [0, S)": (lambda m: _mutant_fp8_over_all_rows(), "segment fp8attn", (45, 1), None),
+    "fp8attn segment 1 over [0, S) (forward)": (lambda m: _mutant_fp8_over_all_rows(), "B1 padding content", FP8ATTN_CASES[0], None),
+    "sta cu1+1": (lambda m: _mutant_cu1(+1), "segment sta", (45, 11), None),
+    "sta cu1-1": (lambda m: _mutant_cu1(-1), "segment sta", (45, 11), None),
+    "fp8attn cu1+1": (lambda m: _mutant_cu1(+1), "segment fp8attn", (45, 11), None),
+    "fp8attn cu1-1": (lambda m: _mutant_cu1(-1), "segment fp8attn", (45, 11), None),
+    "sta cu1+1 (forward)": (lambda m: _mutant_cu1(+1), "B1 padding content", STA_CASES[0], None),
 }
 
 
@@ -639,7 +850,11 @@ def run_named_check(h: Harness, check: str, case: Optional[Case]):
         return check_cache(h)
     if check == "B7 batch":
         return check_batch(h)
-    model = h.model(case.model_kind)
+    if check == "grid change":
+        return check_grid_change(h)
+    if check.startswith("segment "):
+        return check_segment_attention(h.dev, check.split()[1], *case)
+    model = flag_model(h, case) if case.flag else h.model(case.model_kind)
     if check == "B2 block call surfaces":
         return check_block_call_surfaces(h, model, case)
     if check == "A block call surfaces":
@@ -653,6 +868,73 @@ def run_named_check(h: Harness, check: str, case: Optional[Case]):
     if check == "B3 rope table edge":
         return check_rope_table_edge(h, model, case, inp, out)
     raise KeyError(check)
+
+
+# ------------------------------------------------------------------------------------------------------------------ segment level
+# attenion.segment_attention_ under tile_plan / fp8_attention on a qkv buffer made here: every output row against the fp64 reference of ITS
+# key set, and B8 - what the segment bounds promise bit for bit.  Device-agnostic: the CPU tier runs it on the doubles, where every
+# mutant of MUTANTS assigned to "segment .." (an ops call site of the host function with one slip of the pen) must be rejected; the GPU
+# tier runs it on the HIP kernels.  The function under test is looked up as modules.models.segment_attention_, the name the blocks call.
+SEGMENT_GEOS = {1: ((1, 1, 1), (1, 1, 1), (1, 1, 1)), 45: ((3, 3, 5), (2, 2, 2), (1, 1, 3)), 320: ((5, 8, 8), (4, 8, 8), (1, 1, 1))}
+SEGMENT_S_TXT = 32
+
+
+def check_segment_attention(dev, flag: str, s_img: int, n_valid: int, heads: int = 2) -> float:
+    """flag "sta" or "fp8attn"; returns the worst error / bound.  Bounds: tests/attention_bounds.AttnRef (the double: rounded_q=False),
+    for the FP8 rows of segment 1 tests/attn_fp8_ref.fp8_bound over the workspace the call filled."""
+    from hunyuanvideo_efficiency_amd import ops
+    from hunyuanvideo_efficiency_amd.modules import models
+    from tests import attention_bounds as AB
+    from tests import attn_fp8_ref as F8
+    from tests.attn_tile_plans import allowed
+    grid, tile, window = SEGMENT_GEOS[s_img]
+    s_txt, d, on_gpu = SEGMENT_S_TXT, heads * 128, str(dev) != "cpu"
+    cu1, S = s_img + n_valid, s_img + s_txt
+    q, k, v = AB.make_case("random", S, S, heads, f"wiring.segment.{s_img}")
+    base = torch.cat([q, k, v], 1)
+    ws = torch.empty(ops.attn_fp8_layout(S, S, heads)["total"], dtype=torch.uint8, device=dev)      # grow-only in the model: may be larger than (cu1, H) needs
+    kw = dict(tile_plan=ops.tile_plan(grid, tile, window, dev)) if flag == "sta" else dict(fp8_attention=True, fp8_workspace=ws)
+
+    def run(qkv):
+        cat = torch.full((S, d + 64), 7.0, dtype=BF16, device=dev)
+        models.segment_attention_(None, qkv.to(dev), cat, s_img, cu1, heads, d, **kw)
+        assert bool((cat[:, d:] == 7.0).all()), "columns behind d were written"
+        return cat[:, :d].cpu()
+
+    def edited(row):
+        e = base.clone()
+        e[row, d:] = (e[row, d:].float() * -0.5 + 0.75).to(BF16)          # k and v of one row
+        return e
+
+    out = run(base)
+    ok, tid = allowed(grid, tile, window)
+    tiles = [(tid == t).nonzero()[:, 0] for t in tid.unique().tolist()]
+    groups = [(list(range(cu1, S)), list(range(cu1, S)))] if S > cu1 else []                       # (query rows, key rows)
+    worst = 0.0
+    if flag == "sta":
+        groups += [(r.tolist(), ok[r[0]].nonzero()[:, 0].tolist() + list(range(s_img, cu1))) for r in tiles]
+        groups += [(list(range(s_img, cu1)), list(range(cu1)))] if n_valid else []
+    elif cu1:
+        worst = F8.check_fwd(out[:cu1], ws.cpu(), cu1, cu1, heads, f"segment 1 under fp8_attention (s_img {s_img}, n_valid {n_valid})")
+    for rows, keys in groups:
+        ref = AB.AttnRef(q[rows], k[keys], v[keys], heads, gap=AB.THR, rounded_q=on_gpu)
+        worst = max(worst, ref.check_o(out[rows], f"{flag} s_img {s_img} n_valid {n_valid}: rows {rows[0]}..{rows[-1]}"))
+    # B8: both sides of cu1, and under the window one image token
+    if cu1 < S:
+        o2 = run(edited(cu1))
+        assert bits_equal(out[:cu1], o2[:cu1]), f"{flag}: k / v of row cu1 (the first padding row) reach rows [0, cu1)"
+        assert not bits_equal(out[cu1:], o2[cu1:]), f"{flag}: k / v of row cu1 do not change the padding rows"
+    if n_valid > 0:
+        assert not bits_equal(out[:s_img], run(edited(cu1 - 1))[:s_img]), f"{flag}: k / v of row cu1 - 1 (the last valid text row) do not reach the image rows"
+    if flag == "sta":
+        j = s_img // 2
+        o3 = run(edited(j))
+        for r in tiles:
+            sees = bool(ok[r[0], j])
+            assert bits_equal(out[r], o3[r]) != sees, f"sta: image token {j} {'does not reach' if sees else 'reaches'} the tile of row {int(r[0])}"
+        if n_valid:
+            assert all(not bits_equal(out[r:r + 1], o3[r:r + 1]) for r in range(s_img, cu1)), f"sta: image token {j} does not reach every valid text row"
+    return worst
 
 
 def report(h: Harness) -> str:

@@ -32,6 +32,8 @@ from hunyuanvideo_efficiency_amd import synthetic as syn
 from oracle import dit_ref as R
 from tests import activation_bounds as ACT
 from tests import attention_bounds as AB
+from tests import attn_fp8_ref as F8
+from tests import attn_tile_plans as TP
 from tests import conv_bounds as CB
 from tests import cpu_kernel_doubles as KD
 from tests import error_bounds as EB
@@ -74,6 +76,8 @@ class Call:
     same: Dict[int, torch.Tensor] = field(default_factory=dict)      # position in the flattened return -> the tensor it must BE
     ref: Any = None                                                  # what the bounded check needs (CPU tensors)
     post: Optional[Callable] = None                                  # (ret, call, peer) -> {name: tensor}: derived values, compared as returns
+    opaque: tuple = ()                                               # positions in the flattened return whose bytes are not compared as a whole
+                                                                     # (a workspace with scratch areas: `post` names what a caller may read)
 
 
 @dataclass
@@ -212,7 +216,8 @@ def compare_call(real, double, case: Case, real_device="cuda", double_device="cp
     # values
     if case.cls in ("copy", "exact"):
         pairs = [(f"buffer {k!r}", a.after[k], b.after[k]) for k in a.after]
-        pairs += [(f"return element {i}", bits(x), bits(y)) for i, (x, y) in enumerate(zip(a.flat, b.flat)) if isinstance(x, torch.Tensor)]
+        pairs += [(f"return element {i}", bits(x), bits(y)) for i, (x, y) in enumerate(zip(a.flat, b.flat))
+                  if isinstance(x, torch.Tensor) and i not in a.call.opaque]
         pairs += [(f"derived {k!r}", bits(a.derived[k]), bits(b.derived[k])) for k in a.derived]
         for nm, x, y in pairs:
             if case.any_nan:
@@ -1137,6 +1142,106 @@ case("ops.attn_fwd", "random-321x449-no-split-workspace", "bounded", _attn_check
 case("sp.attn_fwd", "random-321x65", "bounded", _attn_check)(lambda dev: _attn_random(dev, "sp", 321, 65, None))
 
 
+# ---- the opt-in attention paths.  Sliding-tile: a ragged ops.tile_plan plan (reference key sets from attn_tile_plans.allowed) and a
+# hand-built one (shuffled perm, a tile listed twice, a tile without keys; reference key sets from the hand-written lists).
+TILE_GEO = ((3, 5, 9), (2, 2, 4), (2, 1, 2))          # ragged in all three axes: tiles of 16, 8, 4, 2 and 1 tokens
+TILE_HAND = (TP.hashed_perm(193, "dp.hand"), [65, 1, 63, 64], [[[1, 0, 1], [], [0, 3, 3], [2]]])
+
+
+def _attn_tile(dev, kind, scale=None):
+    m = Mem(dev)
+    H = 2
+    if kind == "tile_plan":
+        grid, tile, window = TILE_GEO
+        n_img, n_dense = math.prod(grid), 5
+        plan, dense = real_fn("ops.tile_plan")(grid, tile, window, dev), (n_img, n_img + n_dense)
+        ok, tid = TP.allowed(grid, tile, window)
+        groups = [((tid == t).nonzero()[:, 0].tolist(), ok[(tid == t).nonzero()[0, 0]].nonzero()[:, 0].tolist() + list(range(*dense)))
+                  for t in tid.unique().tolist()]
+    else:
+        perm, sizes, lists = TILE_HAND
+        n_img, n_dense, dense = len(perm), 0, (0, 0)
+        plan = TP.hand_plan(perm, sizes, lists, dev)
+        groups = [([perm[s] for s in TP.slots(sizes, t)], TP.key_rows(perm, sizes, lists[0][t], dense)) for t in range(len(sizes))]
+    q, k, v = AB.make_case("random", n_img, n_img + n_dense + 2, H, f"dp.tile.{kind}")      # two rows behind the dense range: never a key
+    Q, K, V = _fused(m, q, k, v, H)
+    o = m.out("out", n_img + 2, H * 128, BF16, pad=64)[:n_img]          # rows behind n_img and the pad columns keep their bits
+    kw = {"dense": dense} if scale is None else {"dense": dense, "scale": scale}
+    return Call((Q, K[:n_img + n_dense], V[:n_img + n_dense], o, H, plan), kw, m.watch, {0: o}, (q, k, v, H, scale, groups))
+
+
+def _attn_tile_check(call, flat, derived, peer, is_double):
+    q, k, v, H, scale, groups = call.ref
+    got, worst = _out0(flat), 0.0
+    for rows, keys in groups:
+        if not keys:
+            assert bool((got[rows].view(torch.int16) == 0).all()), "attn_fwd_tile: a tile without keys must get rows of zero bits"
+            continue
+        ref = AB.AttnRef(q[rows], k[keys], v[keys], H, scale=scale, gap=AB.THR, rounded_q=not is_double)
+        worst = max(worst, ref.check_o(got[rows], f"attn_fwd_tile rows {rows[:3]}.."))
+    return worst
+
+
+case("ops.attn_fwd_tile", "tile_plan-ragged-3x5x9", "bounded", _attn_tile_check)(lambda dev: _attn_tile(dev, "tile_plan"))
+case("ops.attn_fwd_tile", "hand-built-twice-empty-shuffled", "bounded", _attn_tile_check)(lambda dev: _attn_tile(dev, "hand"))
+case("ops.attn_fwd_tile", f"hand-built-scale={ATTN_SCALE}", "bounded", _attn_tile_check)(lambda dev: _attn_tile(dev, "hand", ATTN_SCALE))
+
+
+# FP8 attention.  The quantiser: the named workspace areas bit for bit through attn_fp8_ref.unpack (the scratch area `part` and the
+# alignment gaps are nobody's to read), the bytes behind workspace_bytes untouched, the given workspace returned.  The forward: each side
+# inside attn_fp8_ref.fp8_bound over ITS OWN dequantised workspace.
+FP8_ATTN_SHAPE = (33, 129, 2)           # n_q, n_kv (three key tiles, the last of one key), heads
+
+
+def _fp8_workspace(dev, n_q, n_kv, H, tail=512):
+    from hunyuanvideo_efficiency_amd.attn_fp8 import attn_fp8_layout
+    need = attn_fp8_layout(n_q, n_kv, H)["total"]
+    return torch.full((need + tail,), 0x5A, dtype=torch.uint8, device=dev), need
+
+
+def _fp8_areas(ret, call, peer):
+    n_q, n_kv, H, need = call.ref[:4]
+    ws = call.kwargs["workspace"]
+    out = {k: _cpu(a).contiguous().view(torch.uint8) if a.dtype == FP8 else _cpu(a) for k, a in F8.unpack(ws, n_q, n_kv, H).items()}
+    out["behind-workspace_bytes"] = _cpu(ws[need:])
+    return out
+
+
+def _fp8_quantise(dev, scale=None):
+    m = Mem(dev)
+    n_q, n_kv, H = FP8_ATTN_SHAPE
+    q, k, v = AB.make_case("random", n_q, n_kv, H, "dp.fp8q")
+    q[0] = 0                                            # an all-zero row: scale 1, codes 0
+    v[:, 5] = 0                                         # an all-zero channel of V
+    Q, K, V = _fused(m, q, k, v, H)
+    ws, need = _fp8_workspace(dev, n_q, n_kv, H)
+    kw = {"workspace": ws} if scale is None else {"workspace": ws, "scale": scale}
+    return Call((Q, K, V, H), kw, m.watch, {0: ws}, (n_q, n_kv, H, need), _fp8_areas, opaque=(0,))
+
+
+case("ops.attn_fp8_quantise", "given-workspace-33x129", "copy")(lambda dev: _fp8_quantise(dev))
+case("ops.attn_fp8_quantise", f"given-workspace-scale={ATTN_SCALE}", "copy")(lambda dev: _fp8_quantise(dev, ATTN_SCALE))
+
+
+def _fp8_fwd(dev, cls):
+    m = Mem(dev)
+    n_q, n_kv, H = FP8_ATTN_SHAPE
+    Q, K, V = _fused(m, *AB.make_case(cls, n_q, n_kv, H, "dp.fp8f"), H)
+    ws, need = _fp8_workspace(dev, n_q, n_kv, H)
+    o = m.out("out", n_q, H * 128, BF16, pad=64)
+    return Call((Q, K, V, o, H), {"workspace": ws}, m.watch, {0: o}, (n_q, n_kv, H, need, ws))
+
+
+def _fp8_fwd_check(call, flat, derived, peer, is_double):
+    n_q, n_kv, H, need, ws = call.ref
+    assert bool((ws[need:] == 0x5A).all()), "attn_fwd_fp8: bytes behind workspace_bytes were written"
+    return F8.check_fwd(_out0(flat), ws.cpu(), n_q, n_kv, H, "attn_fwd_fp8")
+
+
+for _cls in ("random", "peaked"):
+    case("ops.attn_fwd_fp8", f"{_cls}-33x129", "bounded", _fp8_fwd_check)(lambda dev, c=_cls: _fp8_fwd(dev, c))
+
+
 def _attn_partial_random(dev, space, n_q, n_kv, splits, merge):
     m = Mem(dev)
     H = 2
@@ -1339,6 +1444,50 @@ _rg("v-inner-stride-2", lambda m: (lambda Q, K, V, o, H: ((Q, K, stride2(V), o, 
     "ops.attn_fwd")
 
 
+def _legal_tile(m, sizes=(3, 2), lists=(((1,), (0, 1)),), plan_dev=None):
+    """five image tokens in two tiles, three dense keys behind them; the plan may be for other sizes, other lists or another device"""
+    H = 2
+    q, k, v = AB.make_case("random", 5, 8, H, "ref.tile")
+    n = sum(sizes)
+    perm = [(3 * i + 1) % n for i in range(n)] if n % 3 else list(range(n))
+    plan = TP.hand_plan(perm, list(sizes), [[list(l) for l in per] for per in lists], m.dev if plan_dev is None else plan_dev)
+    return m.rows("q", q), m.rows("k", k), m.rows("v", v), m.out("out", 5, H * 128, BF16, pad=64), H, plan
+
+
+def _other_device(dev):
+    return "meta" if str(dev) == "cpu" else "cpu"          # the CPU tier has one real device: a meta plan stands for "elsewhere"
+
+
+_TL = "ops.attn_fwd_tile"
+_rg("plan-for-another-n_img", lambda m: (lambda Q, K, V, o, H, p: ((Q, K, V, o, H, p), {"dense": (5, 8)}))(*_legal_tile(m, sizes=(3, 3))), _TL)
+_rg("plan-on-another-device", lambda m: (lambda Q, K, V, o, H, p: ((Q, K, V, o, H, p), {"dense": (5, 8)}))(*_legal_tile(m, plan_dev=_other_device(m.dev))), _TL)
+_rg("n_lists-not-1-or-H", lambda m: (lambda Q, K, V, o, H, p: ((Q, K, V, o, H, p), {"dense": (5, 8)}))(*_legal_tile(m, lists=(((1,), (0, 1)),) * 3)), _TL)
+_rg("k-wrong-dtype", lambda m: (lambda Q, K, V, o, H, p: ((Q, K.view(F16), V, o, H, p), {"dense": (5, 8)}))(*_legal_tile(m)), _TL)
+_rg("out-rows-disagree", lambda m: (lambda Q, K, V, o, H, p: ((Q, K, V, o[:4], H, p), {"dense": (5, 8)}))(*_legal_tile(m)), _TL)
+_rg("dense-range-behind-n_kv", lambda m: (lambda Q, K, V, o, H, p: ((Q, K, V, o, H, p), {"dense": (5, 9)}))(*_legal_tile(m)), _TL)
+_rg("fewer-keys-than-queries", lambda m: (lambda Q, K, V, o, H, p: ((Q, K[:4], V[:4], o, H, p), {"dense": (0, 0)}))(*_legal_tile(m)), _TL)
+
+
+def _legal_fp8(m, extra=512):
+    H = 2
+    q, k, v = AB.make_case("random", 5, 65, H, "ref.fp8")
+    ws, need = _fp8_workspace(m.dev, 5, 65, H, tail=extra)
+    m.watch["workspace"] = ws
+    return m.rows("q", q), m.rows("k", k), m.rows("v", v), m.out("out", 5, H * 128, BF16, pad=64), H, ws, need
+
+
+for _op in ("ops.attn_fwd_fp8", "ops.attn_fp8_quantise"):
+    _a = (lambda Q, K, V, o, H: (Q, K, V, o, H)) if _op == "ops.attn_fwd_fp8" else (lambda Q, K, V, o, H: (Q, K, V, H))
+    _rg("short-workspace", lambda m, a=_a: (lambda Q, K, V, o, H, ws, need: (a(Q, K, V, o, H), {"workspace": ws[:need - 1]}))(*_legal_fp8(m)), _op)
+    _rg("workspace-not-contiguous", lambda m, a=_a: (lambda Q, K, V, o, H, ws, need: (a(Q, K, V, o, H), {"workspace": ws[::2]}))(
+        *_legal_fp8(m, extra=70000)), _op)
+    _rg("workspace-wrong-dtype", lambda m, a=_a: (lambda Q, K, V, o, H, ws, need: (a(Q, K, V, o, H), {"workspace": ws.view(torch.int8)}))(*_legal_fp8(m)), _op)
+    _rg("workspace-not-a-vector", lambda m, a=_a: (lambda Q, K, V, o, H, ws, need: (a(Q, K, V, o, H), {"workspace": ws[:need // 256 * 256].view(-1, 256)}))(
+        *_legal_fp8(m)), _op)
+    _rg("k-wrong-dtype", lambda m, a=_a: (lambda Q, K, V, o, H, ws, need: (a(Q, K.view(F16), V, o, H), {"workspace": ws}))(*_legal_fp8(m)), _op)
+_rg("out-rows-disagree", lambda m: (lambda Q, K, V, o, H, ws, need: ((Q, K, V, o[:4], H), {"workspace": ws}))(*_legal_fp8(m)), "ops.attn_fwd_fp8")
+
+
 def _legal_copy3d(m):
     return m.rows("src", special_16((10, 40), "ref.copy3d", BF16), pad=8), m.out("dst", 14, 24, BF16, c0=8, pad=8)
 
@@ -1497,6 +1646,24 @@ REFUSAL_ERRORS = {
     "ops.attn_fwd:k-wrong-dtype": "TypeError",
     "ops.attn_fwd:q-stride-breaks-16-byte-rule": "HVKernelError",
     "ops.attn_fwd:v-inner-stride-2": "ValueError",
+    "ops.attn_fwd_tile:plan-for-another-n_img": "ValueError",
+    "ops.attn_fwd_tile:plan-on-another-device": "ValueError",
+    "ops.attn_fwd_tile:n_lists-not-1-or-H": "ValueError",
+    "ops.attn_fwd_tile:k-wrong-dtype": "TypeError",
+    "ops.attn_fwd_tile:out-rows-disagree": "AssertionError",
+    "ops.attn_fwd_tile:dense-range-behind-n_kv": "HVKernelError",
+    "ops.attn_fwd_tile:fewer-keys-than-queries": "HVKernelError",
+    "ops.attn_fwd_fp8:short-workspace": "ValueError",
+    "ops.attn_fwd_fp8:workspace-not-contiguous": "ValueError",
+    "ops.attn_fwd_fp8:workspace-wrong-dtype": "TypeError",
+    "ops.attn_fwd_fp8:workspace-not-a-vector": "ValueError",
+    "ops.attn_fwd_fp8:k-wrong-dtype": "TypeError",
+    "ops.attn_fwd_fp8:out-rows-disagree": "AssertionError",
+    "ops.attn_fp8_quantise:short-workspace": "ValueError",
+    "ops.attn_fp8_quantise:workspace-not-contiguous": "ValueError",
+    "ops.attn_fp8_quantise:workspace-wrong-dtype": "TypeError",
+    "ops.attn_fp8_quantise:workspace-not-a-vector": "ValueError",
+    "ops.attn_fp8_quantise:k-wrong-dtype": "TypeError",
     "ops.copy3d:cols-not-multiple-of-8": "HVKernelError",
     "ops.copy3d:dst_ld-below-cols": "HVKernelError",
     "ops.copy3d:src_ld-breaks-8-element-rule": "HVKernelError",

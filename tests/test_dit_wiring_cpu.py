@@ -1,7 +1,10 @@
 """CPU: the checks of tests/dit_wiring.py on the REAL host code (modules/models.py, token_refiner.py, attenion.py, layers.py) with
 the kernels replaced by the CPU doubles (tests/cpu_kernel_doubles.py): (1) the correct wiring passes every check at every case;
 (2) every mutant - a deliberately mis-wired variant of the host code - is rejected by the check named for it, and one that only a
-tolerance can see exceeds that tolerance at least 2x here, so that the rounding of the HIP kernels cannot hide it.  No GPU."""
+tolerance can see exceeds that tolerance at least 2x here, so that the rounding of the HIP kernels cannot hide it; (3) segment_attention_
+under tile_plan and under fp8_attention (dit_wiring.check_segment_attention) at s_img 1, 45, 320 x n_valid 0, 1, 32; (4) the model under
+enable_sliding_tile_attention against the windowed oracle and under enable_fp8_attention (STA_CASES, FP8ATTN_CASES), the grid change at
+equal s_img, re-keying, batch rows, the RuntimeError of a block without a plan; their mutants are entries of MUTANTS.  No GPU."""
 import pytest
 import torch
 
@@ -56,7 +59,7 @@ def test_fp8_mfma_configuration(world, i):
 def test_mutant_is_rejected(world, name):
     make, check, case, stage = W.MUTANTS[name]
     h = W.Harness("cpu")                          # its own models and no entry in the ratio report
-    model = h.model(case.model_kind if case is not None else "tiny")
+    model = h.model(case.model_kind if isinstance(case, W.Case) else "tiny")
     if check.startswith("A"):
         clean = W.run_named_check(h, check, case)
         assert clean[stage] <= 1.0
@@ -70,6 +73,38 @@ def test_mutant_is_rejected(world, name):
         with pytest.raises(AssertionError) as e:
             W.run_named_check(h, check, case)
     print(f"[dit wiring] mutant {name}: rejected by {check}: {e.value}")
+
+
+@pytest.mark.parametrize("n_valid", [0, 1, W.SEGMENT_S_TXT])
+@pytest.mark.parametrize("s_img", sorted(W.SEGMENT_GEOS))
+@pytest.mark.parametrize("flag", ["sta", "fp8attn"])
+def test_segment_attention_under_the_opt_in_flags(world, flag, s_img, n_valid):
+    r = W.check_segment_attention("cpu", flag, s_img, n_valid)
+    print(f"[dit wiring] segment attention {flag} s_img {s_img} n_valid {n_valid}: worst error / bound {r:.3f} (doubles)")
+
+
+@pytest.mark.parametrize("case", W.STA_CASES + W.FP8ATTN_CASES, ids=lambda c: c.name)
+def test_opt_in_attention_case(world, case):
+    W.check_flag_case(world, case)
+
+
+def test_sliding_tile_plan_follows_a_grid_change_at_equal_s_img(world):
+    W.check_grid_change(world)
+
+
+def test_block_forward_without_a_plan_raises(world):
+    W.check_no_plan_raises(world)
+
+
+@pytest.mark.parametrize("flag", ["sta", "fp8attn"])
+def test_rekey_under_the_opt_in_flags(world, flag):
+    W.check_flag_rekey(world, flag)
+
+
+@pytest.mark.parametrize("flag", ["sta", "fp8attn"])
+def test_batch_rows_under_the_opt_in_flags(world, flag):
+    W.flag_model(world, W.STA_CASES[0] if flag == "sta" else W.FP8ATTN_CASES[0])
+    W.check_batch(world, flag)
 
 
 def test_zz_ratio_report(world):

@@ -1,10 +1,11 @@
 """GPU: the opt-in FP8 attention of include/hv_attn_fp8.h.
 
 (1) The quantiser, bit for bit: means, scales and e4m3 bytes of the workspace equal a torch restatement in fp32 in the header's order
-(`restate`), after the header's V permutation and transposition are undone (`unpack`).
+(`restate`), after the header's V permutation and transposition are undone (`unpack`); both live in tests/attn_fp8_ref.py, which the
+CPU doubles share.
 
 (2) The kernel against fp64 attention over the DEQUANTISED operands (sq Q8, sk K8, sv V8, log2 domain), element by element.  With w_j
-the fp64 softmax weights, l = sum_j 2^(s_j - M) >= 1 and v~ the dequantised V, the bound per output element d is
+the fp64 softmax weights, l = sum_j 2^(s_j - M) >= 1 and v~ the dequantised V, the bound per output element d is (attn_fp8_ref.fp8_bound)
 
     ulp_bf16(O64_d)                                                   the final rounding (EB.ulp_out)
   + sum_j max(2^-4 w_j, 2^-18 / l) |v~_jd|                            e4m3(p 2^8): half an ulp relative (3 mantissa bits) down to
@@ -22,8 +23,6 @@ outside 2^-4 |v|), `phantom` the tail mask, `flat` P = 1 everywhere.
 
 (3) The tiny model with enable_fp8_attention against itself without: different bytes (the path is taken) within 1e-1 of the output range,
 the figure tests/test_gpu_fp8_mfma.py uses for an FP8 approximation against non-FP8 semantics; the flag with an SP object raises."""
-import math
-
 import pytest
 import torch
 
@@ -31,13 +30,11 @@ pytestmark = pytest.mark.gpu
 
 from hunyuanvideo_efficiency_amd import synthetic as syn  # noqa: E402
 from tests import attention_bounds as AB  # noqa: E402
-from tests import error_bounds as EB  # noqa: E402
+from tests.attn_fp8_ref import dequantised, fp8_bound, restate, unpack  # noqa: E402
 
 DEV = "cuda"
 FP8 = torch.float8_e4m3fn
 D, KVT = 128, 64
-P = torch.arange(KVT)
-V_KEY = 32 * ((P >> 4) & 1) + 8 * ((P >> 2) & 3) + 4 * (P >> 5) + (P & 3)      # the header's key(p)
 
 
 @pytest.fixture(scope="module")
@@ -54,50 +51,6 @@ def fused(q, k, v, H):
     return buf[:q.shape[0], :H * D], buf[:k.shape[0], H * D:2 * H * D], buf[:k.shape[0], 2 * H * D:]
 
 
-def unpack(ops, ws, n_q, n_kv, H):
-    """the workspace areas in natural order: kmean, sv [H, 128], sk [H, nt], sq [n_q, H] fp32; q8 [n_q, H, 128], k8, v8 [H, nt 64, 128] e4m3"""
-    L = ops.attn_fp8_layout(n_q, n_kv, H)
-    nt = L["nt"]
-    area = lambda name, n, dtype: ws[L[name]:L[name] + n * torch.empty(0, dtype=dtype).element_size()].view(dtype)
-    v8 = area("v8", H * nt * 8192, FP8).view(H, nt, D, KVT)
-    v_nat = torch.empty(H, nt, KVT, D, dtype=FP8, device=ws.device)
-    v_nat.view(torch.uint8)[:, :, V_KEY.to(ws.device)] = v8.view(torch.uint8).transpose(2, 3)
-    return dict(kmean=area("kmean", H * D, torch.float32).view(H, D), sv=area("sv", H * D, torch.float32).view(H, D),
-                sk=area("sk", H * nt, torch.float32).view(H, nt), sq=area("sq", n_q * H, torch.float32).view(n_q, H),
-                q8=area("q8", n_q * H * D, FP8).view(n_q, H, D), k8=area("k8", H * nt * 8192, FP8).view(H, nt * KVT, D),
-                v8=v_nat.view(H, nt * KVT, D))
-
-
-def restate(q, k, v, H, blk):
-    """the header's quantisation rules in fp32 torch, natural order (q [n_q, H 128], k, v [n_kv, H 128] bf16 on the CPU)"""
-    f32 = lambda x: torch.tensor(x, dtype=torch.float32)
-    scale_of = lambda a: torch.where(a > 0, torch.clamp(a * (f32(1.0) / f32(448.0)), min=2.0 ** -126), torch.ones_like(a))
-    code = lambda x, s: (x * (f32(1.0) / s)).clamp(-448.0, 448.0).to(FP8)
-    n_q, n_kv, nt = q.shape[0], k.shape[0], -(-k.shape[0] // KVT)
-    kf, vf = k.float().view(n_kv, H, D), v.float().view(n_kv, H, D)
-    total, vmax = torch.zeros(H, D), torch.zeros(H, D)
-    for b0 in range(0, n_kv, blk):
-        sums, maxs = [], []
-        for c in range(4):
-            s, m = torch.zeros(H, D), torch.zeros(H, D)
-            for j in range(b0 + c, min(b0 + blk, n_kv), 4):
-                s, m = s + kf[j], torch.maximum(m, vf[j].abs())
-            sums.append(s), maxs.append(m)
-        total = total + ((sums[0] + sums[1]) + (sums[2] + sums[3]))
-        vmax = torch.maximum(vmax, torch.stack(maxs).max(dim=0).values)
-    kmean, sv = total / f32(float(n_kv)), scale_of(vmax)
-    qp = q.float().view(n_q, H, D) * AB.scale_log2e()
-    sq = scale_of(qp.abs().amax(dim=2))
-    kc = torch.zeros(nt * KVT, H, D)
-    kc[:n_kv] = kf - kmean
-    sk = scale_of(kc.view(nt, KVT, H, D).abs().amax(dim=(1, 3))).T.contiguous()                    # [H, nt]
-    v_pad = torch.zeros(nt * KVT, H, D)
-    v_pad[:n_kv] = vf
-    return dict(kmean=kmean, sv=sv, sk=sk, sq=sq, q8=code(qp, sq[:, :, None]),
-                k8=code(kc.view(nt, KVT, H, D), sk.T[:, None, :, None]).view(nt * KVT, H, D).transpose(0, 1),
-                v8=code(v_pad, sv[None]).transpose(0, 1))
-
-
 @pytest.mark.parametrize("H", [1, 3])
 @pytest.mark.parametrize("n_kv", [1, 63, 64, 65, 129])
 def test_quantiser_bit_exact(ops, n_kv, H):
@@ -107,28 +60,12 @@ def test_quantiser_bit_exact(ops, n_kv, H):
     q[1] = (q[1].float() * 2.0 ** -120).to(q.dtype)     # amax below 448 * 2^-126: the scale floor
     v[:, 5] = 0                                         # an all-zero channel of V
     ws = ops.attn_fp8_quantise(*fused(q, k, v, H), H)
-    got, want = unpack(ops, ws, n_q, n_kv, H), restate(q, k, v, H, ops.ATTN_FP8["HV_ATTN_FP8_STAT_KEYS"])
+    got, want = unpack(ws, n_q, n_kv, H), restate(q, k, v, H, ops.ATTN_FP8["HV_ATTN_FP8_STAT_KEYS"])
     assert float(want["sq"][0, 0]) == 1.0 and float(want["sq"][1, 0]) == 2.0 ** -126 and float(want["sv"][0, 5]) == 1.0
     for name, w in want.items():
         g = got[name].cpu()
         same = torch.equal(g.view(torch.uint8), w.contiguous().view(torch.uint8)) if w.dtype == FP8 else torch.equal(g, w)
         assert same, f"{name} differs from the restatement (n_kv {n_kv}, {H} heads)"
-
-
-def fp8_bound(qd, kd, vd, n_kv):
-    """one head, fp64: dequantised q' [n_q, 128], k, v [n_kv, 128] -> (O64, bound); the module docstring's terms"""
-    ref = EB.Ref().add(qd, kd)
-    s = ref.y
-    M = s.max(dim=1, keepdim=True).values
-    e = torch.exp2(s - M)
-    l = e.sum(dim=1, keepdim=True)
-    w = e / l
-    O = w @ vd
-    p8 = torch.maximum(2.0 ** -4 * w, 2.0 ** -18 / l.expand_as(w)) @ vd.abs()
-    bs = EB.C * math.sqrt(D) * EB.EPS32 * ref.s + 2.0 ** -22 * (s.abs() + M.abs())
-    eta = AB._eta_term((AB.LN2 * bs + 2.0 ** -22) * w, vd, O)
-    acc = EB.C * math.sqrt(n_kv) * EB.EPS32 * (w @ vd.abs() + 2.0 * O.abs())
-    return O, EB.ulp_out(O, torch.bfloat16) + p8 + eta + acc
 
 
 BM, RING = 256, 3
@@ -145,13 +82,10 @@ def test_kernel_within_fp64_bound(ops, n_q, n_kv, H, cls):
     ws = torch.empty(ops.attn_fp8_workspace_bytes(n_q, n_kv, H) + 512, dtype=torch.uint8, device=DEV)
     ops.attn_fwd_fp8(q, k, v, out[:, :H * D], H, workspace=ws)
     assert bool((out[:, H * D:] == 7.0).all()), "guard columns behind the output were written"
-    u = unpack(ops, ws, n_q, n_kv, H)
+    u = unpack(ws, n_q, n_kv, H)
     worst = 0.0
     for h in range(H):
-        qd = u["q8"][:, h].float().double() * u["sq"][:, h, None].double()
-        kd = (u["k8"][h].float().double() * u["sk"][h].double().repeat_interleave(KVT)[:, None])[:n_kv]
-        vd = (u["v8"][h].float().double() * u["sv"][h].double())[:n_kv]
-        O, bound = fp8_bound(qd, kd, vd, n_kv)
+        O, bound = fp8_bound(*dequantised(u, h, n_kv), n_kv)
         got = out[:, h * D:(h + 1) * D].double()
         assert bool(torch.isfinite(got).all())
         ratio = (got - O).abs() / bound

@@ -1,7 +1,7 @@
 """GPU: the opt-in sliding-tile attention of include/hv_attn_tile.h.
 
 (1) The kernel element by element against fp64 masked attention.  The mask is restated here from (grid, tile, window) with index arithmetic
-of its own (`allowed`), not read from the plan tensors the kernel consumes: a query may see the image tokens whose tile lies in the clamped
+of its own (`allowed`, tests/attn_tile_plans.py), not read from the plan tensors the kernel consumes: a query may see the image tokens whose tile lies in the clamped
 window of its own tile, and the dense range.  Per query tile and head the allowed keys are gathered and handed to AB.AttnRef with
 gap = AB.THR (the kernel's running maximum is never deferred: within the contract's threshold); the bound is that of the dense kernel,
 tests/attention_bounds.py, unchanged.  `peaked` puts dominant keys inside some tiles' windows and outside others' (and one behind the dense
@@ -19,6 +19,7 @@ pytestmark = pytest.mark.gpu
 
 from hunyuanvideo_efficiency_amd import synthetic as syn  # noqa: E402
 from tests import attention_bounds as AB  # noqa: E402
+from tests.attn_tile_plans import allowed  # noqa: E402
 
 DEV = "cuda"
 D = 128
@@ -34,17 +35,6 @@ def ops():
     from hunyuanvideo_efficiency_amd import ops as _ops, _lib
     _lib.torch_ops()
     return _ops
-
-
-def allowed(grid, tile, window):
-    """-> ([n_img, n_img] bool: may query i see key j, [n_img] tile id of each token), tokens in (t, h, w) raster order"""
-    g, tl, w = torch.tensor(grid), torch.tensor(tile), torch.tensor(window)
-    tc = torch.stack(torch.meshgrid(*[torch.arange(x) for x in grid], indexing="ij"), -1).reshape(-1, 3) // tl
-    nt = -(-g // tl)
-    n = torch.minimum(w, nt)                                   # tiles per axis actually attended
-    lo = torch.minimum((tc - w // 2).clamp(min=0), nt - n)     # the window starts w // 2 before the tile, pushed back inside the grid
-    ok = ((tc[None] >= lo[:, None]) & (tc[None] < (lo + n)[:, None])).all(-1)
-    return ok, (tc[:, 0] * nt[1] + tc[:, 1]) * nt[2] + tc[:, 2]
 
 
 def check_case(ops, grid, tile, windows, n_dense, H, cls):

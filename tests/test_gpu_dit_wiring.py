@@ -13,6 +13,25 @@ MI355X, largest error / tolerance over all cases (test_zz_ratio_report prints th
   dit_vec 0.008, patch_embed 0.000, token_refiner 0.111, double_block img 0.198 / txt 0.202, single_block 0.170,
   final_layer + unpatchify 0.056; block call surfaces (vec half-width 1.5): double img 0.206 / txt 0.205, single 0.169;
   whole output 6.6e-3 of range (0.22 of 3e-2), FP8-MFMA configuration 7.4e-3 (0.25).
+
+Segment level (dit_wiring.check_segment_attention): attenion.segment_attention_ under tile_plan and under fp8_attention on a qkv buffer
+made by the test, s_img 1, 45, 320 x n_valid 0, 1, s_txt = 32.  Every output row against the fp64 reference of its own key set (image
+rows: the window restated by attn_tile_plans.allowed plus [s_img, cu1); valid-text rows: [0, cu1); padding rows: [cu1, S); AttnRef's
+bound, under FP8 attn_fp8_ref.fp8_bound over the workspace the call filled), then B8 bitwise: k / v of row cu1 leave rows [0, cu1)
+bit-equal and change the padding rows, row cu1 - 1 changes image rows, one image token changes exactly the tiles whose window holds it
+and every valid-text row.  MI355X, worst error / bound: tile_plan 0.523, fp8_attention 0.709 (s_img 1, n_valid 1).
+
+Model level under the opt-in flags (dit_wiring.STA_CASES, FP8ATTN_CASES; the tiny config).  enable_sliding_tile_attention: A against the
+WINDOWED oracle (oracle.dit_ref.attention_varlen replaced for segment 1 by R.sdpa with the mask attn_tile_plans.allowed restates, plus
+the valid text; text queries see all of [0, cu1)) at the block tolerance, the whole output at 3e-2 of range, B1, B3, B4; re-keying
+between two grids; a grid change at equal s_img (latent (2, 8, 16), (4, 8, 8), the first again: the second run has the bits of a fresh
+model, the third those of the first); batch rows; block.forward without a plan raises.  enable_fp8_attention: the whole output within
+1e-1 of the range of the unflagged oracle, B1, B4, re-keying larger -> smaller -> larger (the grow-only workspace reused), batch rows.
+MI355X: under the window no stage above the figures of the first paragraph (double_block img 0.198), whole output 6.6e-3 of range (0.22 of
+3e-2, one tile of one chunk, n_valid 1); under FP8 attention whole output 6.6e-3 of range (0.066 of 1e-1).
+The mutants (dit_wiring.MUTANTS: dense=(s_img, S), dense=(s_img + 1, cu1), text queries not launched, the plan of the previous grid
+reused, FP8 over [0, S), cu1 +- 1 under either flag) patch the ops call sites, models.model_plan or models.segment_attention_, and
+are rejected on the CPU tier only (tests/test_dit_wiring_cpu.py).
 """
 import pytest
 
@@ -60,7 +79,45 @@ def test_fp8_mfma_configuration(world, i):
     W.check_fp8_case(world, W.FP8_CASES[i], W.FP8_CASES[(i + 1) % len(W.FP8_CASES)])
 
 
+@pytest.mark.parametrize("case", W.STA_CASES + W.FP8ATTN_CASES, ids=lambda c: c.name)
+def test_opt_in_attention_case(world, case):
+    W.check_flag_case(world, case)
+
+
+def test_sliding_tile_plan_follows_a_grid_change_at_equal_s_img(world):
+    W.check_grid_change(world)
+
+
+def test_block_forward_without_a_plan_raises(world):
+    W.check_no_plan_raises(world)
+
+
+@pytest.mark.parametrize("flag", ["sta", "fp8attn"])
+def test_rekey_under_the_opt_in_flags(world, flag):
+    W.check_flag_rekey(world, flag)
+
+
+@pytest.mark.parametrize("flag", ["sta", "fp8attn"])
+def test_batch_rows_under_the_opt_in_flags(world, flag):
+    W.flag_model(world, W.STA_CASES[0] if flag == "sta" else W.FP8ATTN_CASES[0])
+    W.check_batch(world, flag)
+
+
+SEGMENT_RATIOS = {}
+
+
+@pytest.mark.parametrize("n_valid", [0, 1, W.SEGMENT_S_TXT])
+@pytest.mark.parametrize("s_img", sorted(W.SEGMENT_GEOS))
+@pytest.mark.parametrize("flag", ["sta", "fp8attn"])
+def test_segment_attention_under_the_opt_in_flags(flag, s_img, n_valid):
+    r = W.check_segment_attention(DEV, flag, s_img, n_valid)
+    SEGMENT_RATIOS[flag] = max(SEGMENT_RATIOS.get(flag, 0.0), r)
+    print(f"[dit wiring] segment attention {flag} s_img {s_img} n_valid {n_valid}: worst error / bound {r:.3f}")
+
+
 def test_zz_ratio_report(world):
     assert world.ratios, "run with the case tests"
     print("\n" + W.report(world))
+    for flag, r in sorted(SEGMENT_RATIOS.items()):
+        print(f"[dit wiring]   segment attention under {flag:<8s} {r:.3f}  (worst error / fp64 bound)")
     assert all(v <= 1.0 for v, _ in world.ratios.values())

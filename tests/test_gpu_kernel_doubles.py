@@ -29,6 +29,13 @@ Class and check per op (copy / exact: bit equality; bounded: the named check, pa
            conv_cout4 affine + SiLU          conv_bounds.cout4_act / cout4_ref, rowwise_bounds.check
            softmax_rows (random)             rowwise_bounds.softmax_ref / check
            attn_fwd, attn_partial, attn_merge  attention_bounds.AttnRef.check_o / check_partial / merge_ratio (double: rounded_q=False)
+           attn_fwd_tile                     AttnRef.check_o per (tile, head) on the key rows with multiplicity (a ragged ops.tile_plan plan:
+                                             from attn_tile_plans.allowed; a hand-built plan with a shuffled perm, a tile listed twice and a
+                                             tile without keys, whose rows must be zero bits: from the hand-written lists)
+           attn_fwd_fp8                      attn_fp8_ref.fp8_bound over the side's OWN dequantised workspace
+  copy     attn_fp8_quantise                 the named workspace areas (kmean, sv, sk, sq, q8, k8, v8 through attn_fp8_ref.unpack) bit for
+                                             bit, the bytes behind workspace_bytes untouched, the given workspace returned; the scratch
+                                             area `part` and the alignment gaps are not compared (Call.opaque)
 
 Measured on an MI355X, the largest error-to-bound ratio per op as printed by test_zz_ratio_report (kernel / double):
   ops.attn_fwd 0.605 / 0.473      ops.attn_partial 0.579 / 0.461      ops.attn_merge 0.500 / 0.500       sp.attn_fwd 0.380 / 0.413
@@ -36,6 +43,7 @@ Measured on an MI355X, the largest error-to-bound ratio per op as printed by tes
   ops.linear_smallm 0.484 / 0.484 ops.ln_modulate 0.499 / 0.499       ops.ln_modulate_fp8 0.499 / 0.499  ops.masked_mean 0.500 / 0.500
   ops.qknorm_rope_ 0.500 / 0.500  ops.timestep_embedding 0.499 / 0.499  vae_ops.conv_cout4 0.471 / 0.471  vae_ops.softmax_rows 0.499 / 0.499
   vae_ops.groupnorm_apply 0.499 / 0.499   vae_ops.groupnorm_affine 0.002 / 0.002   vae_ops.groupnorm_affine_from_stats 0.001 / 0.001
+  ops.attn_fwd_tile 0.523 / 0.526   ops.attn_fwd_fp8 0.262 / 0.262   ops.attn_fp8_quantise: bit-equal
 (ratios of 0.5 are the final rounding's half ulp: kernel and double are then both the correctly rounded fp64 value.)  Every copy and
 exact case is bit-equal.  The conversions to bf16 (patchify, fp8_dequant of the two NaN codes) keep a NaN a NaN in the same cell; the
 kernel writes 0x7FC0 where torch's conversion writes 0xFFFF, so those cases compare NaNs as NaNs (Case.any_nan) and everything else bit

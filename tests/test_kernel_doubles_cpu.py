@@ -3,7 +3,8 @@ they replace, the shared case table of tests/double_parity.py held to cover ever
 and the parity harness shown to reject each way a double can drift.  The kernel side of every case is tests/test_gpu_kernel_doubles.py.
 
   surface      inspect.signature of every double equals its wrapper's: names, order, defaults (EXTRA_HOOKS lists the trailing test hooks)
-  coverage     every double has a case in double_parity.CASES; every public wrapper that launches a kernel has a double or a NO_DOUBLE reason
+  coverage     every double has a case in double_parity.CASES; every public wrapper that launches a kernel - defined in ops / vae_ops or
+               re-exported there from a sibling module - has a double or a NO_DOUBLE reason
   exactness    every "exact" case evaluated in fp64 with the same rounding points, and with the K / channel order reversed, gives the bits
                of its fp32 evaluation: bit equality is then the right demand on the GPU
   teeth        compare_call with the pristine double as the kernel and a mutated copy as the double: each mutant rejected by the named check
@@ -24,6 +25,7 @@ from tests.test_ulysses_gloo import CpuKernelDouble
 
 BF16 = torch.bfloat16
 EXTRA_HOOKS = {"vae_ops.softmax_rows": ["mutant"]}          # trailing parameters a double may have on top of its wrapper's
+PACKAGE = ops.__name__.rsplit(".", 1)[0]                     # the census follows re-exports inside the package, not stray imports
 SP_METHODS = sorted(n for n, v in vars(CpuKernelDouble).items() if isinstance(v, staticmethod))
 
 
@@ -73,7 +75,9 @@ def test_every_launching_wrapper_has_a_double_or_a_reason():
     launching = set()
     for mod, space in ((ops, "ops"), (vae_ops, "vae_ops")):
         for name, f in vars(mod).items():
-            if inspect.isfunction(f) and f.__module__ == mod.__name__ and not name.startswith("_") and "_lib.call(" in inspect.getsource(f):
+            # whatever module defines it: a wrapper that lives in a sibling module and is re-exported (attn_tile.py, attn_fp8.py) counts
+            if (inspect.isfunction(f) and f.__module__.startswith(PACKAGE + ".") and not name.startswith("_")
+                    and "_lib.call(" in inspect.getsource(f)):
                 launching.add(f"{space}.{name}")
     assert launching, "no launching wrapper found: the scan is broken"
     assert not sorted(launching - doubled - set(P.NO_DOUBLE)), f"wrappers with neither a double nor a NO_DOUBLE reason: {sorted(launching - doubled - set(P.NO_DOUBLE))}"
@@ -84,7 +88,7 @@ def test_every_launching_wrapper_has_a_double_or_a_reason():
 
 def test_refusal_table_covers_the_ops_the_host_hands_views_to():
     need = {"ops.gemm", "ops.gemm_fp8", "ops.ln_modulate", "ops.ln_modulate_fp8", "ops.quant_rows_fp8", "ops.qknorm_rope_", "ops.attn_fwd",
-            "ops.copy3d", "vae_ops.gemm_f16", "vae_ops.conv3d_causal", "vae_ops.groupnorm_apply", "vae_ops.softmax_rows"}
+            "ops.attn_fwd_tile", "ops.attn_fwd_fp8", "ops.copy3d", "vae_ops.gemm_f16", "vae_ops.conv3d_causal", "vae_ops.groupnorm_apply", "vae_ops.softmax_rows"}
     assert need <= {r.op for r in P.REFUSALS}
     assert len({r.id for r in P.REFUSALS}) == len(P.REFUSALS)
 
@@ -220,6 +224,18 @@ def m_gemm_returns_a_fresh_tensor(*a, **kw):
     return KD.gemm(*a, **kw).clone()
 
 
+def m_tile_counts_every_key_once(q, k, v, out, n_heads, plan, dense=(0, 0), scale=None):
+    return KD._attn_fwd_tile(q, k, v, out, n_heads, plan, dense, scale, mutant="keys-once")
+
+
+def m_tile_perm_on_keys_but_not_on_the_output_scatter(q, k, v, out, n_heads, plan, dense=(0, 0), scale=None):
+    return KD._attn_fwd_tile(q, k, v, out, n_heads, plan, dense, scale, mutant="no-output-scatter")
+
+
+def m_tile_without_keys_is_0_over_0(q, k, v, out, n_heads, plan, dense=(0, 0), scale=None):
+    return KD._attn_fwd_tile(q, k, v, out, n_heads, plan, dense, scale, mutant="empty-is-0/0")
+
+
 MUTANTS = [      # (case id, mutant, the check that must catch it)
     ("ops.unpatchify:out-given", m_unpatchify_ignores_out, "written-set"),
     (f"ops.attn_fwd:random-321x449-scale={P.ATTN_SCALE}", m_attn_ignores_scale, "bounded"),
@@ -229,6 +245,9 @@ MUTANTS = [      # (case id, mutant, the check that must catch it)
     ("ops.quant_rows_fp8:given-outputs-long-scale", m_quant_writes_scales_behind_m, "written-set"),
     ("ops.copy3d:batched-strided", m_copy3d_strides_swapped, "written-set"),
     ("ops.gemm:B3-bias", m_gemm_returns_a_fresh_tensor, "return-identity"),
+    ("ops.attn_fwd_tile:hand-built-twice-empty-shuffled", m_tile_counts_every_key_once, "bounded"),
+    ("ops.attn_fwd_tile:hand-built-twice-empty-shuffled", m_tile_perm_on_keys_but_not_on_the_output_scatter, "bounded"),
+    ("ops.attn_fwd_tile:hand-built-twice-empty-shuffled", m_tile_without_keys_is_0_over_0, "bounded"),
 ]
 
 
