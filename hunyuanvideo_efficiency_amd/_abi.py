@@ -104,3 +104,10 @@ if not os.path.exists(ATTN_TILE_HEADER):
     raise HVKernelError(f"{ATTN_TILE_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
 with open(ATTN_TILE_HEADER) as _f:
     ATTN_TILE_DECLS, ATTN_TILE_MACROS = parse(_f.read())
+
+# include/hv_gemm_mx4.h: the MXFP4 block-scaled GEMM and its quantisers (csrc/hv_gemm_mx4.hip), declared and parsed the same way
+GEMM_MX4_HEADER = os.path.join(os.path.dirname(HEADER), "hv_gemm_mx4.h")
+if not os.path.exists(GEMM_MX4_HEADER):
+    raise HVKernelError(f"{GEMM_MX4_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
+with open(GEMM_MX4_HEADER) as _f:
+    GEMM_MX4_DECLS, GEMM_MX4_MACROS = parse(_f.read())

@@ -20,6 +20,7 @@
 //     tiles form a 4(M) x 8(N) patch (A and W panels are shared inside an XCD).
 // Algorithmic work: 2*M*N*K flop; HBM bytes >= 2*(M*K + N*K + M*N).
 #include "hv_common.hpp"
+#include "hv_tile_order.hpp"
 #include "../../include/hv_kernels.h"
 #include <cstdlib>
 #include <type_traits>
@@ -37,7 +38,6 @@ constexpr int BM = 256, BK = 64;                 // BN is a template parameter: 
 constexpr int TILE_BYTES = BM * BK * 2;          // 32 KiB per A tile (W tile: BN * BK * 2)
 template <int BN> constexpr int stage_bytes() { return TILE_BYTES + BN * BK * 2; }
 template <int BN> constexpr int lds_bytes() { return 2 * stage_bytes<BN>(); }   // double buffered: 128 KiB (BN=256) / 96 KiB (BN=128)
-constexpr int GROUP_M = 4;                       // M tiles per band of the tile order (2 ~ 4 > 8 > 16: DESIGN.md section 7)
 
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
@@ -125,30 +125,10 @@ struct IdRowMap {
     __device__ __forceinline__ int64_t operator()(int m) const { return m; }
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
 __device__ __forceinline__ int swz_a(int row) { return (row >> 1) & 7; }
 __device__ __forceinline__ int swz_w(int row) { return (((row >> 3) & 3) << 1) | ((row >> 1) & 1); }
 
 // ---- pieces shared by every main loop below
-
-// XCD-aware tile mapping (bijective for any grid size): workgroup -> linear tile index, so that each XCD (workgroup id mod 8) gets a
-// contiguous chunk of tiles
-__device__ __forceinline__ int xcd_linear_tile() {
-    const int nwg = gridDim.x;
-    const int bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
-// banded tile order: linear index -> (tm, tn), M fastest inside a band of GROUP_M M-tiles (the last band may be shorter)
-struct TileMN { int tm, tn; };
-__device__ __forceinline__ TileMN tile_of(int lin, int tiles_m, int tiles_n) {
-    const int band = lin / (GROUP_M * tiles_n), rem = lin % (GROUP_M * tiles_n);
-    const int band_m0 = band * GROUP_M;
-    const int gm = min(GROUP_M, tiles_m - band_m0);
-    return TileMN{band_m0 + rem % gm, rem / gm};
-}
 
 // Conv gather: source coordinates of an output row (= output voxel), and the source row a tap reads from them.  Replicate / causal
 // padding = the clamps, nearest upsample = the halvings (first frame not repeated in T), stride = the coordinate multipliers.

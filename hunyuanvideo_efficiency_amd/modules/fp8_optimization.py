@@ -85,6 +85,8 @@ def convert_fp8_linear(module, dit_weight_path: Optional[str], original_dtype, p
     read with torch.load(weights_only=True) (never unpickled).  Without a checkpoint (random-init benchmarks) pass
     dit_weight_path=None: every layer is quantised from its current weights with scale = max|W|/448 - the reference's own
     fallback for non-fp8 weights (:57-62)."""
+    if getattr(module, "mxfp4_linears_converted", False):
+        raise ValueError("--use-fp8 and --mxfp4-linears exclude each other: a layer has one stored format (convert_mxfp4_linear already ran)")
     setattr(module, "fp8_matmul_enabled", True)
     if fp8_map is None and dit_weight_path is not None:
         fp8_map_path = dit_weight_path.replace(".pt", "_map.pt")

@@ -22,7 +22,7 @@ from typing import Any, Dict, List, Optional, Tuple, Union
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import gemm_mx4, ops
 from ..attn_tile import model_plan
 from .attenion import get_cu_seqlens, n_valid_text, segment_attention_, pad_segment_attention_, check_fp8_attention, check_tile_plan
 from .token_refiner import SingleTokenRefiner
@@ -47,6 +47,8 @@ class _Workspace:
         self.xq = self.xs = self.catq = self.cats = None
         self.tile_plan = None   # sliding-tile attention (opt-in): the plan of this forward's token grid, set by the transformer's forward
         self.attn8 = None       # FP8 attention (opt-in): the workspace of include/hv_attn_fp8.h, allocated on first use, grow-only
+        # MXFP4 linears (opt-in, allocated on first use): e2m1 codes + E8M0 block scales of the A operands
+        self.x4 = self.x4s = self.cat4 = self.cat4s = None
 
     def fp8_attention_workspace(self, n_rows: int, heads: int):
         need = ops.attn_fp8_workspace_bytes(n_rows, n_rows, heads)
@@ -63,6 +65,31 @@ class _Workspace:
             self.catq = torch.empty(s, self.cat.shape[1], dtype=torch.float8_e4m3fn, device=dev)
             self.cats = torch.empty(s, dtype=torch.float32, device=dev)
         return self
+
+
+    def mx4_buffers(self):
+        if self.x4 is None:
+            s, d = self.x.shape
+            c, dev = self.cat.shape[1], self.x.device
+            self.x4 = torch.empty(s, d // 2, dtype=torch.uint8, device=dev)
+            self.x4s = torch.empty(s, d // 32, dtype=torch.uint8, device=dev)
+            self.cat4 = torch.empty(s, c // 2, dtype=torch.uint8, device=dev)
+            self.cat4s = torch.empty(s, c // 32, dtype=torch.uint8, device=dev)
+        return self
+
+
+MX4 = "mx4"     # the value _linear_mode returns for the MXFP4 path (False: bf16, True: FP8 MFMA)
+
+
+def _linear_mode(block, sp, *layers):
+    """How this block's Linears run: MX4 when opted in (mxfp4_optimization.enable_mxfp4_linears) and every Linear involved is packed
+    (uint8 codes) with a reduction length hv_gemm_mxfp4 takes; else _use_fp8_mfma's answer."""
+    if getattr(block, "mxfp4_linears", False) and all(l.weight.dtype == torch.uint8 and l.in_features >= 512 and l.in_features % 128 == 0
+                                                      for l in layers):
+        if sp is not None:
+            raise NotImplementedError("MXFP4 linears are not available with sequence parallelism (the chunked QKV slices weight rows)")
+        return MX4
+    return _use_fp8_mfma(block, *layers)
 
 
 def _use_fp8_mfma(block, *layers) -> bool:
@@ -91,8 +118,11 @@ def _attention(block, sp, ws: _Workspace, s_img: int, cu1: int, H: int, d: int):
 
 
 def _ln(ws: _Workspace, lo: int, hi: int, shift, scale, fp8: bool):
-    """K1 on rows [lo, hi): bf16 into ws.xmod, or (FP8-MFMA path) e4m3 + row scales into ws.xq / ws.xs."""
-    if fp8:
+    """K1 on rows [lo, hi): bf16 into ws.xmod, or (FP8-MFMA path) e4m3 + row scales into ws.xq / ws.xs, or (MXFP4) codes + block scales."""
+    if fp8 == MX4:
+        ws.mx4_buffers()
+        gemm_mx4.ln_modulate_mxfp4(ws.x[lo:hi], shift, scale, codes=ws.x4[lo:hi], scales=ws.x4s[lo:hi])
+    elif fp8:
         ws.fp8_buffers()
         ops.ln_modulate_fp8(ws.x[lo:hi], shift, scale, out_q=ws.xq[lo:hi], out_scale=ws.xs[lo:hi])
     else:
@@ -107,6 +137,14 @@ def _gemm(ws: _Workspace, layer, src: str, lo: int, hi: int, fp8: bool, wrows: O
     d = ws.x.shape[1]
     cols = {"xmod": None, "attn": slice(0, d), "hid": slice(d, None), "cat": slice(None)}[src]
     b = layer.bias if wrows is None or layer.bias is None else layer.bias[wrows]
+    if fp8 == MX4:       # MXFP4: LayerNorm outputs are already codes; the other A operands are quantised here, per block of 32
+        ws.mx4_buffers()
+        if src == "xmod":
+            a4, a4s = ws.x4[lo:hi], ws.x4s[lo:hi]
+        else:
+            c0, c1 = cols.indices(ws.cat.shape[1])[:2]
+            a4, a4s = gemm_mx4.quant_rows_mxfp4(ws.cat[lo:hi, cols], codes=ws.cat4[lo:hi, c0 // 2:c1 // 2], scales=ws.cat4s[lo:hi, c0 // 32:c1 // 32])
+        return gemm_mx4.gemm_mxfp4(a4, a4s, layer.weight, layer.mx_scale, b, **epi)
     if not fp8:
         a = ws.xmod[lo:hi] if src == "xmod" else ws.cat[lo:hi, cols]
         w = layer.w()
@@ -185,7 +223,7 @@ class MMDoubleStreamBlock(nn.Module):
         check_tile_plan(ws.tile_plan if getattr(self, "sliding_tile", False) else None, bool(getattr(self, "fp8_attention", False)), sp)
         overlap = sp is not None and hasattr(sp, "send") and H % 2 == 0
         mods = {}
-        fp8 = {s: _use_fp8_mfma(self, getattr(self, f"{s}_attn_qkv"), getattr(self, f"{s}_attn_proj"), getattr(self, f"{s}_mlp").fc1,
+        fp8 = {s: _linear_mode(self, sp, getattr(self, f"{s}_attn_qkv"), getattr(self, f"{s}_attn_proj"), getattr(self, f"{s}_mlp").fc1,
                                 getattr(self, f"{s}_mlp").fc2) for s in ("img", "txt")}
         for s, lo, hi, n_rope in streams:
             mod = getattr(self, f"{s}_mod")
@@ -272,10 +310,10 @@ class MMSingleStreamBlock(nn.Module):
         d, H = self.hidden_size, self.heads_num
         m = ops.linear_smallm(vec, self.modulation.linear.w(), self.modulation.linear.bias, silu_in=True)
         shift, scale, gate = m[0, :d], m[0, d:2 * d], m[0, 2 * d:]
-        fp8 = _use_fp8_mfma(self, self.linear1, self.linear2)
+        sp = self.hybrid_seq_parallel_attn
+        fp8 = _linear_mode(self, sp, self.linear1, self.linear2)
         s_all = ws.x.shape[0]
         _ln(ws, 0, s_all, shift, scale, fp8)
-        sp = self.hybrid_seq_parallel_attn
         check_fp8_attention(bool(getattr(self, "fp8_attention", False)), sp)
         check_tile_plan(ws.tile_plan if getattr(self, "sliding_tile", False) else None, bool(getattr(self, "fp8_attention", False)), sp)
         n_rope = s_img if cos is not None else 0

@@ -45,6 +45,9 @@ def parse_args(argv=None):
     p.add_argument("--cfg-scale", type=float, default=1.0)
     p.add_argument("--embedded-cfg-scale", type=float, default=6.0)
     p.add_argument("--use-fp8", action="store_true")
+    p.add_argument("--mxfp4-linears", action="store_true", help="pack the block GEMM weights as MXFP4 (e2m1 codes, one E8M0 scale per 32) and "
+                   "run them with MXFP4 activations on the CDNA4 block-scaled matrix cores (include/hv_gemm_mx4.h) - an opt-in approximation "
+                   "whose video fidelity has not been measured; not available with --use-fp8 or --ulysses-degree / --ring-degree > 1")
     p.add_argument("--fp8-attention", action="store_true", help="run the main attention segment of every block with Q, K, V and P in "
                    "e4m3 on the CDNA4 FP8 matrix cores (include/hv_attn_fp8.h) - an opt-in approximation, independent of --use-fp8; not "
                    "available with --ulysses-degree / --ring-degree > 1")
@@ -87,6 +90,8 @@ def parse_args(argv=None):
     a = p.parse_args(argv)
     if (a.sta_tile is not None or a.sta_window is not None) and not a.sliding_tile_attention:
         p.error("--sta-tile and --sta-window are only valid with --sliding-tile-attention")
+    if a.mxfp4_linears and a.use_fp8:
+        p.error("--mxfp4-linears and --use-fp8 exclude each other: a layer has one stored format")
     if a.save_chroma is not None and a.save_format not in ("y4m", "yuv"):
         p.error("--save-chroma is only valid with --save-format y4m or yuv")
     if a.save_quality is not None and a.save_format != "avi":
@@ -131,6 +136,10 @@ def main(argv=None):
         checkpoint.load_state_dict(a, model, a.model_base)
     elif a.use_fp8:
         convert_fp8_linear(model, None, torch.bfloat16)
+    if a.mxfp4_linears:
+        from hunyuanvideo_efficiency_amd.modules.mxfp4_optimization import convert_mxfp4_linear, enable_mxfp4_linears
+        convert_mxfp4_linear(model)
+        enable_mxfp4_linears(model)
     if a.fp8_attention:
         from hunyuanvideo_efficiency_amd.modules.fp8_optimization import enable_fp8_attention
         enable_fp8_attention(model)
