@@ -111,3 +111,10 @@ if not os.path.exists(GEMM_MX4_HEADER):
     raise HVKernelError(f"{GEMM_MX4_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
 with open(GEMM_MX4_HEADER) as _f:
     GEMM_MX4_DECLS, GEMM_MX4_MACROS = parse(_f.read())
+
+# include/hv_gemm_mx6.h: the MXFP6 block-scaled GEMM and its quantisers (csrc/hv_gemm_mx6.hip), declared and parsed the same way
+GEMM_MX6_HEADER = os.path.join(os.path.dirname(HEADER), "hv_gemm_mx6.h")
+if not os.path.exists(GEMM_MX6_HEADER):
+    raise HVKernelError(f"{GEMM_MX6_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
+with open(GEMM_MX6_HEADER) as _f:
+    GEMM_MX6_DECLS, GEMM_MX6_MACROS = parse(_f.read())

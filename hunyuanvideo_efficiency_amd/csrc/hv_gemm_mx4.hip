@@ -27,10 +27,9 @@
 // load rises into the counted waits.
 #include "hv_common.hpp"
 #include "hv_ln_row.hpp"
+#include "hv_mx_tile.hpp"
 #include "hv_tile_order.hpp"
 #include "../../include/hv_gemm_mx4.h"
-#include <type_traits>
-#include <utility>
 
 namespace {
 
@@ -44,21 +43,7 @@ constexpr int OPS_PER_STAGE = 5;                     // vector-memory operations
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
-struct Mx4Args {
-    const uint8_t *A, *As, *W, *Ws;
-    int64_t lda, ldas, ldw, ldws;
-    const uint16_t* bias;
-    int M, N, K;
-    uint16_t* out0; int64_t ld0; int act0;
-    int n_split;
-    uint16_t* out1; int64_t ld1; int act1;
-    const uint16_t* gate;
-    const uint16_t* res; int64_t ld_res;
-    int tiles_m, tiles_n;
-};
-
-template <int... I, typename F>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
+using Mx4Args = MxGemmArgs;        // hv_mx_tile.hpp: argument block, W row deal and epilogue shared with hv_gemm_mx6.hip
 
 // one scaled FP4 matrix instruction: 4-register operands travel in the low half of the builtin's 8-register type (cbsz = blgp = 4
 // makes the instruction read 4); OW / OA = byte of the scale register (op_sel), an immediate
@@ -67,68 +52,6 @@ __device__ __forceinline__ f32x4 mfma_mx4(i32x4 w, int sw, i32x4 a, int sa, f32x
     const i32x4 z = {0, 0, 0, 0};
     return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(__builtin_shufflevector(w, z, 0, 1, 2, 3, 4, 5, 6, 7),
                                                             __builtin_shufflevector(a, z, 0, 1, 2, 3, 4, 5, 6, 7), c, 4, 4, OW, sw, OA, sa);
-}
-
-// W row (inside the 256-row tile) held by LDS row lr = wn * 64 + ni * 16 + i
-__device__ __forceinline__ int w_tile_row(int lr) {
-    const int wn = lr >> 6, ni = (lr >> 4) & 3, i = lr & 15;
-    return wn * 64 + (ni >> 1) * 32 + (i >> 2) * 8 + (ni & 1) * 4 + (i & 3);
-}
-
-// bf16 epilogue of hv_gemm.hip (bias, activation on the rounded value, gated residual, column split), 8 consecutive n per lane
-__device__ __forceinline__ void mx4_epilogue(const Mx4Args& g, f32x4 (&acc)[8][4], int mrow0, int ncol0, int fq) {
-    int64_t orow[8];                        // clamped rows are loaded, never stored
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi) orow[mi] = min(mrow0 + mi * 16, g.M - 1);
-#pragma unroll
-    for (int np = 0; np < 2; ++np) {
-        const int n = ncol0 + np * 32 + fq * 8;
-        if (n >= g.N) continue;
-        float b[8], gt[8];
-        u32x4 rraw[8];
-        if (g.res) {
-#pragma unroll
-            for (int mi = 0; mi < 8; ++mi) rraw[mi] = *reinterpret_cast<const u32x4*>(g.res + orow[mi] * g.ld_res + n);
-        }
-        if (g.bias) unpack8(*reinterpret_cast<const u32x4*>(g.bias + n), b);
-        else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) b[j] = 0.f;
-        }
-        if (g.gate) unpack8(*reinterpret_cast<const u32x4*>(g.gate + n), gt);
-        const bool second = n >= g.n_split;
-        uint16_t* obase = second ? g.out1 + (n - g.n_split) : g.out0 + n;
-        const int64_t ldo = second ? g.ld1 : g.ld0;
-        const int act = second ? g.act1 : g.act0;
-#pragma unroll
-        for (int mi = 0; mi < 8; ++mi) {
-            float v[8];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                v[r] = acc[mi][2 * np][r] + b[r];
-                v[4 + r] = acc[mi][2 * np + 1][r] + b[4 + r];
-            }
-            if (act == 1) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = gelu_tanh_f(rbf(v[j]));
-            } else if (act == 2) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = silu_f(rbf(v[j]));
-            }
-            if (g.res) {
-                float rs[8];
-                unpack8(rraw[mi], rs);
-                if (g.gate) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = rs[j] + rbf(rbf(v[j]) * gt[j]);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = rs[j] + rbf(v[j]);
-                }
-            }
-            if (mrow0 + mi * 16 < g.M) *reinterpret_cast<u32x4*>(obase + orow[mi] * ldo) = pack8(v);
-        }
-    }
 }
 
 __global__ __launch_bounds__(512, 2) void gemm_mx4_kernel(Mx4Args g) {
@@ -315,7 +238,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mx4_kernel(Mx4Args g) {
     Mx4Args ge = g;
     asm volatile("s_waitcnt vmcnt(0)" : "+s"(ge.bias), "+s"(ge.gate), "+s"(ge.res), "+s"(ge.out0), "+s"(ge.out1) : : "memory");
     __builtin_amdgcn_sched_barrier(0);
-    mx4_epilogue(ge, acc, m0 + wm * 128 + fr, n0 + wn * 64, fq);
+    mx_epilogue(ge, acc, m0 + wm * 128 + fr, n0 + wn * 64, fq);
 }
 
 // ------------------------------------------------------------------------------------------------ quantisers
@@ -433,27 +356,10 @@ extern "C" int hv_gemm_mxfp4(const void* A_codes, int64_t lda, const void* A_sca
                              const void* W_scales, int64_t ldws, const void* bias, int M, int N, int K, void* out0, int64_t ld0, int act0,
                              int n_split, void* out1, int64_t ld1, int act1, const void* gate, const void* res, int64_t ld_res,
                              hipStream_t stream) {
-    if (!A_codes || !A_scales || !W_codes || !W_scales || !out0 || M < 0 || N <= 0 || (N & 7) || K < HV_MX4_MIN_K || (K % KS))
-        return HV_ERR_ARG;
-    if (!hv_aligned16(A_codes) || !hv_aligned16(W_codes) || (lda & 15) || (ldw & 15) || lda < 0 || ldw < 0 || lda > (1 << 23) ||
-        ldw > (1 << 23))
-        return HV_ERR_ARG;
-    if (((uintptr_t)A_scales & 3) || ((uintptr_t)W_scales & 3) || (ldas & 3) || (ldws & 3) || (ld0 & 7)) return HV_ERR_ARG;
-    if (n_split <= 0 || n_split > N) n_split = N;
-    if (n_split < N && (!out1 || (n_split & 7) || (ld1 & 7))) return HV_ERR_ARG;
-    if ((gate && !res) || (res && (ld_res & 7))) return HV_ERR_ARG;
-    if (act0 < 0 || act0 > 2 || act1 < 0 || act1 > 2) return HV_ERR_ARG;
-    if (!hv_pitch_ok(M, ld0, n_split) || (n_split < N && !hv_pitch_ok(M, ld1, N - n_split))) return HV_ERR_ARG;
     Mx4Args g{};
-    g.A = (const uint8_t*)A_codes; g.As = (const uint8_t*)A_scales; g.W = (const uint8_t*)W_codes; g.Ws = (const uint8_t*)W_scales;
-    g.lda = lda; g.ldas = ldas; g.ldw = ldw; g.ldws = ldws;
-    g.bias = (const uint16_t*)bias; g.M = M; g.N = N; g.K = K;
-    g.out0 = (uint16_t*)out0; g.ld0 = ld0; g.act0 = act0; g.n_split = n_split;
-    g.out1 = (uint16_t*)out1; g.ld1 = ld1; g.act1 = act1;
-    g.gate = (const uint16_t*)gate; g.res = (const uint16_t*)res; g.ld_res = ld_res;
-    g.tiles_m = (int)(((int64_t)M + BM - 1) / BM);
-    g.tiles_n = (N + BN - 1) / BN;
-    if (!hv_grid_x_ok((int64_t)g.tiles_m * g.tiles_n)) return HV_ERR_ARG;
+    if (K < HV_MX4_MIN_K || (K % KS) || !mx_gemm_args(g, A_codes, lda, A_scales, ldas, W_codes, ldw, W_scales, ldws, bias, M, N, K, out0, ld0, act0,
+                                                     n_split, out1, ld1, act1, gate, res, ld_res))
+        return HV_ERR_ARG;
     if (M == 0) return HV_OK;
     static HvPerDeviceOnce once;
     if (hv_set_max_lds(once, (const void*)gemm_mx4_kernel, LDS_BYTES) != HV_OK) return HV_ERR_LAUNCH;

@@ -87,6 +87,8 @@ def convert_fp8_linear(module, dit_weight_path: Optional[str], original_dtype, p
     fallback for non-fp8 weights (:57-62)."""
     if getattr(module, "mxfp4_linears_converted", False):
         raise ValueError("--use-fp8 and --mxfp4-linears exclude each other: a layer has one stored format (convert_mxfp4_linear already ran)")
+    if getattr(module, "mxfp6_linears_converted", False):
+        raise ValueError("--use-fp8 and --mxfp6-linears exclude each other: a layer has one stored format (convert_mxfp6_linear already ran)")
     setattr(module, "fp8_matmul_enabled", True)
     if fp8_map is None and dit_weight_path is not None:
         fp8_map_path = dit_weight_path.replace(".pt", "_map.pt")

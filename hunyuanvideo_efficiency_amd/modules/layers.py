@@ -34,8 +34,9 @@ class ParamLinear(nn.Module):
         single scratch per device is enough and the bf16 copy of the model never exists in HBM."""
         wt = self.weight
         if wt.dtype == torch.uint8:
-            raise RuntimeError("this Linear holds MXFP4 codes (convert_mxfp4_linear): it has no bf16 weight and runs only through "
-                               "gemm_mx4.gemm_mxfp4 - enable the path with --mxfp4-linears / enable_mxfp4_linears")
+            raise RuntimeError("this Linear holds MXFP4 or MXFP6 codes (convert_mxfp4_linear / convert_mxfp6_linear): it has no bf16 weight "
+                               "and runs only through gemm_mx4.gemm_mxfp4 / gemm_mx6.gemm_mxfp6 - enable the path with --mxfp4-linears / "
+                               "enable_mxfp4_linears or --mxfp6-linears / enable_mxfp6_linears")
         if wt.dtype != torch.float8_e4m3fn:
             return wt
         key = str(wt.device)

@@ -22,7 +22,7 @@ from typing import Any, Dict, List, Optional, Tuple, Union
 import torch
 import torch.nn as nn
 
-from .. import gemm_mx4, ops
+from .. import gemm_mx4, gemm_mx6, ops
 from ..attn_tile import model_plan
 from .attenion import get_cu_seqlens, n_valid_text, segment_attention_, pad_segment_attention_, check_fp8_attention, check_tile_plan
 from .token_refiner import SingleTokenRefiner
@@ -49,6 +49,8 @@ class _Workspace:
         self.attn8 = None       # FP8 attention (opt-in): the workspace of include/hv_attn_fp8.h, allocated on first use, grow-only
         # MXFP4 linears (opt-in, allocated on first use): e2m1 codes + E8M0 block scales of the A operands
         self.x4 = self.x4s = self.cat4 = self.cat4s = None
+        # MXFP6 linears (opt-in, allocated on first use): dense e2m3 codes (3/4 byte per element) + E8M0 block scales of the A operands
+        self.x6 = self.x6s = self.cat6 = self.cat6s = None
 
     def fp8_attention_workspace(self, n_rows: int, heads: int):
         need = ops.attn_fp8_workspace_bytes(n_rows, n_rows, heads)
@@ -78,12 +80,30 @@ class _Workspace:
         return self
 
 
+    def mx6_buffers(self):
+        if self.x6 is None:
+            s, d = self.x.shape
+            c, dev = self.cat.shape[1], self.x.device
+            self.x6 = torch.empty(s, d // 4 * 3, dtype=torch.uint8, device=dev)
+            self.x6s = torch.empty(s, d // 32, dtype=torch.uint8, device=dev)
+            self.cat6 = torch.empty(s, c // 4 * 3, dtype=torch.uint8, device=dev)
+            self.cat6s = torch.empty(s, c // 32, dtype=torch.uint8, device=dev)
+        return self
+
+
+MX6 = "mx6"     # ... and for the MXFP6 path
 MX4 = "mx4"     # the value _linear_mode returns for the MXFP4 path (False: bf16, True: FP8 MFMA)
 
 
 def _linear_mode(block, sp, *layers):
     """How this block's Linears run: MX4 when opted in (mxfp4_optimization.enable_mxfp4_linears) and every Linear involved is packed
-    (uint8 codes) with a reduction length hv_gemm_mxfp4 takes; else _use_fp8_mfma's answer."""
+    (uint8 codes) with a reduction length hv_gemm_mxfp4 takes; MX6 likewise (mxfp6_optimization.enable_mxfp6_linears, layers packed by
+    convert_mxfp6_linear, hv_gemm_mxfp6); else _use_fp8_mfma's answer."""
+    if getattr(block, "mxfp6_linears", False) and all(l.weight.dtype == torch.uint8 and getattr(l, "mx_format", 4) == 6 and
+                                                      l.in_features >= 512 and l.in_features % 128 == 0 for l in layers):
+        if sp is not None:
+            raise NotImplementedError("MXFP6 linears are not available with sequence parallelism (the chunked QKV slices weight rows)")
+        return MX6
     if getattr(block, "mxfp4_linears", False) and all(l.weight.dtype == torch.uint8 and l.in_features >= 512 and l.in_features % 128 == 0
                                                       for l in layers):
         if sp is not None:
@@ -119,7 +139,10 @@ def _attention(block, sp, ws: _Workspace, s_img: int, cu1: int, H: int, d: int):
 
 def _ln(ws: _Workspace, lo: int, hi: int, shift, scale, fp8: bool):
     """K1 on rows [lo, hi): bf16 into ws.xmod, or (FP8-MFMA path) e4m3 + row scales into ws.xq / ws.xs, or (MXFP4) codes + block scales."""
-    if fp8 == MX4:
+    if fp8 == MX6:
+        ws.mx6_buffers()
+        gemm_mx6.ln_modulate_mxfp6(ws.x[lo:hi], shift, scale, codes=ws.x6[lo:hi], scales=ws.x6s[lo:hi])
+    elif fp8 == MX4:
         ws.mx4_buffers()
         gemm_mx4.ln_modulate_mxfp4(ws.x[lo:hi], shift, scale, codes=ws.x4[lo:hi], scales=ws.x4s[lo:hi])
     elif fp8:
@@ -137,6 +160,14 @@ def _gemm(ws: _Workspace, layer, src: str, lo: int, hi: int, fp8: bool, wrows: O
     d = ws.x.shape[1]
     cols = {"xmod": None, "attn": slice(0, d), "hid": slice(d, None), "cat": slice(None)}[src]
     b = layer.bias if wrows is None or layer.bias is None else layer.bias[wrows]
+    if fp8 == MX6:       # MXFP6: as MXFP4 below, 3/4 byte per element
+        ws.mx6_buffers()
+        if src == "xmod":
+            a6, a6s = ws.x6[lo:hi], ws.x6s[lo:hi]
+        else:
+            c0, c1 = cols.indices(ws.cat.shape[1])[:2]
+            a6, a6s = gemm_mx6.quant_rows_mxfp6(ws.cat[lo:hi, cols], codes=ws.cat6[lo:hi, c0 // 4 * 3:c1 // 4 * 3], scales=ws.cat6s[lo:hi, c0 // 32:c1 // 32])
+        return gemm_mx6.gemm_mxfp6(a6, a6s, layer.weight, layer.mx_scale, b, **epi)
     if fp8 == MX4:       # MXFP4: LayerNorm outputs are already codes; the other A operands are quantised here, per block of 32
         ws.mx4_buffers()
         if src == "xmod":

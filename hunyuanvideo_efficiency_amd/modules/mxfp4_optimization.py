@@ -30,6 +30,8 @@ def convert_mxfp4_linear(module) -> int:
     format: a model converted by convert_fp8_linear is refused.  Returns the number of layers packed."""
     if getattr(module, "fp8_matmul_enabled", False):
         raise ValueError(f"{FLAG} and --use-fp8 exclude each other: a layer has one stored format (convert_fp8_linear already ran)")
+    if getattr(module, "mxfp6_linears_converted", False):
+        raise ValueError(f"{FLAG} and --mxfp6-linears exclude each other: a layer has one stored format (convert_mxfp6_linear already ran)")
     n = 0
     for block in _blocks(module):
         for layer in _gemm_linears(block):

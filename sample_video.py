@@ -48,6 +48,10 @@ def parse_args(argv=None):
     p.add_argument("--mxfp4-linears", action="store_true", help="pack the block GEMM weights as MXFP4 (e2m1 codes, one E8M0 scale per 32) and "
                    "run them with MXFP4 activations on the CDNA4 block-scaled matrix cores (include/hv_gemm_mx4.h) - an opt-in approximation "
                    "whose video fidelity has not been measured; not available with --use-fp8 or --ulysses-degree / --ring-degree > 1")
+    p.add_argument("--mxfp6-linears", action="store_true", help="pack the block GEMM weights as MXFP6 (dense 6-bit e2m3 codes, one E8M0 scale per "
+                   "32) and run them with MXFP6 activations on the CDNA4 block-scaled matrix cores (include/hv_gemm_mx6.h) - an opt-in "
+                   "approximation whose video fidelity has not been measured; not available with --use-fp8, --mxfp4-linears or "
+                   "--ulysses-degree / --ring-degree > 1")
     p.add_argument("--fp8-attention", action="store_true", help="run the main attention segment of every block with Q, K, V and P in "
                    "e4m3 on the CDNA4 FP8 matrix cores (include/hv_attn_fp8.h) - an opt-in approximation, independent of --use-fp8; not "
                    "available with --ulysses-degree / --ring-degree > 1")
@@ -92,6 +96,8 @@ def parse_args(argv=None):
         p.error("--sta-tile and --sta-window are only valid with --sliding-tile-attention")
     if a.mxfp4_linears and a.use_fp8:
         p.error("--mxfp4-linears and --use-fp8 exclude each other: a layer has one stored format")
+    if a.mxfp6_linears and (a.use_fp8 or a.mxfp4_linears):
+        p.error("--mxfp6-linears excludes --use-fp8 and --mxfp4-linears: a layer has one stored format")
     if a.save_chroma is not None and a.save_format not in ("y4m", "yuv"):
         p.error("--save-chroma is only valid with --save-format y4m or yuv")
     if a.save_quality is not None and a.save_format != "avi":
@@ -140,6 +146,10 @@ def main(argv=None):
         from hunyuanvideo_efficiency_amd.modules.mxfp4_optimization import convert_mxfp4_linear, enable_mxfp4_linears
         convert_mxfp4_linear(model)
         enable_mxfp4_linears(model)
+    if a.mxfp6_linears:
+        from hunyuanvideo_efficiency_amd.modules.mxfp6_optimization import convert_mxfp6_linear, enable_mxfp6_linears
+        convert_mxfp6_linear(model)
+        enable_mxfp6_linears(model)
     if a.fp8_attention:
         from hunyuanvideo_efficiency_amd.modules.fp8_optimization import enable_fp8_attention
         enable_fp8_attention(model)
