@@ -118,3 +118,10 @@ if not os.path.exists(GEMM_MX6_HEADER):
     raise HVKernelError(f"{GEMM_MX6_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
 with open(GEMM_MX6_HEADER) as _f:
     GEMM_MX6_DECLS, GEMM_MX6_MACROS = parse(_f.read())
+
+# include/hv_mx_rot.h: the MXFP4 quantisers behind a block-Hadamard rotation (csrc/hv_mx_rot.hip), declared and parsed the same way
+MX_ROT_HEADER = os.path.join(os.path.dirname(HEADER), "hv_mx_rot.h")
+if not os.path.exists(MX_ROT_HEADER):
+    raise HVKernelError(f"{MX_ROT_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
+with open(MX_ROT_HEADER) as _f:
+    MX_ROT_DECLS, MX_ROT_MACROS = parse(_f.read())

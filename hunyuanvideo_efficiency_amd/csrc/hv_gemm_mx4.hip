@@ -27,6 +27,7 @@
 // load rises into the counted waits.
 #include "hv_common.hpp"
 #include "hv_ln_row.hpp"
+#include "hv_mx4_quant.hpp"
 #include "hv_mx_tile.hpp"
 #include "hv_tile_order.hpp"
 #include "../../include/hv_gemm_mx4.h"
@@ -242,30 +243,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mx4_kernel(Mx4Args g) {
 }
 
 // ------------------------------------------------------------------------------------------------ quantisers
-// Four adjacent lanes hold one block of 32 (8 elements each).  Everything after the block maximum is integer work or an exact fp32
-// multiply by a power of two and compares against constants: no rounding happens here that the contract does not name.
-__device__ __forceinline__ uint32_t e2m1_code(float x, float mul) {
-    const float v = fabsf(x) * mul;
-    const uint32_t c = (uint32_t)(v > 0.25f) + (uint32_t)(v >= 0.75f) + (uint32_t)(v > 1.25f) + (uint32_t)(v >= 1.75f) +
-                       (uint32_t)(v > 2.5f) + (uint32_t)(v >= 3.5f) + (uint32_t)(v > 5.0f);
-    return c ? c | ((__float_as_uint(x) >> 28) & 8u) : 0u;
-}
-// 8 values of a lane -> its 4 code bytes; e = the block's E8M0 byte (the same in the block's four lanes)
-__device__ __forceinline__ uint32_t mx4_quant8(const float (&f)[8], uint32_t& e) {
-    uint32_t amax = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) amax = max(amax, __float_as_uint(f[j]) & 0x7FFFFFFFu);     // non-negative floats order as integers
-    amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
-    amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2, 64));
-    const uint32_t E = amax >> 23;
-    e = E > 2 ? E - 2 : 0;
-    const float mul = __uint_as_float((254u - e) << 23);         // 2^(127 - e): e <= 253, a normal number
-    uint32_t w = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) w |= e2m1_code(f[j], mul) << (4 * j);
-    return w;
-}
-
+// (the rule itself - e2m1_code, mx4_quant8 - lives in hv_mx4_quant.hpp, shared with the rotated quantisers of hv_mx_rot.hip)
 __global__ __launch_bounds__(256) void quant_rows_mx4_kernel(const bf16_t* __restrict__ x, int64_t ldx, uint8_t* __restrict__ codes,
                                                               int64_t ldq, uint8_t* __restrict__ scales, int64_t lds, int64_t M, int K) {
     const int lane = threadIdx.x & 63;
@@ -324,16 +302,11 @@ __global__ __launch_bounds__(256) void ln_mod_mx4_kernel(const bf16_t* __restric
     }
 }
 
-bool quant_args_ok(const void* x, const void* codes, const void* scales, int64_t M, int K, int64_t ldx, int64_t ldq, int64_t lds) {
-    if (!x || !codes || !scales || M < 0 || K <= 0 || (K % HV_MX4_BLOCK) || (ldx & 7) || (ldq & 15) || !hv_aligned16(codes)) return false;
-    return hv_pitch_ok(M, ldq, K / 2) && hv_pitch_ok(M, lds, K / HV_MX4_BLOCK) && hv_grid_x_ok((M + 3) / 4);
-}
-
 }  // namespace
 
 extern "C" int hv_quant_rows_mxfp4(const void* x, int64_t ldx, void* codes, int64_t ldq, void* scales, int64_t lds, int64_t M, int K,
                                    hipStream_t stream) {
-    if (!quant_args_ok(x, codes, scales, M, K, ldx, ldq, lds)) return HV_ERR_ARG;
+    if (!mx4_quant_args_ok(x, codes, scales, M, K, ldx, ldq, lds)) return HV_ERR_ARG;
     if (M == 0) return HV_OK;
     quant_rows_mx4_kernel<<<dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream>>>((const bf16_t*)x, ldx, (uint8_t*)codes, ldq,
                                                                                   (uint8_t*)scales, lds, M, K);
@@ -342,7 +315,7 @@ extern "C" int hv_quant_rows_mxfp4(const void* x, int64_t ldx, void* codes, int6
 
 extern "C" int hv_ln_modulate_mxfp4(const void* x, const void* shift, const void* scale, void* codes, int64_t ldq, void* scales,
                                     int64_t lds, int64_t M, int D, int64_t ldx, float eps, hipStream_t stream) {
-    if (!quant_args_ok(x, codes, scales, M, D, ldx, ldq, lds) || D > 4096) return HV_ERR_ARG;
+    if (!mx4_quant_args_ok(x, codes, scales, M, D, ldx, ldq, lds) || D > 4096) return HV_ERR_ARG;
     if (M == 0) return HV_OK;
     dim3 grid((unsigned)((M + 3) / 4)), block(256);
     ln_dispatch_maxc(D, [&](auto maxc) {

@@ -22,7 +22,7 @@ from typing import Any, Dict, List, Optional, Tuple, Union
 import torch
 import torch.nn as nn
 
-from .. import gemm_mx4, gemm_mx6, ops
+from .. import gemm_mx4, gemm_mx6, mx_rot, ops
 from ..attn_tile import model_plan
 from .attenion import get_cu_seqlens, n_valid_text, segment_attention_, pad_segment_attention_, check_fp8_attention, check_tile_plan
 from .token_refiner import SingleTokenRefiner
@@ -108,8 +108,19 @@ def _linear_mode(block, sp, *layers):
                                                       for l in layers):
         if sp is not None:
             raise NotImplementedError("MXFP4 linears are not available with sequence parallelism (the chunked QKV slices weight rows)")
+        _mx_rot(*layers)        # one rotation per block: mixed values are refused here
         return MX4
     return _use_fp8_mfma(block, *layers)
+
+
+def _mx_rot(*layers) -> int:
+    """The block-Hadamard group size the MXFP4 weights of these Linears were packed with (convert_mxfp4_linear(rot=...); 0 = none):
+    their A operands go through the rotated quantisers of include/hv_mx_rot.h with the same value."""
+    rots = {getattr(l, "mx_rot", 0) for l in layers}
+    if len(rots) > 1:
+        raise ValueError(f"the MXFP4 Linears of one block were packed with different rotations {sorted(rots)}: a LayerNorm output and a "
+                         "cat row are quantised once for all the Linears that read them")
+    return rots.pop()
 
 
 def _use_fp8_mfma(block, *layers) -> bool:
@@ -137,14 +148,18 @@ def _attention(block, sp, ws: _Workspace, s_img: int, cu1: int, H: int, d: int):
                        fp8_workspace=ws.fp8_attention_workspace(cu1, H) if sp is None and cu1 > 0 else None)
 
 
-def _ln(ws: _Workspace, lo: int, hi: int, shift, scale, fp8: bool):
-    """K1 on rows [lo, hi): bf16 into ws.xmod, or (FP8-MFMA path) e4m3 + row scales into ws.xq / ws.xs, or (MXFP4) codes + block scales."""
+def _ln(ws: _Workspace, lo: int, hi: int, shift, scale, fp8: bool, rot: int = 0):
+    """K1 on rows [lo, hi): bf16 into ws.xmod, or (FP8-MFMA path) e4m3 + row scales into ws.xq / ws.xs, or (MXFP4) codes + block scales,
+    rotated first when the Linear that reads them was packed with rot > 0 (_mx_rot)."""
     if fp8 == MX6:
         ws.mx6_buffers()
         gemm_mx6.ln_modulate_mxfp6(ws.x[lo:hi], shift, scale, codes=ws.x6[lo:hi], scales=ws.x6s[lo:hi])
     elif fp8 == MX4:
         ws.mx4_buffers()
-        gemm_mx4.ln_modulate_mxfp4(ws.x[lo:hi], shift, scale, codes=ws.x4[lo:hi], scales=ws.x4s[lo:hi])
+        if rot:
+            mx_rot.ln_modulate_mxfp4_rot(ws.x[lo:hi], shift, scale, rot, codes=ws.x4[lo:hi], scales=ws.x4s[lo:hi])
+        else:
+            gemm_mx4.ln_modulate_mxfp4(ws.x[lo:hi], shift, scale, codes=ws.x4[lo:hi], scales=ws.x4s[lo:hi])
     elif fp8:
         ws.fp8_buffers()
         ops.ln_modulate_fp8(ws.x[lo:hi], shift, scale, out_q=ws.xq[lo:hi], out_scale=ws.xs[lo:hi])
@@ -174,7 +189,9 @@ def _gemm(ws: _Workspace, layer, src: str, lo: int, hi: int, fp8: bool, wrows: O
             a4, a4s = ws.x4[lo:hi], ws.x4s[lo:hi]
         else:
             c0, c1 = cols.indices(ws.cat.shape[1])[:2]
-            a4, a4s = gemm_mx4.quant_rows_mxfp4(ws.cat[lo:hi, cols], codes=ws.cat4[lo:hi, c0 // 2:c1 // 2], scales=ws.cat4s[lo:hi, c0 // 32:c1 // 32])
+            out = dict(codes=ws.cat4[lo:hi, c0 // 2:c1 // 2], scales=ws.cat4s[lo:hi, c0 // 32:c1 // 32])
+            rot = _mx_rot(layer)
+            a4, a4s = mx_rot.quant_rows_mxfp4_rot(ws.cat[lo:hi, cols], rot, **out) if rot else gemm_mx4.quant_rows_mxfp4(ws.cat[lo:hi, cols], **out)
         return gemm_mx4.gemm_mxfp4(a4, a4s, layer.weight, layer.mx_scale, b, **epi)
     if not fp8:
         a = ws.xmod[lo:hi] if src == "xmod" else ws.cat[lo:hi, cols]
@@ -261,8 +278,8 @@ class MMDoubleStreamBlock(nn.Module):
             m = ops.linear_smallm(vec, mod.linear.w(), mod.linear.bias, silu_in=True)  # [1, 6d]
             mods[s] = [m[0, i * d:(i + 1) * d] for i in range(6)]   # shift1, scale1, gate1, shift2, scale2, gate2
             sh1, sc1 = mods[s][0], mods[s][1]
-            _ln(ws, lo, hi, sh1, sc1, fp8[s])
             qkv_l = getattr(self, f"{s}_attn_qkv")
+            _ln(ws, lo, hi, sh1, sc1, fp8[s], _mx_rot(qkv_l))
             qw, kw = getattr(self, f"{s}_attn_q_norm").weight, getattr(self, f"{s}_attn_k_norm").weight
             if overlap and s == "img":
                 # q / k / v as three column-chunk GEMMs; each chunk's all-to-all travels while the next chunk's GEMM runs
@@ -289,7 +306,7 @@ class MMDoubleStreamBlock(nn.Module):
                     _gemm(ws, proj, "attn", r0, r1, fp8[s], out=ws.x[r0:r1], gate=g1, res=ws.x[r0:r1])
             else:
                 _gemm(ws, proj, "attn", lo, hi, fp8[s], out=x, gate=g1, res=x)
-            _ln(ws, lo, hi, sh2, sc2, fp8[s])
+            _ln(ws, lo, hi, sh2, sc2, fp8[s], _mx_rot(mlp.fc1))
             _gemm(ws, mlp.fc1, "xmod", lo, hi, fp8[s], out=ws.cat[lo:hi, d:], act=ops.ACT_GELU_TANH)
             _gemm(ws, mlp.fc2, "hid", lo, hi, fp8[s], out=x, gate=g2, res=x)
 
@@ -344,7 +361,7 @@ class MMSingleStreamBlock(nn.Module):
         sp = self.hybrid_seq_parallel_attn
         fp8 = _linear_mode(self, sp, self.linear1, self.linear2)
         s_all = ws.x.shape[0]
-        _ln(ws, 0, s_all, shift, scale, fp8)
+        _ln(ws, 0, s_all, shift, scale, fp8, _mx_rot(self.linear1))
         check_fp8_attention(bool(getattr(self, "fp8_attention", False)), sp)
         check_tile_plan(ws.tile_plan if getattr(self, "sliding_tile", False) else None, bool(getattr(self, "fp8_attention", False)), sp)
         n_rope = s_img if cos is not None else 0

@@ -1,12 +1,14 @@
 """MXFP4 linears (opt-in; include/hv_gemm_mx4.h): pack the block GEMM weights as e2m1 codes + E8M0 block scales and run them, with
 activations quantised the same way, on v_mfma_scale_f32_16x16x128_f8f6f4.  Not the reference's arithmetic: round-to-nearest e2m1 on both
-operands carries roughly 10 % relative noise per element, and nothing here (rotations, low-rank branches, calibration) reduces it; no
-run on real weights has measured video fidelity under it."""
+operands carries roughly 10 % relative noise per element.  convert_mxfp4_linear(rot=16 / 64 / 256) rotates both operands by a
+block-diagonal Hadamard matrix along K (include/hv_mx_rot.h), which spreads outlier channels over their group and changes nothing on
+Gaussian data; nothing else here (low-rank branches, calibration) reduces the noise, and no run on real weights has measured video
+fidelity under either form."""
 from __future__ import annotations
 
 import torch
 
-from .. import gemm_mx4
+from .. import gemm_mx4, mx_rot
 from .layers import ParamLinear
 
 FLAG = "--mxfp4-linears"
@@ -24,26 +26,30 @@ def _gemm_linears(block):
                                                 getattr(block, f"{s}_mlp").fc1, getattr(block, f"{s}_mlp").fc2)]
 
 
-def convert_mxfp4_linear(module) -> int:
+def convert_mxfp4_linear(module, rot: int = 0) -> int:
     """Pack qkv / proj / fc1 / fc2 per stream of every double block and linear1 / linear2 of every single block: layer.weight becomes the
     uint8 codes [out, in / 2], layer.mx_scale the uint8 scales [out, in / 32]; the bf16 weight is released.  A layer has ONE stored
-    format: a model converted by convert_fp8_linear is refused.  Returns the number of layers packed."""
+    format: a model converted by convert_fp8_linear is refused.  rot > 0 (16, 64 or 256) packs W H instead of W, H the block-diagonal
+    Hadamard rotation of include/hv_mx_rot.h, and records layer.mx_rot: models._ln / models._gemm then quantise the layer's activations
+    through the rotated quantisers, (A H)(W H)^T = A W^T.  Returns the number of layers packed."""
+    if rot not in (0,) + mx_rot.ROTS:
+        raise ValueError(f"rot must be 0 or one of {mx_rot.ROTS}, got {rot}")
     if getattr(module, "fp8_matmul_enabled", False):
         raise ValueError(f"{FLAG} and --use-fp8 exclude each other: a layer has one stored format (convert_fp8_linear already ran)")
     if getattr(module, "mxfp6_linears_converted", False):
         raise ValueError(f"{FLAG} and --mxfp6-linears exclude each other: a layer has one stored format (convert_mxfp6_linear already ran)")
-    n = 0
-    for block in _blocks(module):
-        for layer in _gemm_linears(block):
-            assert isinstance(layer, ParamLinear)
-            if hasattr(layer, "mx_scale"):
-                continue
-            codes, scales = gemm_mx4.quant_rows_mxfp4(layer.weight.data)
-            layer.weight = torch.nn.Parameter(codes, requires_grad=False)
-            layer.mx_scale = scales
-            n += 1
+    layers = [l for block in _blocks(module) for l in _gemm_linears(block) if not hasattr(l, "mx_scale")]
+    for layer in layers:                    # refuse before the first layer is packed
+        assert isinstance(layer, ParamLinear)
+        if rot and layer.in_features % rot:
+            raise ValueError(f"rot = {rot} does not divide in_features = {layer.in_features}: rotation groups are whole")
+    for layer in layers:
+        codes, scales = mx_rot.quant_rows_mxfp4_rot(layer.weight.data, rot) if rot else gemm_mx4.quant_rows_mxfp4(layer.weight.data)
+        layer.weight = torch.nn.Parameter(codes, requires_grad=False)
+        layer.mx_scale = scales
+        layer.mx_rot = rot
     module.mxfp4_linears_converted = True
-    return n
+    return len(layers)
 
 
 def enable_mxfp4_linears(module, enable: bool = True) -> int:
