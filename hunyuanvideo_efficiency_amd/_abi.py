@@ -125,3 +125,10 @@ if not os.path.exists(MX_ROT_HEADER):
     raise HVKernelError(f"{MX_ROT_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
 with open(MX_ROT_HEADER) as _f:
     MX_ROT_DECLS, MX_ROT_MACROS = parse(_f.read())
+
+# include/hv_mx_lowrank.h: the MXFP4 GEMM with a low-rank bf16 branch and its quantise + down-project pass (csrc/hv_mx_lowrank.hip)
+MX_LOWRANK_HEADER = os.path.join(os.path.dirname(HEADER), "hv_mx_lowrank.h")
+if not os.path.exists(MX_LOWRANK_HEADER):
+    raise HVKernelError(f"{MX_LOWRANK_HEADER} is missing: hunyuanvideo_efficiency_amd runs from a source checkout")
+with open(MX_LOWRANK_HEADER) as _f:
+    MX_LOWRANK_DECLS, MX_LOWRANK_MACROS = parse(_f.read())

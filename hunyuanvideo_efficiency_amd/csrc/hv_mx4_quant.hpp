@@ -12,13 +12,15 @@ __device__ __forceinline__ uint32_t e2m1_code(float x, float mul) {
                        (uint32_t)(v > 2.5f) + (uint32_t)(v >= 3.5f) + (uint32_t)(v > 5.0f);
     return c ? c | ((__float_as_uint(x) >> 28) & 8u) : 0u;
 }
-// 8 values of a lane -> its 4 code bytes; e = the block's E8M0 byte (the same in the block's four lanes)
-__device__ __forceinline__ uint32_t mx4_quant8(const float (&f)[8], uint32_t& e) {
+// the largest magnitude of a lane's 8 values, as fp32 bits (non-negative floats order as integers)
+__device__ __forceinline__ uint32_t mx4_amax8(const float (&f)[8]) {
     uint32_t amax = 0;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) amax = max(amax, __float_as_uint(f[j]) & 0x7FFFFFFFu);     // non-negative floats order as integers
-    amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
-    amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2, 64));
+    for (int j = 0; j < 8; ++j) amax = max(amax, __float_as_uint(f[j]) & 0x7FFFFFFFu);
+    return amax;
+}
+// 8 values of a lane + the block's largest magnitude -> its 4 code bytes; e = the block's E8M0 byte
+__device__ __forceinline__ uint32_t mx4_codes8(const float (&f)[8], uint32_t amax, uint32_t& e) {
     const uint32_t E = amax >> 23;
     e = E > 2 ? E - 2 : 0;
     const float mul = __uint_as_float((254u - e) << 23);         // 2^(127 - e): e <= 253, a normal number
@@ -26,6 +28,13 @@ __device__ __forceinline__ uint32_t mx4_quant8(const float (&f)[8], uint32_t& e)
 #pragma unroll
     for (int j = 0; j < 8; ++j) w |= e2m1_code(f[j], mul) << (4 * j);
     return w;
+}
+// the same where four ADJACENT lanes hold the block (the row quantisers: one wave per row, a lane = one 16-byte load)
+__device__ __forceinline__ uint32_t mx4_quant8(const float (&f)[8], uint32_t& e) {
+    uint32_t amax = mx4_amax8(f);
+    amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
+    amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2, 64));
+    return mx4_codes8(f, amax, e);
 }
 
 static inline bool mx4_quant_args_ok(const void* x, const void* codes, const void* scales, int64_t M, int K, int64_t ldx, int64_t ldq,

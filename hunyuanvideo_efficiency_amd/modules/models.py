@@ -22,7 +22,7 @@ from typing import Any, Dict, List, Optional, Tuple, Union
 import torch
 import torch.nn as nn
 
-from .. import gemm_mx4, gemm_mx6, mx_rot, ops
+from .. import gemm_mx4, gemm_mx6, mx_lowrank, mx_rot, ops
 from ..attn_tile import model_plan
 from .attenion import get_cu_seqlens, n_valid_text, segment_attention_, pad_segment_attention_, check_fp8_attention, check_tile_plan
 from .token_refiner import SingleTokenRefiner
@@ -49,6 +49,7 @@ class _Workspace:
         self.attn8 = None       # FP8 attention (opt-in): the workspace of include/hv_attn_fp8.h, allocated on first use, grow-only
         # MXFP4 linears (opt-in, allocated on first use): e2m1 codes + E8M0 block scales of the A operands
         self.x4 = self.x4s = self.cat4 = self.cat4s = None
+        self.lr_t = None        # ... with a low-rank branch (opt-in): T = bf16(A Dn^T) [S, R] of the Linear being run
         # MXFP6 linears (opt-in, allocated on first use): dense e2m3 codes (3/4 byte per element) + E8M0 block scales of the A operands
         self.x6 = self.x6s = self.cat6 = self.cat6s = None
 
@@ -78,6 +79,12 @@ class _Workspace:
             self.cat4 = torch.empty(s, c // 2, dtype=torch.uint8, device=dev)
             self.cat4s = torch.empty(s, c // 32, dtype=torch.uint8, device=dev)
         return self
+
+
+    def lowrank_t(self, lo: int, hi: int, r: int):
+        if self.lr_t is None or self.lr_t.shape[1] < r:
+            self.lr_t = torch.empty(self.x.shape[0], r, dtype=BF16, device=self.x.device)
+        return self.lr_t[lo:hi, :r]
 
 
     def mx6_buffers(self):
@@ -148,10 +155,14 @@ def _attention(block, sp, ws: _Workspace, s_img: int, cu1: int, H: int, d: int):
                        fp8_workspace=ws.fp8_attention_workspace(cu1, H) if sp is None and cu1 > 0 else None)
 
 
-def _ln(ws: _Workspace, lo: int, hi: int, shift, scale, fp8: bool, rot: int = 0):
+def _ln(ws: _Workspace, lo: int, hi: int, shift, scale, fp8: bool, rot: int = 0, lowrank: int = 0):
     """K1 on rows [lo, hi): bf16 into ws.xmod, or (FP8-MFMA path) e4m3 + row scales into ws.xq / ws.xs, or (MXFP4) codes + block scales,
-    rotated first when the Linear that reads them was packed with rot > 0 (_mx_rot)."""
-    if fp8 == MX6:
+    rotated first when the Linear that reads them was packed with rot > 0 (_mx_rot).  MXFP4 with a low-rank branch (lowrank > 0, the
+    consuming Linear's mx_lowrank): bf16 into ws.xmod as on the bf16 path - _gemm quantises it while it down-projects it, one more bf16
+    write and read per LayerNorm than the fused MXFP4 form; the LayerNorm is not fused into that pass."""
+    if fp8 == MX4 and lowrank:
+        ops.ln_modulate(ws.x[lo:hi], shift, scale, out=ws.xmod[lo:hi])
+    elif fp8 == MX6:
         ws.mx6_buffers()
         gemm_mx6.ln_modulate_mxfp6(ws.x[lo:hi], shift, scale, codes=ws.x6[lo:hi], scales=ws.x6s[lo:hi])
     elif fp8 == MX4:
@@ -185,6 +196,15 @@ def _gemm(ws: _Workspace, layer, src: str, lo: int, hi: int, fp8: bool, wrows: O
         return gemm_mx6.gemm_mxfp6(a6, a6s, layer.weight, layer.mx_scale, b, **epi)
     if fp8 == MX4:       # MXFP4: LayerNorm outputs are already codes; the other A operands are quantised here, per block of 32
         ws.mx4_buffers()
+        r = getattr(layer, "mx_lowrank", 0)
+        if r:            # low-rank branch: every LayerNorm output and cat slice has exactly one consuming Linear, so nothing is shared
+            if src == "xmod":
+                a, out = ws.xmod[lo:hi], dict(codes=ws.x4[lo:hi], scales=ws.x4s[lo:hi])
+            else:
+                c0, c1 = cols.indices(ws.cat.shape[1])[:2]
+                a, out = ws.cat[lo:hi, cols], dict(codes=ws.cat4[lo:hi, c0 // 2:c1 // 2], scales=ws.cat4s[lo:hi, c0 // 32:c1 // 32])
+            a4, a4s, t = mx_lowrank.quant_rows_mxfp4_lr(a, layer.mx_lr_dn, t=ws.lowrank_t(lo, hi, r), **out)
+            return mx_lowrank.gemm_mxfp4_lr(a4, a4s, layer.weight, layer.mx_scale, t, layer.mx_lr_up, b, **epi)
         if src == "xmod":
             a4, a4s = ws.x4[lo:hi], ws.x4s[lo:hi]
         else:
@@ -279,7 +299,7 @@ class MMDoubleStreamBlock(nn.Module):
             mods[s] = [m[0, i * d:(i + 1) * d] for i in range(6)]   # shift1, scale1, gate1, shift2, scale2, gate2
             sh1, sc1 = mods[s][0], mods[s][1]
             qkv_l = getattr(self, f"{s}_attn_qkv")
-            _ln(ws, lo, hi, sh1, sc1, fp8[s], _mx_rot(qkv_l))
+            _ln(ws, lo, hi, sh1, sc1, fp8[s], _mx_rot(qkv_l), getattr(qkv_l, "mx_lowrank", 0))
             qw, kw = getattr(self, f"{s}_attn_q_norm").weight, getattr(self, f"{s}_attn_k_norm").weight
             if overlap and s == "img":
                 # q / k / v as three column-chunk GEMMs; each chunk's all-to-all travels while the next chunk's GEMM runs
@@ -306,7 +326,7 @@ class MMDoubleStreamBlock(nn.Module):
                     _gemm(ws, proj, "attn", r0, r1, fp8[s], out=ws.x[r0:r1], gate=g1, res=ws.x[r0:r1])
             else:
                 _gemm(ws, proj, "attn", lo, hi, fp8[s], out=x, gate=g1, res=x)
-            _ln(ws, lo, hi, sh2, sc2, fp8[s], _mx_rot(mlp.fc1))
+            _ln(ws, lo, hi, sh2, sc2, fp8[s], _mx_rot(mlp.fc1), getattr(mlp.fc1, "mx_lowrank", 0))
             _gemm(ws, mlp.fc1, "xmod", lo, hi, fp8[s], out=ws.cat[lo:hi, d:], act=ops.ACT_GELU_TANH)
             _gemm(ws, mlp.fc2, "hid", lo, hi, fp8[s], out=x, gate=g2, res=x)
 
@@ -361,7 +381,7 @@ class MMSingleStreamBlock(nn.Module):
         sp = self.hybrid_seq_parallel_attn
         fp8 = _linear_mode(self, sp, self.linear1, self.linear2)
         s_all = ws.x.shape[0]
-        _ln(ws, 0, s_all, shift, scale, fp8, _mx_rot(self.linear1))
+        _ln(ws, 0, s_all, shift, scale, fp8, _mx_rot(self.linear1), getattr(self.linear1, "mx_lowrank", 0))
         check_fp8_attention(bool(getattr(self, "fp8_attention", False)), sp)
         check_tile_plan(ws.tile_plan if getattr(self, "sliding_tile", False) else None, bool(getattr(self, "fp8_attention", False)), sp)
         n_rope = s_img if cos is not None else 0

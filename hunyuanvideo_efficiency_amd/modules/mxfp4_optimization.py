@@ -2,13 +2,15 @@
 activations quantised the same way, on v_mfma_scale_f32_16x16x128_f8f6f4.  Not the reference's arithmetic: round-to-nearest e2m1 on both
 operands carries roughly 10 % relative noise per element.  convert_mxfp4_linear(rot=16 / 64 / 256) rotates both operands by a
 block-diagonal Hadamard matrix along K (include/hv_mx_rot.h), which spreads outlier channels over their group and changes nothing on
-Gaussian data; nothing else here (low-rank branches, calibration) reduces the noise, and no run on real weights has measured video
-fidelity under either form."""
+Gaussian data.  convert_mxfp4_linear(lowrank=32 / 64 / 96 / 128) splits W = Up Dn + Res by an SVD, packs only Res and multiplies the
+rank-R part in bf16 from the unquantised activations (include/hv_mx_lowrank.h), which removes the error of a weight's dominant directions
+(about ninefold on a weight with a strong rank-4 part, by the share of the spectrum R directions carry on a Gaussian one).  Nothing here
+calibrates on data, and no run on real weights has measured video fidelity under any of these forms."""
 from __future__ import annotations
 
 import torch
 
-from .. import gemm_mx4, mx_rot
+from .. import gemm_mx4, mx_lowrank, mx_rot
 from .layers import ParamLinear
 
 FLAG = "--mxfp4-linears"
@@ -26,12 +28,19 @@ def _gemm_linears(block):
                                                 getattr(block, f"{s}_mlp").fc1, getattr(block, f"{s}_mlp").fc2)]
 
 
-def convert_mxfp4_linear(module, rot: int = 0) -> int:
+def convert_mxfp4_linear(module, rot: int = 0, lowrank: int = 0) -> int:
     """Pack qkv / proj / fc1 / fc2 per stream of every double block and linear1 / linear2 of every single block: layer.weight becomes the
     uint8 codes [out, in / 2], layer.mx_scale the uint8 scales [out, in / 32]; the bf16 weight is released.  A layer has ONE stored
     format: a model converted by convert_fp8_linear is refused.  rot > 0 (16, 64 or 256) packs W H instead of W, H the block-diagonal
     Hadamard rotation of include/hv_mx_rot.h, and records layer.mx_rot: models._ln / models._gemm then quantise the layer's activations
-    through the rotated quantisers, (A H)(W H)^T = A W^T.  Returns the number of layers packed."""
+    through the rotated quantisers, (A H)(W H)^T = A W^T.  lowrank > 0 (32, 64, 96 or 128) packs Res of W = Up Dn + Res
+    (mx_lowrank.factorise: a deterministic fp32 SVD per layer) and stores layer.mx_lr_up [out, R], layer.mx_lr_dn [R, in] and
+    layer.mx_lowrank: models._gemm then runs the layer through the two kernels of include/hv_mx_lowrank.h.  rot and lowrank together
+    are not built.  Returns the number of layers packed."""
+    if lowrank not in (0,) + mx_lowrank.RANKS:
+        raise ValueError(f"lowrank must be 0 or one of {mx_lowrank.RANKS}, got {lowrank}")
+    if rot and lowrank:
+        raise ValueError("rot > 0 together with lowrank > 0 is not built: the down-projection would have to read the unrotated rows")
     if rot not in (0,) + mx_rot.ROTS:
         raise ValueError(f"rot must be 0 or one of {mx_rot.ROTS}, got {rot}")
     if getattr(module, "fp8_matmul_enabled", False):
@@ -44,10 +53,14 @@ def convert_mxfp4_linear(module, rot: int = 0) -> int:
         if rot and layer.in_features % rot:
             raise ValueError(f"rot = {rot} does not divide in_features = {layer.in_features}: rotation groups are whole")
     for layer in layers:
-        codes, scales = mx_rot.quant_rows_mxfp4_rot(layer.weight.data, rot) if rot else gemm_mx4.quant_rows_mxfp4(layer.weight.data)
+        w = layer.weight.data
+        if lowrank:
+            layer.mx_lr_up, layer.mx_lr_dn, w = mx_lowrank.factorise(w, lowrank)
+        codes, scales = mx_rot.quant_rows_mxfp4_rot(w, rot) if rot else gemm_mx4.quant_rows_mxfp4(w)
         layer.weight = torch.nn.Parameter(codes, requires_grad=False)
         layer.mx_scale = scales
         layer.mx_rot = rot
+        layer.mx_lowrank = lowrank
     module.mxfp4_linears_converted = True
     return len(layers)
 

@@ -52,6 +52,10 @@ def parse_args(argv=None):
                    "both GEMM operands by a block-diagonal Hadamard matrix over groups of this many consecutive k (include/hv_mx_rot.h) - "
                    "the weights when they are packed, the activations inside their quantiser passes; it spreads outlier channels over "
                    "their group (no gain on Gaussian activations; video fidelity not measured)")
+    p.add_argument("--mxfp4-lowrank", type=int, choices=(32, 64, 96, 128), default=0, metavar="{32,64,96,128}", help="with --mxfp4-linears: "
+                   "split every packed weight W = Up Dn + Res by an SVD, pack only Res and multiply the rank-R part in bf16 from the "
+                   "unquantised activations, folded into the GEMM (include/hv_mx_lowrank.h); not available with --mxfp4-rotate (video "
+                   "fidelity not measured)")
     p.add_argument("--mxfp6-linears", action="store_true", help="pack the block GEMM weights as MXFP6 (dense 6-bit e2m3 codes, one E8M0 scale per "
                    "32) and run them with MXFP6 activations on the CDNA4 block-scaled matrix cores (include/hv_gemm_mx6.h) - an opt-in "
                    "approximation whose video fidelity has not been measured; not available with --use-fp8, --mxfp4-linears or "
@@ -102,6 +106,8 @@ def parse_args(argv=None):
         p.error("--mxfp4-linears and --use-fp8 exclude each other: a layer has one stored format")
     if a.mxfp4_rotate and not a.mxfp4_linears:
         p.error("--mxfp4-rotate is only valid with --mxfp4-linears")
+    if a.mxfp4_lowrank and (not a.mxfp4_linears or a.mxfp4_rotate or a.mxfp6_linears or a.use_fp8):
+        p.error("--mxfp4-lowrank is only valid with --mxfp4-linears and excludes --mxfp4-rotate, --mxfp6-linears and --use-fp8")
     if a.mxfp6_linears and (a.use_fp8 or a.mxfp4_linears):
         p.error("--mxfp6-linears excludes --use-fp8 and --mxfp4-linears: a layer has one stored format")
     if a.save_chroma is not None and a.save_format not in ("y4m", "yuv"):
@@ -150,7 +156,7 @@ def main(argv=None):
         convert_fp8_linear(model, None, torch.bfloat16)
     if a.mxfp4_linears:
         from hunyuanvideo_efficiency_amd.modules.mxfp4_optimization import convert_mxfp4_linear, enable_mxfp4_linears
-        convert_mxfp4_linear(model, rot=a.mxfp4_rotate)
+        convert_mxfp4_linear(model, rot=a.mxfp4_rotate, lowrank=a.mxfp4_lowrank)
         enable_mxfp4_linears(model)
     if a.mxfp6_linears:
         from hunyuanvideo_efficiency_amd.modules.mxfp6_optimization import convert_mxfp6_linear, enable_mxfp6_linears
