@@ -79,6 +79,9 @@ MX_ROT_RESTYPES = {name: _ctype(ret, name) for ret, name, _ in _abi.MX_ROT_DECLS
 # and for include/hv_mx_lowrank.h
 MX_LOWRANK_SIGNATURES = {name: [_ctype(t, f"{name}({p})") for t, p in params] for _, name, params in _abi.MX_LOWRANK_DECLS}
 MX_LOWRANK_RESTYPES = {name: _ctype(ret, name) for ret, name, _ in _abi.MX_LOWRANK_DECLS}
+# and for include/hv_attn_select.h
+ATTN_SELECT_SIGNATURES = {name: [_ctype(t, f"{name}({p})") for t, p in params] for _, name, params in _abi.ATTN_SELECT_DECLS}
+ATTN_SELECT_RESTYPES = {name: _ctype(ret, name) for ret, name, _ in _abi.ATTN_SELECT_DECLS}
 _lib = _hv = None       # the loaded ctypes handle / torch.ops.hv namespace
 
 
@@ -103,13 +106,13 @@ def load():
             list(GSSIM_SIGNATURES.items()) + list(YUVW_SIGNATURES.items()) + list(MOTION_SIGNATURES.items()) + list(MJPEG_SIGNATURES.items()) + \
             list(MJPEG_READ_SIGNATURES.items()) + list(MJPEG_SYNC_SIGNATURES.items()) + list(ATTN_FP8_SIGNATURES.items()) + \
             list(ATTN_TILE_SIGNATURES.items()) + list(GEMM_MX4_SIGNATURES.items()) + list(GEMM_MX6_SIGNATURES.items()) + \
-            list(MX_ROT_SIGNATURES.items()) + list(MX_LOWRANK_SIGNATURES.items()):
+            list(MX_ROT_SIGNATURES.items()) + list(MX_LOWRANK_SIGNATURES.items()) + list(ATTN_SELECT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
             raise HVKernelError(f"{LIB_PATH} does not export {name}") from e
         fn.argtypes = argtypes
-        fn.restype = {**MX_LOWRANK_RESTYPES, **MX_ROT_RESTYPES, **GEMM_MX6_RESTYPES, **GEMM_MX4_RESTYPES, **ATTN_TILE_RESTYPES, **ATTN_FP8_RESTYPES, **MJPEG_SYNC_RESTYPES, **MJPEG_READ_RESTYPES, **MJPEG_RESTYPES, **MOTION_RESTYPES, **YUVW_RESTYPES, **GSSIM_RESTYPES, **TEMPORAL_RESTYPES, **CONTENT_RESTYPES, **RESTYPES}[name]
+        fn.restype = {**ATTN_SELECT_RESTYPES, **MX_LOWRANK_RESTYPES, **MX_ROT_RESTYPES, **GEMM_MX6_RESTYPES, **GEMM_MX4_RESTYPES, **ATTN_TILE_RESTYPES, **ATTN_FP8_RESTYPES, **MJPEG_SYNC_RESTYPES, **MJPEG_READ_RESTYPES, **MJPEG_RESTYPES, **MOTION_RESTYPES, **YUVW_RESTYPES, **GSSIM_RESTYPES, **TEMPORAL_RESTYPES, **CONTENT_RESTYPES, **RESTYPES}[name]
     v = lib.hv_abi_version()
     if v != ABI_VERSION:
         raise HVKernelError(f"libhv_kernels ABI {v} != expected {ABI_VERSION}: rebuild the extension")
@@ -147,7 +150,7 @@ def torch_ops():
     for name in list(SIGNATURES) + list(CONTENT_SIGNATURES) + list(TEMPORAL_SIGNATURES) + list(GSSIM_SIGNATURES) + list(YUVW_SIGNATURES) + \
             list(MOTION_SIGNATURES) + list(MJPEG_SIGNATURES) + list(MJPEG_READ_SIGNATURES) + list(MJPEG_SYNC_SIGNATURES) + list(ATTN_FP8_SIGNATURES) + \
             list(ATTN_TILE_SIGNATURES) + list(GEMM_MX4_SIGNATURES) + list(GEMM_MX6_SIGNATURES) + list(MX_ROT_SIGNATURES) + \
-            list(MX_LOWRANK_SIGNATURES):
+            list(MX_LOWRANK_SIGNATURES) + list(ATTN_SELECT_SIGNATURES):
         if not hasattr(hv, name[len("hv_"):]):
             raise HVKernelError(f"{TORCH_OPS_PATH} does not register torch.ops.hv.{name[len('hv_'):]}")
     _hv = hv

@@ -106,6 +106,9 @@ def enable_sliding_tile_attention(model, tile=(4, 8, 8), window=(3, 3, 3), enabl
     triple or one per head.  The default tile (4, 8, 8) makes a full tile one 256-row workgroup and four full key chunks.  An
     approximation of the model, not the reference's arithmetic; no fidelity of generated video has been measured under any window.
     Together with sequence parallelism or fp8_attention the blocks raise NotImplementedError.  Returns the number of blocks."""
+    if enable and getattr(model, "adaptive_tile", None) is not None:
+        raise ValueError("enable_sliding_tile_attention: enable_adaptive_tile_attention (attn_select.py) is on for this model; a block "
+                         "has one source of key-tile lists: switch that one off first")
     n = 0
     for _, block in model.named_modules():
         if hasattr(block, "hybrid_seq_parallel_attn") and hasattr(block, "run"):

@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import gemm_mx4, gemm_mx6, mx_lowrank, mx_rot, ops
+from ..attn_select import model_state as adaptive_state
 from ..attn_tile import model_plan
 from .attenion import get_cu_seqlens, n_valid_text, segment_attention_, pad_segment_attention_, check_fp8_attention, check_tile_plan
 from .token_refiner import SingleTokenRefiner
@@ -46,6 +47,7 @@ class _Workspace:
         # FP8-MFMA path (allocated on first use): per-token quantised A operands + their row scales
         self.xq = self.xs = self.catq = self.cats = None
         self.tile_plan = None   # sliding-tile attention (opt-in): the plan of this forward's token grid, set by the transformer's forward
+        self.adaptive = None    # adaptive tile attention (opt-in): the base plan and list buffers of this forward's token grid, likewise
         self.attn8 = None       # FP8 attention (opt-in): the workspace of include/hv_attn_fp8.h, allocated on first use, grow-only
         # MXFP4 linears (opt-in, allocated on first use): e2m1 codes + E8M0 block scales of the A operands
         self.x4 = self.x4s = self.cat4 = self.cat4s = None
@@ -138,9 +140,29 @@ def _use_fp8_mfma(block, *layers) -> bool:
         l.weight.dtype == torch.float8_e4m3fn and l.in_features >= 384 and l.in_features % 128 == 0 for l in layers)
 
 
+def _block_plan(block, ws: _Workspace):
+    """the tile plan whose refusals (attenion.check_tile_plan) hold for this block: the sliding-tile plan, or the base plan of adaptive
+    tile attention; None for a block under neither flag"""
+    if getattr(block, "sliding_tile", False):
+        return ws.tile_plan
+    if getattr(block, "adaptive_tile", False) and ws.adaptive is not None:
+        return ws.adaptive.base
+    return None
+
+
 def _attention(block, sp, ws: _Workspace, s_img: int, cu1: int, H: int, d: int):
     """segment_attention_ with the block's opt-in flags: FP8 attention (fp8_optimization.enable_fp8_attention) and sliding-tile
-    attention (attn_tile.enable_sliding_tile_attention; the plan waits in ws.tile_plan)"""
+    attention (attn_tile.enable_sliding_tile_attention; the plan waits in ws.tile_plan), or adaptive tile attention
+    (attn_select.enable_adaptive_tile_attention): the same kernel under lists chosen here, from this block's q and k"""
+    if getattr(block, "adaptive_tile", False):
+        if ws.adaptive is None:
+            raise RuntimeError("adaptive tile attention is enabled on this block but no base plan was built: run the block through "
+                               "HYVideoDiffusionTransformer.forward, which knows the token grid")
+        fp8a = bool(getattr(block, "fp8_attention", False))
+        check_tile_plan(ws.adaptive.base, fp8a, sp)                         # before the selection runs: the refusals of a tile plan
+        plan = ws.adaptive.select(ws.qkv[:s_img, :d], ws.qkv[:s_img, d:2 * d], H)
+        segment_attention_(sp, ws.qkv, ws.cat, s_img, cu1, H, d, fp8_attention=fp8a, tile_plan=plan)
+        return
     if getattr(block, "sliding_tile", False):
         if ws.tile_plan is None:
             raise RuntimeError("sliding-tile attention is enabled on this block but no tile plan was built: run the block through "
@@ -288,7 +310,7 @@ class MMDoubleStreamBlock(nn.Module):
         streams = (("txt", s_img, s_img + s_txt, 0), ("img", 0, s_img, s_img if cos is not None else 0))
         sp = self.hybrid_seq_parallel_attn
         check_fp8_attention(bool(getattr(self, "fp8_attention", False)), sp)
-        check_tile_plan(ws.tile_plan if getattr(self, "sliding_tile", False) else None, bool(getattr(self, "fp8_attention", False)), sp)
+        check_tile_plan(_block_plan(self, ws), bool(getattr(self, "fp8_attention", False)), sp)
         overlap = sp is not None and hasattr(sp, "send") and H % 2 == 0
         mods = {}
         fp8 = {s: _linear_mode(self, sp, getattr(self, f"{s}_attn_qkv"), getattr(self, f"{s}_attn_proj"), getattr(self, f"{s}_mlp").fc1,
@@ -383,7 +405,7 @@ class MMSingleStreamBlock(nn.Module):
         s_all = ws.x.shape[0]
         _ln(ws, 0, s_all, shift, scale, fp8, _mx_rot(self.linear1), getattr(self.linear1, "mx_lowrank", 0))
         check_fp8_attention(bool(getattr(self, "fp8_attention", False)), sp)
-        check_tile_plan(ws.tile_plan if getattr(self, "sliding_tile", False) else None, bool(getattr(self, "fp8_attention", False)), sp)
+        check_tile_plan(_block_plan(self, ws), bool(getattr(self, "fp8_attention", False)), sp)
         n_rope = s_img if cos is not None else 0
         if sp is not None and hasattr(sp, "send") and H % 2 == 0:
             # sequence parallel: q | k | v | mlp as four column-chunk GEMMs of linear1; the all-to-all of each attention chunk
@@ -539,6 +561,7 @@ class HYVideoDiffusionTransformer(nn.Module):
         s_img, s_txt, d = tt * th * tw, text_states.shape[1], self.hidden_size
         ws = self._workspace(s_img, s_txt, dev)
         ws.tile_plan = model_plan(self, (tt, th, tw), dev)               # None unless enable_sliding_tile_attention was called
+        ws.adaptive = adaptive_state(self, (tt, th, tw), self.heads_num, dev)    # None unless enable_adaptive_tile_attention was called
 
         # ---- modulation vector (models.py:618-631)
         t32 = t.reshape(-1).to(torch.float32)

@@ -70,6 +70,16 @@ def parse_args(argv=None):
                    "tile along (t, h, w), at most 256 in all (default 4 8 8)")
     p.add_argument("--sta-window", type=int, nargs=3, default=None, metavar=("T", "H", "W"), help="with --sliding-tile-attention: tiles per "
                    "window along (t, h, w) (default 3 3 3)")
+    p.add_argument("--adaptive-tile-attention", action="store_true", help="as --sliding-tile-attention, but every block chooses its key "
+                   "tiles per head on the GPU from the pooled Q.K of the call (include/hv_attn_select.h) - an opt-in approximation whose "
+                   "effect on generated video has not been measured; not available with --sliding-tile-attention, --fp8-attention or "
+                   "--ulysses-degree / --ring-degree > 1")
+    p.add_argument("--ata-tile", type=int, nargs=3, default=None, metavar=("T", "H", "W"), help="with --adaptive-tile-attention: tokens "
+                   "per tile along (t, h, w), at most 256 in all (default 4 8 8)")
+    p.add_argument("--ata-cdf", type=float, default=None, help="with --adaptive-tile-attention: the pooled softmax mass the kept tiles "
+                   "must reach, in (0, 1] (default 0.9)")
+    p.add_argument("--ata-kmin", type=int, default=None, help="with --adaptive-tile-attention: the fewest key tiles per list (default 1)")
+    p.add_argument("--ata-kmax", type=int, default=None, help="with --adaptive-tile-attention: the most key tiles per list (default: all)")
     p.add_argument("--ulysses-degree", type=int, default=1)
     p.add_argument("--ring-degree", type=int, default=1)
     p.add_argument("--text-len", type=int, default=256)
@@ -102,6 +112,10 @@ def parse_args(argv=None):
     a = p.parse_args(argv)
     if (a.sta_tile is not None or a.sta_window is not None) and not a.sliding_tile_attention:
         p.error("--sta-tile and --sta-window are only valid with --sliding-tile-attention")
+    if any(x is not None for x in (a.ata_tile, a.ata_cdf, a.ata_kmin, a.ata_kmax)) and not a.adaptive_tile_attention:
+        p.error("--ata-tile, --ata-cdf, --ata-kmin and --ata-kmax are only valid with --adaptive-tile-attention")
+    if a.adaptive_tile_attention and a.sliding_tile_attention:
+        p.error("--adaptive-tile-attention and --sliding-tile-attention exclude each other: a block has one source of key-tile lists")
     if a.mxfp4_linears and a.use_fp8:
         p.error("--mxfp4-linears and --use-fp8 exclude each other: a layer has one stored format")
     if a.mxfp4_rotate and not a.mxfp4_linears:
@@ -168,6 +182,10 @@ def main(argv=None):
     if a.sliding_tile_attention:
         from hunyuanvideo_efficiency_amd.attn_tile import enable_sliding_tile_attention
         enable_sliding_tile_attention(model, tuple(a.sta_tile or (4, 8, 8)), tuple(a.sta_window or (3, 3, 3)))
+    if a.adaptive_tile_attention:
+        from hunyuanvideo_efficiency_amd.attn_select import enable_adaptive_tile_attention
+        enable_adaptive_tile_attention(model, tuple(a.ata_tile or (4, 8, 8)), 0.9 if a.ata_cdf is None else a.ata_cdf,
+                                       1 if a.ata_kmin is None else a.ata_kmin, a.ata_kmax)
     if a.vae_path:
         from hunyuanvideo_efficiency_amd.vae import load_vae
         vae = load_vae(a.vae, a.vae_precision, vae_path=a.vae_path, device=dev)[0]

@@ -17,12 +17,13 @@ host tables, const uint8_t* huff_tables / quant_tables, are int[] of the header'
 those of include/hv_mjpeg_sync.h to csrc/hv_mjpeg_sync_torch_ops.cpp, those of include/hv_attn_fp8.h to csrc/hv_attn_fp8_torch_ops.cpp,
 those of include/hv_attn_tile.h to csrc/hv_attn_tile_torch_ops.cpp, those of include/hv_gemm_mx4.h to csrc/hv_gemm_mx4_torch_ops.cpp,
 those of include/hv_gemm_mx6.h to csrc/hv_gemm_mx6_torch_ops.cpp, those of include/hv_mx_rot.h to csrc/hv_mx_rot_torch_ops.cpp,
-those of include/hv_mx_lowrank.h to csrc/hv_mx_lowrank_torch_ops.cpp.
-Run:  python tools/gen_torch_ops.py            (rewrites the fifteen .cpp files; tests/test_capi_cpu.py, tests/test_content_refusals_cpu.py,
+those of include/hv_mx_lowrank.h to csrc/hv_mx_lowrank_torch_ops.cpp, those of include/hv_attn_select.h to
+csrc/hv_attn_select_torch_ops.cpp.
+Run:  python tools/gen_torch_ops.py            (rewrites the sixteen .cpp files; tests/test_capi_cpu.py, tests/test_content_refusals_cpu.py,
                                                 tests/test_temporal_refusals_cpu.py, tests/test_gssim_refusals_cpu.py,
                                                 tests/test_yuv_write_refusals_cpu.py, tests/test_motion_refusals_cpu.py and
                                                 tests/test_mjpeg_refusals_cpu.py, tests/test_mjpeg_read_refusals_cpu.py and
-                                                tests/test_mjpeg_sync_cpu.py, tests/test_attn_fp8_cpu.py, tests/test_attn_tile_cpu.py, tests/test_gemm_mx4_cpu.py, tests/test_gemm_mx6_cpu.py, tests/test_mx_rot_cpu.py, tests/test_mx_lowrank_cpu.py check they are up to date)
+                                                tests/test_mjpeg_sync_cpu.py, tests/test_attn_fp8_cpu.py, tests/test_attn_tile_cpu.py, tests/test_gemm_mx4_cpu.py, tests/test_gemm_mx6_cpu.py, tests/test_mx_rot_cpu.py, tests/test_mx_lowrank_cpu.py, tests/test_attn_select_cpu.py check they are up to date)
       python tools/gen_torch_ops.py --record-abi    (after a bump of HV_ABI_VERSION: writes tests/golden/abi_v<N>.json, the
                                                       declarations the same test holds the header to until the next bump)
 """
@@ -50,6 +51,7 @@ GEMM_MX4_OUT = os.path.join(ROOT, "hunyuanvideo_efficiency_amd", "csrc", "hv_gem
 GEMM_MX6_OUT = os.path.join(ROOT, "hunyuanvideo_efficiency_amd", "csrc", "hv_gemm_mx6_torch_ops.cpp")   # from include/hv_gemm_mx6.h
 MX_ROT_OUT = os.path.join(ROOT, "hunyuanvideo_efficiency_amd", "csrc", "hv_mx_rot_torch_ops.cpp")   # from include/hv_mx_rot.h
 MX_LOWRANK_OUT = os.path.join(ROOT, "hunyuanvideo_efficiency_amd", "csrc", "hv_mx_lowrank_torch_ops.cpp")   # from include/hv_mx_lowrank.h
+ATTN_SELECT_OUT = os.path.join(ROOT, "hunyuanvideo_efficiency_amd", "csrc", "hv_attn_select_torch_ops.cpp")   # from include/hv_attn_select.h
 HOST_BYTES = {"huff_tables": _abi.MJPEG_READ_MACROS["HV_MJPEG_HUFF_BYTES"], "quant_tables": _abi.MJPEG_READ_MACROS["HV_MJPEG_QUANT_BYTES"]}
 HOST_ARRAYS = {"a_strides", "b_strides", "src_strides", "dst_strides", "dims"}
 HOST_ARRAY_LEN = 4      # every host array of the C ABI is a 4-vector (hv_vae_blend_f16, hv_copy4d_16b: strides / dims of a 4-D view)
@@ -227,7 +229,8 @@ if __name__ == "__main__":
                        (GEMM_MX4_OUT, gen(_abi.GEMM_MX4_DECLS, "hv_gemm_mx4.h")),
                        (GEMM_MX6_OUT, gen(_abi.GEMM_MX6_DECLS, "hv_gemm_mx6.h")),
                        (MX_ROT_OUT, gen(_abi.MX_ROT_DECLS, "hv_mx_rot.h")),
-                       (MX_LOWRANK_OUT, gen(_abi.MX_LOWRANK_DECLS, "hv_mx_lowrank.h"))):
+                       (MX_LOWRANK_OUT, gen(_abi.MX_LOWRANK_DECLS, "hv_mx_lowrank.h")),
+                       (ATTN_SELECT_OUT, gen(_abi.ATTN_SELECT_DECLS, "hv_attn_select.h"))):
         with open(path, "w") as f:
             f.write(text)
         print(f"wrote {path}: {text.count('m.def(')} ops")
